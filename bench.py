@@ -9,14 +9,21 @@ registerFeatures(source, target, identity) for every pair of the batch, through 
 the only communication is the gather of the 64-byte result records: RCCL behind the C ABI,
 loamx_gather_results_dev, inside the timed step).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process starts the N ranks itself
 (`python -m torch.distributed.run` as a CHILD process, before torch or HIP are touched here) and exits
 with the child's code.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with extra objects:
+A plain run sets up, warms up, times K steps and prints ONE JSON line on rank 0: metric, value, unit,
+higher_is_better, dtype, ms_per_step (wall time of one timed step) and the configuration.
+`--dump-outputs DIR` then also writes the result records of the last timed step (every pair of the step,
+gathered over the ranks), as the caller of the path receives them: DIR/pose.npy (float64, pairs x 7:
+qx qy qz qw tx ty tz), DIR/termination.npy and DIR/iterations.npy (float64, one per pair). The scans
+are synthesised from --seed, so the same arguments give the same inputs on every run.
+
+`--full` adds, after the timed steps, the objects below (--no-kernel-stats, --no-cpu-baseline, --no-streamed leave out the first three):
   roofline     — dominant kernel scope: algorithmic bytes per launch / average launch duration measured
                  with HIP events on the launch stream, vs 8 TB/s HBM peak; `compute` = vector-instruction
                  roofline of the (instruction-bound) k-NN kernel from the committed PMC pass
@@ -25,6 +32,7 @@ Prints ONE JSON line on rank 0 (contract in the task description) with extra obj
   extra        — streamed: the same pairs from PINNED HOST memory to host results (loamx_register_scan_pairs: chunked uploads on
                  a copy stream under the kernels), double and float scans: pairs/s and the PCIe rate reached, + the latency of
                  one pair from host buffers. Never `value`: the headline is device-resident
+  results      — terminations and mean ICF iterations of the batch
   ranks        — (N > 1) what RCCL reported: communicator size, the gathered rank ids and devices
 """
 import argparse
@@ -73,7 +81,25 @@ def parse_args():
     ap.add_argument("--no-streamed", action="store_true",
                     help="skip the host-memory figure (extra.streamed: loamx_register_scan_pairs from pinned host scans, N = 1 only)")
     ap.add_argument("--streamed-pairs", type=int, default=512, help="pairs per call of the streamed figure (pinned host copy: 3.1 MB per pair)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: per-kernel event pass and "
+                         "roofline, results summary, CPU baseline + parity, streamed figure, gather proof of the ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result records of the last timed step as DIR/pose.npy, termination.npy, iterations.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def dump_outputs(d, rec):
+    """The records of the last timed step (RESULT_DTYPE, every pair of the step) as float64 arrays: 72 B per pair. The scans
+    of a step are resident in HBM at 3.1 MB per pair, so 8 GPUs of 288 GB hold fewer than 750 k pairs: < 54 MB of output."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "pose.npy"), np.ascontiguousarray(rec["pose"], dtype=np.float64))
+    np.save(os.path.join(d, "termination.npy"), rec["termination"].astype(np.float64))
+    np.save(os.path.join(d, "iterations.npy"), rec["iterations"].astype(np.float64))
 
 
 def fan_out(args):
@@ -275,11 +301,17 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share_gpu else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    res_all = res = None
+    if args.full or args.dump_outputs:  # what the last timed step handed its caller: every rank's records, gathered
+        res_all = all_results.cpu().numpy().view(capi.RESULT_DTYPE)
+        res = res_all[first_pair:first_pair + P]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res_all)
 
     # ---- per-kernel pass: the same steps again with HIP events on the kernels (outside the headline timing: a
     # timed dispatch carries a completion signal, which costs ~2.5 % of the step) ------------------------------------
     stats, stat_steps = {}, 0
-    if not args.no_kernel_stats:
+    if args.full and not args.no_kernel_stats:
         stat_steps = max(1, min(args.steps, 3))
         ctx.enable_kernel_timing(True)
         ctx.reset_kernel_stats()
@@ -289,10 +321,8 @@ def main():
         stats = ctx.kernel_stats()
         ctx.enable_kernel_timing(False)
 
-    res_all = all_results.cpu().numpy().view(capi.RESULT_DTYPE)
-    res = res_all[first_pair:first_pair + P]
     ranks = None
-    if world > 1:
+    if args.full and world > 1:
         # what the collective saw: every rank contributes one record {rank, device}; gathered through the same entry point
         proof = np.zeros(1, dtype=capi.RESULT_DTYPE)
         proof["termination"], proof["iterations"] = rank, dev_index
@@ -414,12 +444,13 @@ def main():
                 roofline["traffic_note"] = f"no usable PMC file ({type(e).__name__})"
             out["roofline"] = roofline
             out["kernels"] = kern
-        out["results"] = {"converged": int((res["termination"] == 0).sum()), "max_iter": int((res["termination"] == 1).sum()),
-                          "insufficient": int((res["termination"] == 2).sum()),
-                          "mean_icf_iterations": round(float(res["iterations"].mean()), 3)}
+        if args.full:
+            out["results"] = {"converged": int((res["termination"] == 0).sum()), "max_iter": int((res["termination"] == 1).sum()),
+                              "insufficient": int((res["termination"] == 2).sum()),
+                              "mean_icf_iterations": round(float(res["iterations"].mean()), 3)}
 
         # ---- CPU baseline + parity spot check (outside the timed region) -----------------------------
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             import oracle_lib as O
             affinity = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
             quota = cgroup_cpu_quota()  # the GPU box hands one GPU's share of the host: 16 of its 256 CPUs
@@ -454,7 +485,7 @@ def main():
                              "tolerance": 1e-5, "termination_and_iterations_equal": bool(term_equal),
                              "feature_index_sequences_equal": idx_equal}
         # ---- the streamed figure (outside the headline: SURVEY 8d prices inputs resident in HBM) -------------
-        if n_gpus == 1 and not args.no_streamed:
+        if args.full and n_gpus == 1 and not args.no_streamed:
             try:
                 out["extra"] = {"streamed": streamed_figure(ctx, capi, xyz, min(P, max(1, args.streamed_pairs)), lidar, fe, reg, f32, res)}
             except Exception as e:  # (e.g. no room for the pinned copy on this host)

@@ -90,3 +90,12 @@ def test_total_pairs_flag_shards_a_fixed_total():
     """bench.py --total-pairs T (strong scaling): the help text names it and the launcher passes it through to the ranks"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert "--total-pairs" in out.stdout
+
+
+def test_full_and_dump_outputs_flags_and_step_count():
+    """bench.py: `--full` (the figures beyond the headline) and `--dump-outputs DIR` are offered; `--steps` below 1 is
+    refused before anything is set up"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--steps must be >= 1" in out.stderr

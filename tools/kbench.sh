@@ -1,8 +1,9 @@
 #!/bin/bash
-# quick A/B on the GPU box: tools/kbench.sh <tag> [bench args] — bench line summary into gpurun_out/<tag>.txt
+# quick A/B on the GPU: tools/kbench.sh <tag> [bench args] — bench line summary into bench_out/<tag>.txt
 tag=${1:-kb}; shift
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-streamed "$@" > gpurun_out/$tag.json 2> gpurun_out/$tag.err; echo "bench rc=$?"
-python3 - gpurun_out/$tag.json <<'PY' | tee gpurun_out/$tag.txt
+mkdir -p bench_out
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-streamed "$@" > bench_out/$tag.json 2> bench_out/$tag.err; echo "bench rc=$?"
+python3 - bench_out/$tag.json <<'PY' | tee bench_out/$tag.txt
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(j["value"], j["unit"], j["ms_per_step"], "ms/step", j["results"])

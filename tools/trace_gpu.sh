@@ -3,7 +3,7 @@
 set -e
 tag=${1:-t}; ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; D=$ROOT/gpurun_out/prof_$tag
 rm -rf "$D"; mkdir -p "$D"; cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$D/trace" --output-format csv -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline > "$D/bench_under_rocprof.log" 2> "$D/trace.err"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$D/trace" --output-format csv -- python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline > "$D/bench_under_rocprof.log" 2> "$D/trace.err"
 python3 - "$D" <<'PY'
 import csv,glob,sys
 f=glob.glob(sys.argv[1]+'/trace/*/*_kernel_stats.csv')[0]
