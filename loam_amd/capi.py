@@ -545,14 +545,29 @@ class Context:
     def register_scan_pairs(self, xyz, n_pairs, lidar, fe=None, reg=None, out=None):
         """Host memory in, host memory out (loamx_register_scan_pairs): xyz = a C-contiguous float64 / float32 array (or an
         integer address + dtype via `xyz=(ptr, np.float32)`) of n_pairs x 2 scans, target scan first; returns the result
-        records (RESULT_DTYPE). Pinned memory (e.g. a torch pin_memory tensor's numpy view) lets the uploads overlap."""
+        records (RESULT_DTYPE). Pinned memory (e.g. a torch pin_memory tensor's numpy view) lets the uploads overlap.
+        The address form states the buffer's element count: `xyz=(ptr, np.float32, count)`. Arguments that do not hold
+        n_pairs x 2 x H x W points, or an `out` that is not n_pairs RESULT_DTYPE records, raise ValueError before anything
+        is copied."""
         fe, reg = fe or FeatureExtractionParams(), reg or RegistrationParams()
         if isinstance(xyz, tuple):
-            ptr, dt = xyz
-            f32 = np.dtype(dt) == np.float32
+            if len(xyz) != 3:
+                raise ValueError("register_scan_pairs: the address form is xyz=(ptr, dtype, element count)")
+            ptr, dt, size = xyz
+            dt = np.dtype(dt)
         else:
-            assert xyz.flags["C_CONTIGUOUS"] and xyz.dtype in (np.float64, np.float32)
-            ptr, f32 = xyz.ctypes.data, xyz.dtype == np.float32
+            if not isinstance(xyz, np.ndarray) or not xyz.flags["C_CONTIGUOUS"]:
+                raise ValueError("register_scan_pairs: xyz must be a C-contiguous numpy array")
+            ptr, dt, size = xyz.ctypes.data, xyz.dtype, xyz.size
+        if dt not in (np.float64, np.float32):
+            raise ValueError(f"register_scan_pairs: xyz must be float64 or float32, not {dt}")
+        f32 = dt == np.float32
+        need = int(n_pairs) * 2 * int(lidar.scan_lines) * int(lidar.points_per_line) * 3
+        if int(size) < need:
+            raise ValueError(f"register_scan_pairs: xyz holds {int(size)} values, {n_pairs} pairs need {need}")
+        if out is not None and (not isinstance(out, np.ndarray) or out.dtype != RESULT_DTYPE or not out.flags["C_CONTIGUOUS"]
+                                or out.size < n_pairs):
+            raise ValueError(f"register_scan_pairs: out must be a C-contiguous array of at least {n_pairs} RESULT_DTYPE records")
         res = out if out is not None else np.zeros(n_pairs, dtype=RESULT_DTYPE)
         fn = self.lib.loamx_register_scan_pairs_f32 if f32 else self.lib.loamx_register_scan_pairs
         self._check(fn(self.h, ptr, n_pairs, C.byref(lidar), C.byref(fe), C.byref(reg), res.ctypes.data))

@@ -435,6 +435,14 @@ uint64_t hostcheck_knn(const double* pts, uint64_t n, const double q[3], uint64_
   return (uint64_t)kept;
 }
 
+// the target grid the kernels choose for a set (grid_choose over its bounding box, the scan-pair cell cap):
+// out = {h, nx, ny, nz}
+void hostcheck_grid_choose(const double* pts, uint64_t n, double max_dist, double out[4]) {
+  HostGrid G;
+  build_grid(pts, (uint32_t)n, max_dist, G);
+  out[0] = G.g.h, out[1] = G.g.nx, out[2] = G.g.ny, out[3] = G.g.nz;
+}
+
 // per-query search statistics of the keyed path (analysis only): candidates and rows visited;
 // grid_out = {nx, ny, nz, h}
 void hostcheck_knn_stats(const double* pts, uint64_t n, const double* queries, uint64_t nq, uint64_t k, double max_dist,

@@ -136,6 +136,14 @@ def knn(pts, q, k, max_dist):
     return out[:m].copy()
 
 
+def grid_choose(pts, max_dist):
+    """(cell edge, (nx, ny, nz)) of the target grid the kernels build over `pts` (reg_math.h grid_choose)"""
+    pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+    out = np.empty(4)
+    lib().hostcheck_grid_choose(_dp(pts), C.c_uint64(len(pts)), C.c_double(max_dist), _dp(out))
+    return float(out[0]), (int(out[1]), int(out[2]), int(out[3]))
+
+
 def fit_plane(pts):
     pts = np.ascontiguousarray(pts, dtype=np.float64)
     out = np.empty(4)
