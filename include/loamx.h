@@ -141,7 +141,7 @@ int loamx_ctx_extract_counters(loamx_ctx* ctx, uint64_t* tie_replays, uint64_t* 
  *                  FUSED_ROWS, NO_SPLIT_CURV, STAGE_ALWAYS
  *   registration:  NO_MOMENTS, NO_REF_MOMENTS, NO_PACKED_GRID, NO_BIG_GRID, NO_GRID_SIDE, NO_EXTRACT_BOXES, NO_SMALL_SETS, DEBUG_POISON,
  *                  QUEUE_TWO_STAGE, QUEUE_ONE_STAGE, NO_COOP_LEFT, NO_MIXED_ASSOC, MAP_CELLS_LOG2 (a number: 0 = default)
- *   host streaming: STREAM_CHUNK_PAIRS (a number: pairs per uploaded chunk of loamx_register_scan_pairs; 0 = default, 128)
+ *   host streaming: STREAM_CHUNK_PAIRS (a number: pairs per uploaded chunk of loamx_register_scan_pairs / _scan_sequence; 0 = default, 128)
  *   multi-GPU:     FORCE_RCCL (a one-rank communicator really enqueues the RCCL collectives)
  *   input checks:  CHECK_FINITE (see "Non-finite input" below)
  * Unknown name: LOAMX_ERR_BAD_PARAM.
@@ -149,10 +149,10 @@ int loamx_ctx_extract_counters(loamx_ctx* ctx, uint64_t* tie_replays, uint64_t* 
  * Non-finite input. The reference is undefined on NaN / Inf coordinates (loam/include/loam/features-inl.h:38 sorts on
  * curvatures computed from them; a NaN range passes every comparison of loam/src/features.cpp:30-68; nanoflann and Ceres
  * receive them as they are). Here: every HOST entry point (loamx_compute_curvature / _valid_points, loamx_extract_features,
- * loamx_register_features / _indexed, loamx_register_scan_pairs, loamx_associate, loamx_fit_lines / _planes, loamx_knn_search, loamx_target_index_create /
+ * loamx_register_features / _indexed, loamx_register_scan_pairs, loamx_register_scan_sequence, loamx_associate, loamx_fit_lines / _planes, loamx_knn_search, loamx_target_index_create /
  * _insert, and their _f32 forms) refuses such input with LOAMX_ERR_BAD_PARAM: its uploaded copy is looked at by one small
  * kernel before anything else is launched (a 4-byte read-back, one extra stream synchronisation; an index is left as it was). The "_dev" entry points (loamx_extract_features_batch_dev, loamx_register_features_batch_dev,
- * loamx_register_scan_pairs_dev, and their _f32 forms) do not look unless the context option CHECK_FINITE is set: then one
+ * loamx_register_scan_pairs_dev, loamx_register_scan_sequence_dev, and their _f32 forms) do not look unless the context option CHECK_FINITE is set: then one
  * small kernel and a 4-byte read-back precede the call (it synchronises) and non-finite input is refused the same way.
  * Without it their result on such input is unspecified, as the reference's. */
 int loamx_ctx_set_option(loamx_ctx* ctx, const char* name, int value);
@@ -318,6 +318,56 @@ int loamx_register_scan_pairs_f32(loamx_ctx* ctx, const float* xyz, size_t n_pai
 int loamx_register_scan_pairs_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_pairs,
                                       const loamx_lidar_params* lidar, const loamx_fe_params* fe,
                                       const loamx_reg_params* reg, loamx_reg_result* d_results);
+
+/* ---- scan sequences ------------------------------------------------------------------------------------------
+ * The reference's own use (README.md, "Example Usage") is a loop over a sensor stream: scan i is the source of one
+ * registration and the target of the next. These entry points take n_scans consecutive scans stored back to back and
+ * register the n_scans - 1 consecutive pairs: pair p has scan p as target and scan p + 1 as source, results[p].pose is
+ * target_T_source exactly as in loamx_register_scan_pairs_dev, and every scan is extracted ONCE (the pair entry points,
+ * fed the duplicated layout [(scan p, scan p + 1)], upload and extract every interior scan twice). The records are bit-identical
+ * to the pair entry points' on that duplicated layout. d_init / init: (n_scans - 1) x 7 doubles, the initial
+ * target_T_source of every pair, or NULL (identity). n_scans < 2: LOAMX_OK, nothing is written. Parameter checks, the
+ * non-finite refusal and the error codes are those of the pair entry points (the initial poses are looked at with the scans).
+ *
+ * Host form: the pairs are cut into chunks of STREAM_CHUNK_PAIRS pairs (default 128) as in loamx_register_scan_pairs; chunk
+ * k of C pairs uploads the C + 1 scans it reads, so the scan two neighbouring chunks share travels and is extracted twice
+ * (1 / C extra): (C + 1) / C scans per pair cross PCIe instead of 2.
+ * Multi-GPU: shard the PAIRS with loamx_shard_range; rank r reads scans [first, first + count] (count + 1 of them) and the
+ * gather of the records is unchanged. */
+int loamx_register_scan_sequence_dev(loamx_ctx* ctx, const double* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                                     const loamx_fe_params* fe, const loamx_reg_params* reg, const double* d_init,
+                                     loamx_reg_result* d_results);
+int loamx_register_scan_sequence_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                                         const loamx_fe_params* fe, const loamx_reg_params* reg, const double* d_init,
+                                         loamx_reg_result* d_results);
+int loamx_register_scan_sequence(loamx_ctx* ctx, const double* xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                                 const loamx_fe_params* fe, const loamx_reg_params* reg, const double* init,
+                                 loamx_reg_result* results);
+int loamx_register_scan_sequence_f32(loamx_ctx* ctx, const float* xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                                     const loamx_fe_params* fe, const loamx_reg_params* reg, const double* init,
+                                     loamx_reg_result* results);
+/* The chained trajectory of n_pairs consecutive results (device records): d_world_T_scan holds (n_pairs + 1) x 7 doubles,
+ * world_T_scan[0] = origin (HOST pointer to a pose; NULL = identity), world_T_scan[i + 1] = world_T_scan[i] (+) results[i].pose
+ * with the arithmetic of Pose3d::compose (geometry.h:32), in the order of the loop a host would write — a pair that ended
+ * LOAMX_INSUFFICIENT_ASSOCIATIONS contributes the pose it returned, as in that loop. Deterministic: the same bytes on every
+ * run. Asynchronous on the context's stream. */
+int loamx_compose_trajectory_dev(loamx_ctx* ctx, const loamx_reg_result* d_results, size_t n_pairs, const double origin[7],
+                                 double* d_world_T_scan);
+/* Motion correction ("de-skew", the dewarping step the reference's README leaves to its users) of n_scans scans stored back
+ * to back. Scans are row-major [line][column]; column c was measured at sweep fraction tau = c / points_per_line.
+ * d_motion[s] = {qx, qy, qz, qw, tx, ty, tz} is start_T_end of sweep s: the sensor's pose at the end of the sweep in its
+ * frame at the start (for consecutive sweeps at constant velocity: the previous pair's target_T_source). q is normalised and
+ * taken along the short arc (negated if w < 0). With T(tau) = (slerp(identity, q, tau), tau t) a point becomes
+ *     p_out = R(rho)^T (R(tau) p + (tau - rho) t),   rho = ref_fraction in [0, 1] (otherwise LOAMX_ERR_BAD_PARAM):
+ * the point in the sensor frame at fraction rho. rho = 1 is the end of the sweep (LOAM's convention), rho = 0 its start.
+ * All arithmetic is FP64; the f32 form widens on load and rounds once on store. An identity motion returns the input bit for
+ * bit. A point whose three coordinates are all exactly zero (a beam without a return) stays zero and a point with a
+ * non-finite coordinate is copied unchanged, so the output is a scan like the input. d_xyz_out may equal d_xyz (in place);
+ * any other overlap is undefined. Asynchronous on the context's stream; lidar->min_range / max_range are not used. */
+int loamx_deskew_scans_dev(loamx_ctx* ctx, const double* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                           const double* d_motion, double ref_fraction, double* d_xyz_out);
+int loamx_deskew_scans_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                               const double* d_motion, double ref_fraction, float* d_xyz_out);
 
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are

@@ -95,6 +95,8 @@ EXPORTS = [
     "loamx_comm_info", "loamx_gather_results_dev", "loamx_comm_barrier", "loamx_comm_stats", "loamx_ctx_extract_counters",
     "loamx_ctx_set_option", "loamx_ctx_get_option",
     "loamx_fit_lines", "loamx_fit_planes", "loamx_knn_search", "loamx_associate", "loamx_target_index_stats",
+    "loamx_register_scan_sequence_dev", "loamx_register_scan_sequence_dev_f32", "loamx_register_scan_sequence",
+    "loamx_register_scan_sequence_f32", "loamx_compose_trajectory_dev", "loamx_deskew_scans_dev", "loamx_deskew_scans_dev_f32",
 ]
 
 _lib = None
@@ -162,6 +164,15 @@ def load(build_if_missing=True):
     lib.loamx_register_scan_pairs_dev_f32.argtypes = lib.loamx_register_scan_pairs_dev.argtypes
     lib.loamx_register_scan_pairs.argtypes = lib.loamx_register_scan_pairs_dev.argtypes  # (host pointers)
     lib.loamx_register_scan_pairs_f32.argtypes = lib.loamx_register_scan_pairs_dev.argtypes
+    lib.loamx_register_scan_sequence_dev.argtypes = [vp, vp, C.c_size_t, C.POINTER(LidarParams),
+                                                     C.POINTER(FeatureExtractionParams), C.POINTER(RegistrationParams),
+                                                     vp, vp]
+    lib.loamx_register_scan_sequence_dev_f32.argtypes = lib.loamx_register_scan_sequence_dev.argtypes
+    lib.loamx_register_scan_sequence.argtypes = lib.loamx_register_scan_sequence_dev.argtypes  # (host pointers)
+    lib.loamx_register_scan_sequence_f32.argtypes = lib.loamx_register_scan_sequence_dev.argtypes
+    lib.loamx_compose_trajectory_dev.argtypes = [vp, vp, C.c_size_t, dp, vp]
+    lib.loamx_deskew_scans_dev.argtypes = [vp, vp, C.c_size_t, C.POINTER(LidarParams), vp, C.c_double, vp]
+    lib.loamx_deskew_scans_dev_f32.argtypes = lib.loamx_deskew_scans_dev.argtypes
     lib.loamx_ctx_enable_kernel_timing.argtypes = [vp, C.c_int]
     lib.loamx_ctx_reset_kernel_stats.argtypes = [vp]
     lib.loamx_ctx_get_kernel_stats.argtypes = [vp, C.POINTER(KernelStat)]
@@ -572,6 +583,89 @@ class Context:
         fn = self.lib.loamx_register_scan_pairs_f32 if f32 else self.lib.loamx_register_scan_pairs
         self._check(fn(self.h, ptr, n_pairs, C.byref(lidar), C.byref(fe), C.byref(reg), res.ctypes.data))
         return res
+
+    # ---- scan sequences: scan i is the source of pair i - 1 and the target of pair i ------------------------
+    def register_scan_sequence_dev(self, d_xyz, n_scans, lidar, fe, reg, d_results, d_init=0, f32=False):
+        """n_scans device-resident scans back to back -> n_scans - 1 device records (pair p: scan p target, scan p + 1
+        source); d_init: (n_scans - 1) x 7 device doubles or 0 (identity). Asynchronous on the context's stream."""
+        fn = self.lib.loamx_register_scan_sequence_dev_f32 if f32 else self.lib.loamx_register_scan_sequence_dev
+        self._check(fn(self.h, d_xyz, n_scans, C.byref(lidar), C.byref(fe), C.byref(reg), d_init or None, d_results))
+
+    def register_scan_sequence(self, xyz, n_scans, lidar, fe=None, reg=None, init=None, out=None):
+        """Host memory in, host memory out (loamx_register_scan_sequence): xyz = a C-contiguous float64 / float32 array
+        (or `xyz=(ptr, dtype, element count)`) of n_scans consecutive scans; returns the n_scans - 1 result records
+        (RESULT_DTYPE). init: None or a C-contiguous float64 array of (n_scans - 1) x 7 initial poses. Arguments that do
+        not hold n_scans x H x W points, or an `out` / `init` of the wrong type or size, raise ValueError before anything
+        is copied."""
+        fe, reg = fe or FeatureExtractionParams(), reg or RegistrationParams()
+        n_scans = int(n_scans)
+        if n_scans < 0:
+            raise ValueError("register_scan_sequence: n_scans must not be negative")
+        n_pairs = max(n_scans - 1, 0)
+        if isinstance(xyz, tuple):
+            if len(xyz) != 3:
+                raise ValueError("register_scan_sequence: the address form is xyz=(ptr, dtype, element count)")
+            ptr, dt, size = xyz
+            dt = np.dtype(dt)
+        else:
+            if not isinstance(xyz, np.ndarray) or not xyz.flags["C_CONTIGUOUS"]:
+                raise ValueError("register_scan_sequence: xyz must be a C-contiguous numpy array")
+            ptr, dt, size = xyz.ctypes.data, xyz.dtype, xyz.size
+        if dt not in (np.float64, np.float32):
+            raise ValueError(f"register_scan_sequence: xyz must be float64 or float32, not {dt}")
+        f32 = dt == np.float32
+        need = n_scans * int(lidar.scan_lines) * int(lidar.points_per_line) * 3
+        if int(size) < need:
+            raise ValueError(f"register_scan_sequence: xyz holds {int(size)} values, {n_scans} scans need {need}")
+        if out is not None and (not isinstance(out, np.ndarray) or out.dtype != RESULT_DTYPE or not out.flags["C_CONTIGUOUS"]
+                                or out.size < n_pairs):
+            raise ValueError(f"register_scan_sequence: out must be a C-contiguous array of at least {n_pairs} RESULT_DTYPE records")
+        if init is not None and (not isinstance(init, np.ndarray) or init.dtype != np.float64 or not init.flags["C_CONTIGUOUS"]
+                                 or init.size < n_pairs * 7):
+            raise ValueError(f"register_scan_sequence: init must be a C-contiguous float64 array of at least {n_pairs} x 7 values")
+        res = out if out is not None else np.zeros(n_pairs, dtype=RESULT_DTYPE)
+        fn = self.lib.loamx_register_scan_sequence_f32 if f32 else self.lib.loamx_register_scan_sequence
+        self._check(fn(self.h, ptr, n_scans, C.byref(lidar), C.byref(fe), C.byref(reg),
+                       init.ctypes.data if init is not None and n_pairs else None, res.ctypes.data))
+        return res
+
+    def compose_trajectory_dev(self, d_results, n_pairs, d_world_T_scan, origin=None):
+        """d_world_T_scan[(n_pairs + 1) x 7] <- origin, origin (+) pose 0, ... (loamx_compose_trajectory_dev); origin: a
+        host pose7 or None (identity). Asynchronous on the context's stream."""
+        o = None if origin is None else np.ascontiguousarray(origin, dtype=np.float64)
+        if o is not None and o.size != 7:
+            raise ValueError("compose_trajectory_dev: origin must be a pose of 7 values")
+        self._check(self.lib.loamx_compose_trajectory_dev(self.h, d_results, n_pairs, _dp(o) if o is not None else None, d_world_T_scan))
+
+    def deskew_scans_dev(self, d_xyz, n_scans, lidar, d_motion, d_xyz_out, ref_fraction=1.0, f32=False):
+        """motion correction of n_scans device-resident scans (loamx_deskew_scans_dev); d_xyz_out may equal d_xyz"""
+        fn = self.lib.loamx_deskew_scans_dev_f32 if f32 else self.lib.loamx_deskew_scans_dev
+        self._check(fn(self.h, d_xyz, n_scans, C.byref(lidar), d_motion, float(ref_fraction), d_xyz_out))
+
+    def deskew_scans(self, xyz, lidar, motions, ref_fraction=1.0):
+        """Uploads the scans (float64 or float32, any shape that holds whole scans) and one motion (pose7) per scan,
+        runs loamx_deskew_scans_dev and returns the corrected scans in the shape and dtype of `xyz`."""
+        a = np.asarray(xyz)
+        if a.dtype != np.float32:
+            a = np.asarray(a, dtype=np.float64)
+        a = np.ascontiguousarray(a)
+        per_scan = int(lidar.scan_lines) * int(lidar.points_per_line) * 3
+        if per_scan == 0 or a.size % per_scan:
+            raise ValueError("deskew_scans: xyz does not hold whole scans")
+        n_scans = a.size // per_scan
+        m = np.ascontiguousarray(motions, dtype=np.float64)
+        if m.size != n_scans * 7:
+            raise ValueError(f"deskew_scans: {n_scans} scans need {n_scans} motions of 7 values")
+        if n_scans == 0:
+            return a.copy()
+        d_xyz, d_m = self.alloc(a.nbytes), self.alloc(m.nbytes)
+        try:
+            d_xyz.upload(a), d_m.upload(m)
+            self.deskew_scans_dev(d_xyz.ptr, n_scans, lidar, d_m.ptr, d_xyz.ptr, ref_fraction, f32=a.dtype == np.float32)
+            self.synchronize()
+            return d_xyz.download(a.dtype, a.size).reshape(a.shape)
+        finally:
+            d_xyz.free(), d_m.free()
 
     def synth_scan_pairs_dev(self, seed, first_pair, n_pairs, scan_lines, points_per_line, sigma, d_xyz):
         self._check(self.lib.loamx_synth_scan_pairs_dev(self.h, seed, first_pair, n_pairs, scan_lines,

@@ -26,7 +26,7 @@ enum WsId {
   WS_EDGE_IDX, WS_PLANAR_IDX, WS_N_EDGE, WS_N_PLANAR, WS_EDGE_XYZ, WS_PLANAR_XYZ,
   WS_GRID_DESC_E, WS_GRID_DESC_P, WS_CELLS_E, WS_CELLS_P, WS_SORTED_E, WS_SORTED_P, WS_REL_E, WS_REL_P,
   WS_SGRID_DESC_E, WS_SGRID_DESC_P, WS_SCELLS_E, WS_SCELLS_P, WS_SSORTED_E, WS_SSORTED_P, WS_SORT_SCRATCH, WS_SORT_SCRATCH_SRC, WS_ASSOC_E, WS_ASSOC_P, WS_NN_E, WS_NN_P, WS_RNN_E, WS_RNN_P, WS_NEAREST_E, WS_NEAREST_P, WS_REST_E, WS_REST_P, WS_EXACT_E, WS_EXACT_P, WS_NASSOC, WS_STATE, WS_PARTIALS, WS_MOM_PARTIALS, WS_MOMENTS, WS_FLAGGED_LIST, WS_FLAGGED_COUNT, WS_LINE_TOT, WS_EXTRACT_EVENTS, WS_BOX, WS_FINITE_FLAG,
-  WS_COUNTERS, WS_ITERINFO, WS_STREAM_IN0, WS_STREAM_IN1, WS_STREAM_RES, WS_DUMP_E, WS_DUMP_P, WS_FIT_IN, WS_FIT_OUT, WS_SRC_E, WS_SRC_P, WS_TGT_E, WS_TGT_P, WS_FCOUNTS, WS_RESULTS, WS_INIT,
+  WS_COUNTERS, WS_ITERINFO, WS_STREAM_IN0, WS_STREAM_IN1, WS_STREAM_RES, WS_DUMP_E, WS_DUMP_P, WS_FIT_IN, WS_FIT_OUT, WS_SRC_E, WS_SRC_P, WS_TGT_E, WS_TGT_P, WS_FCOUNTS, WS_RESULTS, WS_INIT, WS_STREAM_INIT,
   WS_COUNT
 };
 
@@ -469,6 +469,7 @@ struct RegInputs {
   const uint32_t *n_src_edge, *n_src_planar, *n_tgt_edge, *n_tgt_planar;
   const double* init;
   ExtractBoxes boxes;  // (optional) bounding boxes of the sets, left by the extraction that produced them
+  uint32_t src_box_offset;  // RegBatch::src_box_offset: scans from a pair's target box to its source box; 0: target boxes only
 };
 
 // host-side hook called after the association kernels of iteration `it` (detail capture)
@@ -583,7 +584,7 @@ int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loa
   B.src_edge = in.src_edge, B.n_src_edge = in.n_src_edge, B.src_planar = in.src_planar, B.n_src_planar = in.n_src_planar;
   B.tgt_edge = in.tgt_edge, B.n_tgt_edge = in.n_tgt_edge, B.tgt_planar = in.tgt_planar, B.n_tgt_planar = in.n_tgt_planar;
   B.init = in.init;
-  if (!(C.flags & kRegFlagNoExtractBoxes)) B.box_min = in.boxes.min, B.box_max = in.boxes.max, B.box_bad = in.boxes.bad;
+  if (!(C.flags & kRegFlagNoExtractBoxes)) B.box_min = in.boxes.min, B.box_max = in.boxes.max, B.box_bad = in.boxes.bad, B.src_box_offset = in.src_box_offset;
   ENSURE(ctx, WS_GRID_DESC_E, np * sizeof(GridDesc));
   ENSURE(ctx, WS_GRID_DESC_P, np * sizeof(GridDesc));
   ENSURE(ctx, WS_CELLS_E, (np * (size_t)(kGridCellsCap + 1) + 4) * sizeof(uint32_t));  // (+4: the search reads four entries at a time)
@@ -1644,9 +1645,14 @@ int loamx_register_features_batch_dev(loamx_ctx* ctx, size_t n_pairs, const doub
   return register_dev(ctx, in, C, d_results, false, nullptr, nullptr);
 }
 
-// (the caller holds ctx->mu and has selected the device; `look` = refuse non-finite input whatever CHECK_FINITE says)
+// How the scans of a call lie in memory. Interleaved pairs: n_pairs x 2 scans, pair p = (scan 2p target, scan 2p + 1 source).
+// Sequence: n_pairs + 1 scans, pair p = (scan p target, scan p + 1 source) — every scan is extracted ONCE and read in both roles.
+enum class ScanLayout { kPairs, kSequence };
+// (the caller holds ctx->mu and has selected the device; `look` = refuse non-finite input whatever CHECK_FINITE says;
+// d_init: n_pairs x 7 doubles or nullptr = identity)
 static int register_scan_pairs_locked(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_pairs, const loamx_lidar_params* lidar,
-                                      const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results, bool look = false) {
+                                      const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results, bool look = false,
+                                      ScanLayout layout = ScanLayout::kPairs, const double* d_init = nullptr) {
   ExtractParams P;
   int rc = make_extract_params(ctx, lidar, fe, P);
   if (rc != LOAMX_OK) return rc;
@@ -1654,9 +1660,17 @@ static int register_scan_pairs_locked(loamx_ctx* ctx, const void* d_xyz, bool f3
   rc = make_reg_config(ctx, reg, C);
   if (rc != LOAMX_OK) return rc;
   if (n_pairs == 0) return LOAMX_OK;
-  const size_t n_scans = 2 * n_pairs, ecap = edge_capacity(P), pcap = planar_capacity(P);
+  const bool seq = layout == ScanLayout::kSequence;
+  const size_t n_scans = seq ? n_pairs + 1 : 2 * n_pairs, ecap = edge_capacity(P), pcap = planar_capacity(P);
   rc = dev_check_finite(ctx, d_xyz, f32, nullptr, n_scans, (size_t)P.H * P.W, 1, look);
   if (rc != LOAMX_OK) return rc;
+  if (d_init && (look || (ctx->reg_flags & kRegFlagCheckFinite))) {
+    rc = finite_begin(ctx);
+    if (rc != LOAMX_OK) return rc;
+    launch_check_finite_scalars(d_init, n_pairs * 7, static_cast<uint32_t*>(ctx->ws[WS_FINITE_FLAG].p), ctx->stream);
+    rc = finite_end(ctx);
+    if (rc != LOAMX_OK) return rc;
+  }
   ENSURE(ctx, WS_N_EDGE, n_scans * sizeof(uint32_t));
   ENSURE(ctx, WS_N_PLANAR, n_scans * sizeof(uint32_t));
   ENSURE(ctx, WS_EDGE_XYZ, n_scans * ecap * 3 * sizeof(double));
@@ -1666,31 +1680,37 @@ static int register_scan_pairs_locked(loamx_ctx* ctx, const void* d_xyz, bool f3
   rc = extract_dev(ctx, d_xyz, f32, n_scans, P, nullptr, wsp<uint32_t>(ctx, WS_N_EDGE), wsp<double>(ctx, WS_EDGE_XYZ), nullptr,
                    wsp<uint32_t>(ctx, WS_N_PLANAR), wsp<double>(ctx, WS_PLANAR_XYZ), false, &boxes);
   if (rc != LOAMX_OK) return rc;
-  // scan 2p = target, scan 2p+1 = source (interleaved => in_pitch 2)
+  // interleaved: scan 2p = target, scan 2p + 1 = source (in_pitch 2); sequence: scan p = target, scan p + 1 = source (in_pitch 1).
+  // Either way a pair's source lies ONE scan behind its target: features, counts and boxes alike.
   RegInputs in{};
-  in.boxes = boxes;
-  in.n_pairs = n_pairs, in.edge_stride = ecap, in.planar_stride = pcap, in.in_pitch = 2;
+  in.boxes = boxes, in.src_box_offset = 1;
+  in.n_pairs = n_pairs, in.edge_stride = ecap, in.planar_stride = pcap, in.in_pitch = seq ? 1 : 2;
   in.tgt_edge = wsp<double>(ctx, WS_EDGE_XYZ), in.src_edge = in.tgt_edge + ecap * 3;
   in.tgt_planar = wsp<double>(ctx, WS_PLANAR_XYZ), in.src_planar = in.tgt_planar + pcap * 3;
   in.n_tgt_edge = wsp<uint32_t>(ctx, WS_N_EDGE), in.n_src_edge = in.n_tgt_edge + 1;
   in.n_tgt_planar = wsp<uint32_t>(ctx, WS_N_PLANAR), in.n_src_planar = in.n_tgt_planar + 1;
-  in.init = nullptr;
+  in.init = d_init;
   return register_dev(ctx, in, C, d_results, false, nullptr, nullptr);
 }
 static int register_scan_pairs(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_pairs, const loamx_lidar_params* lidar,
-                               const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results) {
+                               const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results,
+                               ScanLayout layout = ScanLayout::kPairs, const double* d_init = nullptr) {
   if (!ctx) return LOAMX_ERR_BAD_PARAM;
   std::lock_guard<std::mutex> lock(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  return register_scan_pairs_locked(ctx, d_xyz, f32, n_pairs, lidar, fe, reg, d_results);
+  return register_scan_pairs_locked(ctx, d_xyz, f32, n_pairs, lidar, fe, reg, d_results, false, layout, d_init);
 }
 
 // Host memory in, host memory out (loamx.h: loamx_register_scan_pairs): chunk k + 1 is uploaded on the copy stream into the
 // other staging buffer while chunk k goes through register_scan_pairs_locked — the host blocks inside that call (its two
 // read-backs), so the next upload is enqueued BEFORE it; a buffer is refilled once the chunk that read it has finished.
+// Sequence layout (loamx_register_scan_sequence): chunk k of C pairs uploads the C + 1 scans k C .. k C + C it reads; the scan two
+// neighbouring chunks share travels and is extracted twice (1 / C extra), so the chunks stay independent of each other.
+// init: n_pairs x 7 host doubles or nullptr; uploaded once, in front of the first chunk.
 constexpr size_t kStreamChunkPairs = 128;
 static int register_scan_pairs_host(loamx_ctx* ctx, const void* xyz, bool f32, size_t n_pairs, const loamx_lidar_params* lidar,
-                                    const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* results) {
+                                    const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* results,
+                                    ScanLayout layout = ScanLayout::kPairs, const double* init = nullptr) {
   if (!ctx) return LOAMX_ERR_BAD_PARAM;
   std::lock_guard<std::mutex> lock(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1704,20 +1724,23 @@ static int register_scan_pairs_host(loamx_ctx* ctx, const void* xyz, bool f32, s
   }
   if (n_pairs == 0) return LOAMX_OK;
   if (!xyz || !results) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
-  const size_t pair_bytes = 2 * (size_t)lidar->scan_lines * lidar->points_per_line * 3 * (f32 ? sizeof(float) : sizeof(double));
+  const bool seq = layout == ScanLayout::kSequence;
+  const size_t scan_bytes = (size_t)lidar->scan_lines * lidar->points_per_line * 3 * (f32 ? sizeof(float) : sizeof(double));
+  const size_t pair_bytes = (seq ? 1 : 2) * scan_bytes;  // from one pair's target scan to the next pair's
+  const size_t tail_bytes = seq ? scan_bytes : 0;        // the source scan of a chunk's last pair (sequence)
   size_t chunk = ctx->stream_chunk_pairs > 0 ? (size_t)ctx->stream_chunk_pairs : kStreamChunkPairs;
   chunk = chunk < n_pairs ? chunk : n_pairs;
   const size_t n_chunks = (n_pairs + chunk - 1) / chunk;
   untimed(ctx);
-  ENSURE(ctx, WS_STREAM_IN0, chunk * pair_bytes);
-  if (n_chunks > 1) ENSURE(ctx, WS_STREAM_IN1, chunk * pair_bytes);
+  ENSURE(ctx, WS_STREAM_IN0, chunk * pair_bytes + tail_bytes);
+  if (n_chunks > 1) ENSURE(ctx, WS_STREAM_IN1, chunk * pair_bytes + tail_bytes);
   ENSURE(ctx, WS_STREAM_RES, n_pairs * sizeof(loamx_reg_result));
-  if (!ctx->copy_stream) {
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    for (int b = 0; b < 2; b++) {
-      HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_up[b], hipEventDisableTiming));
-      HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_free[b], hipEventDisableTiming));
-    }
+  if (init) ENSURE(ctx, WS_STREAM_INIT, n_pairs * 7 * sizeof(double));
+  // (each handle on its own: a creation that failed half-way in an earlier call must not leave the others null for good)
+  if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+  for (int b = 0; b < 2; b++) {
+    if (!ctx->ev_up[b]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_up[b], hipEventDisableTiming));
+    if (!ctx->ev_free[b]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_free[b], hipEventDisableTiming));
   }
   unsigned char* in[2] = {wsp<unsigned char>(ctx, WS_STREAM_IN0), n_chunks > 1 ? wsp<unsigned char>(ctx, WS_STREAM_IN1) : nullptr};
   loamx_reg_result* d_res = wsp<loamx_reg_result>(ctx, WS_STREAM_RES);
@@ -1727,7 +1750,7 @@ static int register_scan_pairs_host(loamx_ctx* ctx, const void* xyz, bool f32, s
     const int b = (int)(k & 1);
     hipError_t e = hipSuccess;
     if (k >= 2) e = hipStreamWaitEvent(ctx->copy_stream, ctx->ev_free[b], 0);  // (the chunk that read this buffer is done)
-    if (e == hipSuccess) e = hipMemcpyAsync(in[b], host + k * chunk * pair_bytes, pairs_of(k) * pair_bytes, hipMemcpyHostToDevice, ctx->copy_stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(in[b], host + k * chunk * pair_bytes, pairs_of(k) * pair_bytes + tail_bytes, hipMemcpyHostToDevice, ctx->copy_stream);
     if (e == hipSuccess) e = hipEventRecord(ctx->ev_up[b], ctx->copy_stream);
     return e;
   };
@@ -1745,12 +1768,14 @@ static int register_scan_pairs_host(loamx_ctx* ctx, const void* xyz, bool f32, s
     if (e_ != hipSuccess) return drain(fail(ctx, LOAMX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_))); \
   } while (0)
   STREAM_TRY(upload(0));
+  double* d_init = init ? wsp<double>(ctx, WS_STREAM_INIT) : nullptr;
+  if (init) STREAM_TRY(hipMemcpyAsync(d_init, init, n_pairs * 7 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   int rc = LOAMX_OK;
   for (size_t k = 0; k < n_chunks && rc == LOAMX_OK; k++) {
     const int b = (int)(k & 1);
     if (k + 1 < n_chunks) STREAM_TRY(upload(k + 1));
     STREAM_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_up[b], 0));
-    rc = register_scan_pairs_locked(ctx, in[b], f32, pairs_of(k), lidar, fe, reg, d_res + k * chunk, true);
+    rc = register_scan_pairs_locked(ctx, in[b], f32, pairs_of(k), lidar, fe, reg, d_res + k * chunk, true, layout, d_init ? d_init + k * chunk * 7 : nullptr);
     untimed(ctx);
     if (rc == LOAMX_OK) STREAM_TRY(hipEventRecord(ctx->ev_free[b], ctx->stream));
   }
@@ -1778,6 +1803,70 @@ int loamx_register_scan_pairs_dev(loamx_ctx* ctx, const double* d_xyz, size_t n_
 int loamx_register_scan_pairs_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_pairs, const loamx_lidar_params* lidar,
                                       const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results) {
   return register_scan_pairs(ctx, d_xyz, true, n_pairs, lidar, fe, reg, d_results);
+}
+
+/* ---- scan sequences: scan i is the source of pair i - 1 and the target of pair i ----------------------------- */
+int loamx_register_scan_sequence_dev(loamx_ctx* ctx, const double* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                                     const loamx_fe_params* fe, const loamx_reg_params* reg, const double* d_init, loamx_reg_result* d_results) {
+  return register_scan_pairs(ctx, d_xyz, false, n_scans < 2 ? 0 : n_scans - 1, lidar, fe, reg, d_results, ScanLayout::kSequence, d_init);
+}
+int loamx_register_scan_sequence_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                                         const loamx_fe_params* fe, const loamx_reg_params* reg, const double* d_init, loamx_reg_result* d_results) {
+  return register_scan_pairs(ctx, d_xyz, true, n_scans < 2 ? 0 : n_scans - 1, lidar, fe, reg, d_results, ScanLayout::kSequence, d_init);
+}
+int loamx_register_scan_sequence(loamx_ctx* ctx, const double* xyz, size_t n_scans, const loamx_lidar_params* lidar, const loamx_fe_params* fe,
+                                 const loamx_reg_params* reg, const double* init, loamx_reg_result* results) {
+  return register_scan_pairs_host(ctx, xyz, false, n_scans < 2 ? 0 : n_scans - 1, lidar, fe, reg, results, ScanLayout::kSequence, init);
+}
+int loamx_register_scan_sequence_f32(loamx_ctx* ctx, const float* xyz, size_t n_scans, const loamx_lidar_params* lidar, const loamx_fe_params* fe,
+                                     const loamx_reg_params* reg, const double* init, loamx_reg_result* results) {
+  return register_scan_pairs_host(ctx, xyz, true, n_scans < 2 ? 0 : n_scans - 1, lidar, fe, reg, results, ScanLayout::kSequence, init);
+}
+
+int loamx_compose_trajectory_dev(loamx_ctx* ctx, const loamx_reg_result* d_results, size_t n_pairs, const double origin[7], double* d_world_T_scan) {
+  if (!ctx) return LOAMX_ERR_BAD_PARAM;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!d_world_T_scan || (n_pairs && !d_results)) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  const double identity[7] = {0, 0, 0, 1, 0, 0, 0};
+  if (origin && !host_all_finite(origin, false, 7)) return fail(ctx, LOAMX_ERR_BAD_PARAM, kNonFiniteMsg);
+  untimed(ctx);
+  launch_trajectory(d_results, n_pairs, origin ? origin : identity, d_world_T_scan, ctx->stream);
+  CHECK_LAUNCH(ctx, "trajectory_kernel");
+  return LOAMX_OK;
+}
+
+static int deskew_scans_dev(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_scans, const loamx_lidar_params* lidar, const double* d_motion,
+                            double ref_fraction, void* d_xyz_out) {
+  if (!ctx) return LOAMX_ERR_BAD_PARAM;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!lidar) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null parameter struct");
+  if (!(ref_fraction >= 0.0 && ref_fraction <= 1.0)) return fail(ctx, LOAMX_ERR_BAD_PARAM, "ref_fraction must lie in [0, 1]");
+  if (lidar->scan_lines > 0xFFFFFFFFull || lidar->points_per_line > 0xFFFFFFFFull)
+    return fail(ctx, LOAMX_ERR_UNSUPPORTED, "scan too large for 32-bit line and column numbers");
+  if (n_scans == 0 || lidar->scan_lines == 0 || lidar->points_per_line == 0) return LOAMX_OK;
+  if (!d_xyz || !d_motion || !d_xyz_out) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  if (n_scans * ((lidar->points_per_line + 255) / 256) > 0x7FFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "too many scans in one call");
+  if (ctx->reg_flags & kRegFlagCheckFinite) {  // (the motions; non-finite POINTS are defined here: copied unchanged)
+    int rc = finite_begin(ctx);
+    if (rc != LOAMX_OK) return rc;
+    launch_check_finite_scalars(d_motion, n_scans * 7, static_cast<uint32_t*>(ctx->ws[WS_FINITE_FLAG].p), ctx->stream);
+    rc = finite_end(ctx);
+    if (rc != LOAMX_OK) return rc;
+  }
+  untimed(ctx);
+  launch_deskew(d_xyz, d_xyz_out, f32, n_scans, (uint32_t)lidar->scan_lines, (uint32_t)lidar->points_per_line, d_motion, ref_fraction, ctx->stream);
+  CHECK_LAUNCH(ctx, "deskew_kernel");
+  return LOAMX_OK;
+}
+int loamx_deskew_scans_dev(loamx_ctx* ctx, const double* d_xyz, size_t n_scans, const loamx_lidar_params* lidar, const double* d_motion,
+                           double ref_fraction, double* d_xyz_out) {
+  return deskew_scans_dev(ctx, d_xyz, false, n_scans, lidar, d_motion, ref_fraction, d_xyz_out);
+}
+int loamx_deskew_scans_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_scans, const loamx_lidar_params* lidar, const double* d_motion,
+                               double ref_fraction, float* d_xyz_out) {
+  return deskew_scans_dev(ctx, d_xyz, true, n_scans, lidar, d_motion, ref_fraction, d_xyz_out);
 }
 
 /* ---- kernel timing ------------------------------------------------------------------------------------ */

@@ -246,11 +246,13 @@ struct RegBatch {
   uint32_t want_nearest;  // 1: a detail hook will read nearest_* (RegistrationDetail pairs); 0: the fit kernels skip that write
   uint32_t ref_moments;   // 1: the first ICF iteration takes its moments at its first candidate after ONE sweep (enqueue_icf_iteration)
   // optional: bounding boxes of the input feature sets, computed by the extraction that produced them (ExtractFused::box_*):
-  // [scan][kind][axis] keys, scan = pair * in_pitch (+ 1 for the source scan of interleaved pairs). Used by the index builds
+  // [scan][kind][axis] keys, scan = pair * in_pitch (+ src_box_offset for the pair's source scan). Used by the index builds
   // in place of their own read pass while *box_bad == 0; nullptr: the builds compute the boxes.
   const unsigned long long* box_min;
   const unsigned long long* box_max;
   const uint32_t* box_bad;
+  uint32_t src_box_offset;  // scans from a pair's target box to its source box (1: the source scan lies one scan behind the target
+                            // scan, in interleaved pairs and in a sequence alike); 0: the source sets have no boxes
   uint32_t small_edge_sets;  // 1: pairs whose TARGET edge set holds at most kBruteMax points get both edge sets from small_sets_build_kernel;
                              // 2: the target is a persistent index whose edge set is that small: every source edge set in its given order
 };
@@ -314,6 +316,11 @@ void launch_assoc_dump(const RegBatch& B, const RegConfig& C, const AssocDumpSet
 void launch_check_finite(const void* d_pts, bool f32, const uint32_t* d_n, size_t n_sets, size_t stride, uint32_t pitch, uint32_t* d_flag,
                          hipStream_t s);
 void launch_check_finite_scalars(const double* d_v, size_t n_scalars, uint32_t* d_flag, hipStream_t s);
+
+/* ---- scan sequences (sequence_kernels.hip): trajectory of the per-pair results, motion correction of scans ------ */
+void launch_deskew(const void* d_xyz, void* d_out, bool f32, size_t n_scans, uint32_t H, uint32_t W, const double* d_motion, double rho,
+                   hipStream_t s);
+void launch_trajectory(const loamx_reg_result* d_results, size_t n_pairs, const double origin[7], double* d_world_T_scan, hipStream_t s);
 
 /* ---- synthetic generator (synth_kernels.hip) --------------------------------------------------- */
 void launch_synth_pairs(uint64_t seed, uint64_t first_pair, size_t n_pairs, uint32_t H, uint32_t W, double sigma,

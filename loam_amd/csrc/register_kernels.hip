@@ -2465,15 +2465,15 @@ void launch_grid_build_source(const RegBatch& B, const RegConfig& C, bool plane,
   const size_t stride = plane ? B.planar_stride : B.edge_stride;
   const uint32_t* n_src = plane ? B.n_src_planar : B.n_src_edge;
   const GridSet& gs = plane ? B.src_grid_plane : B.src_grid_edge;
-  // (boxes: the source scan of an interleaved pair is the scan behind its target scan)
+  // (boxes: a pair's source scan lies src_box_offset scans behind its target scan; 0: the caller has no boxes for the sources)
   if (!plane && B.small_edge_sets == 2u) {  // (persistent index with a brute-force sized edge set: the sources in their given order, as in a plain call)
     launch_kernel(small_sets_build_kernel, dim3((unsigned)B.n_pairs), dim3(kSmallThreads), 0, s, static_cast<const double*>(nullptr), static_cast<const uint32_t*>(nullptr),
                   B.src_edge, B.n_src_edge, B.edge_stride, B.in_pitch, C.r_edge, B.grid_edge, B.src_grid_edge, B.grid_bytes, static_cast<const unsigned long long*>(nullptr),
                   static_cast<const unsigned long long*>(nullptr), static_cast<const uint32_t*>(nullptr));
     return;
   }
-  const unsigned long long* bmin = (B.box_min && B.in_pitch == 2) ? B.box_min + 6 + (plane ? 3 : 0) : nullptr;
-  const unsigned long long* bmax = (B.box_max && B.in_pitch == 2) ? B.box_max + 6 + (plane ? 3 : 0) : nullptr;
+  const unsigned long long* bmin = (B.box_min && B.src_box_offset) ? B.box_min + 6 * B.src_box_offset + (plane ? 3 : 0) : nullptr;
+  const unsigned long long* bmax = (B.box_max && B.src_box_offset) ? B.box_max + 6 * B.src_box_offset + (plane ? 3 : 0) : nullptr;
   launch_grid_build<true>(B.n_pairs, plane ? B.src_planar : B.src_edge, n_src, stride, B.in_pitch, plane ? C.r_plane : C.r_edge, gs,
                           B.sort_scratch_src, C.flags, s, B.grid_bytes, bmin, bmax, B.box_bad, (!plane && B.small_edge_sets == 1u) ? B.n_tgt_edge : nullptr);
   if (stride && !grid_small(stride, C.flags))

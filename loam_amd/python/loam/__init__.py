@@ -4,3 +4,4 @@ from .loam_python import (FeatureExtractionParams, LidarParams, LoamFeatures, Po
                           RegistrationDetail, RegistrationIterationInfo, RegistrationParams,
                           RegistrationTerminationType, computeCurvature, computeValidPoints, extractFeatures,
                           registerFeatures)
+from .loam_python import deskewScan, registerScanSequence  # noqa: F401  (extensions: scan sequences)

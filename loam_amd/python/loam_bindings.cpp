@@ -2,13 +2,15 @@
 // reference's python/loam_bindings.cpp:24-144: LidarParams, Pose3d, Quaterniond,
 // FeatureExtractionParams, LoamFeatures, extractFeatures, computeCurvature, computeValidPoints,
 // RegistrationParams, RegistrationIterationInfo, RegistrationTerminationType, RegistrationDetail,
-// registerFeatures — with the same keyword arguments. Point clouds are contiguous (N,3) float64
+// registerFeatures — with the same keyword arguments; plus two extensions the reference does not have, registerScanSequence
+// and deskewScan (include/loamx.h: "scan sequences"). Point clouds are contiguous (N,3) float64
 // arrays handed to the C ABI without per-point objects (a list of 3-vectors is converted once).
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
 #include <cstring>
+#include <optional>
 
 #include "loam/loam.h"
 
@@ -63,6 +65,21 @@ inline int c_valid(loamx_ctx* c, const double* x, size_t n, const loamx_lidar_pa
 }
 inline int c_valid(loamx_ctx* c, const float* x, size_t n, const loamx_lidar_params* l, const loamx_fe_params* f, uint8_t* o) {
   return loamx_compute_valid_points_f32(c, x, n, l, f, o);
+}
+
+inline int c_sequence(loamx_ctx* c, const double* x, size_t n, const loamx_lidar_params* l, const loamx_fe_params* f, const loamx_reg_params* r,
+                      const double* init, loamx_reg_result* out) {
+  return loamx_register_scan_sequence(c, x, n, l, f, r, init, out);
+}
+inline int c_sequence(loamx_ctx* c, const float* x, size_t n, const loamx_lidar_params* l, const loamx_fe_params* f, const loamx_reg_params* r,
+                      const double* init, loamx_reg_result* out) {
+  return loamx_register_scan_sequence_f32(c, x, n, l, f, r, init, out);
+}
+inline int c_deskew(loamx_ctx* c, const double* in, const loamx_lidar_params* l, const double* motion, double rho, double* out) {
+  return loamx_deskew_scans_dev(c, in, 1, l, motion, rho, out);
+}
+inline int c_deskew(loamx_ctx* c, const float* in, const loamx_lidar_params* l, const double* motion, double rho, float* out) {
+  return loamx_deskew_scans_dev_f32(c, in, 1, l, motion, rho, out);
 }
 
 loam::Vector3d vec_from(const Arr& a) {
@@ -128,6 +145,63 @@ py::array_t<bool> compute_valid_points(const A& scan, const loam::LidarParams& l
   const loamx_fe_params cfp = loam::gpu::toC(params);
   static_assert(sizeof(bool) == 1, "bool must be one byte");
   loam::gpu::check(ctx, c_valid(ctx, scan.data(), n, &clp, &cfp, reinterpret_cast<uint8_t*>(out.mutable_data())));
+  return out;
+}
+
+// Extension: n consecutive scans as one (n, N, 3) array (or anything numpy stacks into one) -> the n - 1 poses
+// target_T_source of the consecutive pairs, every scan extracted once (loamx_register_scan_sequence)
+template <typename A>
+std::vector<loam::Pose3d> register_scan_sequence(const A& scans, const loam::LidarParams& lp, const loam::FeatureExtractionParams& fe,
+                                                 const loam::RegistrationParams& rp, const std::optional<std::vector<loam::Pose3d>>& inits) {
+  if (scans.ndim() != 3 || scans.shape(2) != 3) throw std::runtime_error("scans: expected an (n_scans, N, 3) array");
+  const size_t n_scans = (size_t)scans.shape(0);
+  scan_size_check((size_t)scans.shape(1), lp);
+  const size_t n_pairs = n_scans < 2 ? 0 : n_scans - 1;
+  if (inits && inits->size() != n_pairs) throw std::runtime_error("inits: expected one pose per consecutive pair (n_scans - 1)");
+  std::vector<loam::Pose3d> out;
+  if (n_pairs == 0) return out;
+  std::vector<double> init;
+  if (inits) {
+    init.resize(7 * n_pairs);
+    for (size_t i = 0; i < n_pairs; i++) (*inits)[i].toArray(&init[7 * i]);
+  }
+  loamx_ctx* ctx = loam::gpu::defaultContext();
+  const loamx_lidar_params clp = loam::gpu::toC(lp);
+  const loamx_fe_params cfp = loam::gpu::toC(fe);
+  const loamx_reg_params crp = loam::gpu::toC(rp);
+  std::vector<loamx_reg_result> res(n_pairs);
+  {
+    py::gil_scoped_release release;
+    loam::gpu::check(ctx, c_sequence(ctx, scans.data(), n_scans, &clp, &cfp, &crp, inits ? init.data() : nullptr, res.data()));
+  }
+  for (const loamx_reg_result& r : res) out.push_back(loam::Pose3d::fromArray(r.pose));
+  return out;
+}
+
+// Extension: motion correction of one scan (loamx_deskew_scans_dev); motion = start_T_end of the sweep
+template <typename A>
+A deskew_scan(const A& scan, const loam::LidarParams& lp, const loam::Pose3d& motion, double ref_fraction) {
+  using T = typename A::value_type;
+  const size_t n = check_points(scan, "scan");
+  scan_size_check(n, lp);
+  A out(std::vector<py::ssize_t>{(py::ssize_t)n, 3});
+  if (n == 0) return out;
+  loamx_ctx* ctx = loam::gpu::defaultContext();
+  const loamx_lidar_params clp = loam::gpu::toC(lp);
+  double m[7];
+  motion.toArray(m);
+  void *d_xyz = nullptr, *d_m = nullptr;
+  const size_t bytes = n * 3 * sizeof(T);
+  loam::gpu::check(ctx, loamx_dev_alloc(ctx, bytes, &d_xyz));
+  int rc = loamx_dev_alloc(ctx, sizeof(m), &d_m);
+  if (rc == LOAMX_OK) rc = loamx_copy_to_device(ctx, d_xyz, scan.data(), bytes);
+  if (rc == LOAMX_OK) rc = loamx_copy_to_device(ctx, d_m, m, sizeof(m));
+  if (rc == LOAMX_OK) rc = c_deskew(ctx, static_cast<const T*>(d_xyz), &clp, static_cast<const double*>(d_m), ref_fraction, static_cast<T*>(d_xyz));
+  if (rc == LOAMX_OK) rc = loamx_copy_to_host(ctx, out.mutable_data(), d_xyz, bytes);  // (on the context's stream, behind the kernel; synchronous)
+  std::string err = rc == LOAMX_OK ? std::string() : std::string(loamx_last_error(ctx));
+  loamx_dev_free(ctx, d_xyz);
+  if (d_m) loamx_dev_free(ctx, d_m);
+  if (rc != LOAMX_OK) throw std::runtime_error(!err.empty() ? err : std::string(loamx_status_string(rc)));
   return out;
 }
 
@@ -261,4 +335,14 @@ PYBIND11_MODULE(loam_python, m) {
       },
       py::arg("source"), py::arg("target"), py::arg("target_T_source_init"),
       py::arg("params") = loam::RegistrationParams(), py::arg("detail") = std::shared_ptr<loam::RegistrationDetail>());
+
+  // ---- extensions (no counterpart in the reference's module) ----
+  m.def("registerScanSequence", &register_scan_sequence<ArrF>, py::arg("scans"), py::arg("lidar_params"),
+        py::arg("fe_params") = loam::FeatureExtractionParams(), py::arg("reg_params") = loam::RegistrationParams(),
+        py::arg("inits") = py::none());
+  m.def("registerScanSequence", &register_scan_sequence<Arr>, py::arg("scans"), py::arg("lidar_params"),
+        py::arg("fe_params") = loam::FeatureExtractionParams(), py::arg("reg_params") = loam::RegistrationParams(),
+        py::arg("inits") = py::none());
+  m.def("deskewScan", &deskew_scan<ArrF>, py::arg("scan"), py::arg("lidar_params"), py::arg("motion"), py::arg("ref_fraction") = 1.0);
+  m.def("deskewScan", &deskew_scan<Arr>, py::arg("scan"), py::arg("lidar_params"), py::arg("motion"), py::arg("ref_fraction") = 1.0);
 }
