@@ -129,6 +129,35 @@ int loamx_ctx_synchronize(loamx_ctx* ctx);
  *   scan_fallbacks calls in which a scan line gave up its (bounded) wait for the lines before it and the features were
  *                  gathered by the fallback kernel instead — the results are the same */
 int loamx_ctx_extract_counters(loamx_ctx* ctx, uint64_t* tie_replays, uint64_t* scan_fallbacks);
+/* Debug / measurement (no reference counterpart): which kernels the LAST extraction enqueued on this context took —
+ * loamx_extract_features*, loamx_compute_curvature / _valid_points, and the extraction inside loamx_register_scan_pairs* /
+ * _scan_sequence* (the last chunk's). The bits are set by the launchers at the place where they choose a kernel, not by a
+ * second copy of their predicates; a test of "kernel K at shape X" asserts from them that K is what ran. Host side only: no
+ * synchronisation, 0 before the first extraction. Never part of a result. */
+enum {
+  LOAMX_ROUTE_SPLIT_CURV = 1u << 0,     /* curvature handed to the selection as hi words | lo words, validity in the sign bit */
+  LOAMX_ROUTE_CURV2 = 1u << 1,          /* curvature_valid2_kernel<3> (two columns per lane) */
+  LOAMX_ROUTE_CURV_V1 = 1u << 2,        /* curvature_valid_kernel<3> (option CURV_V1) */
+  LOAMX_ROUTE_CURV_GENERIC = 1u << 3,   /* curvature_valid_kernel<0>: neighbor_points as a run-time value */
+  LOAMX_ROUTE_ROWS = 1u << 4,           /* select_rows_kernel: four scan lines per wavefront (geometry in the ROWS_R / ROWS_CH fields) */
+  LOAMX_ROUTE_ROWS_CH11 = 1u << 5,      /* ... in the instantiation specialised for 11 points per lane; clear: the generic one */
+  LOAMX_ROUTE_ROWS_PASS2 = 1u << 6,     /* ... followed by the conditional select_rows_stage_kernel launch (only_if) */
+  LOAMX_ROUTE_ROWS_LIST16 = 1u << 7,    /* ... with 16-bit pick lists; clear: bytes */
+  LOAMX_ROUTE_MIS = 1u << 8,            /* select_mis_kernel: one scan line per wavefront */
+  LOAMX_ROUTE_MIS_4LINES = 1u << 9,     /* ... four lines (wavefronts) per workgroup; clear: one */
+  LOAMX_ROUTE_MIS_TWO = 1u << 10,       /* ... two picks per lane (65..128 picks per sector) */
+  LOAMX_ROUTE_MIS_CONST_W = 1u << 11,   /* ... with the line length compiled in (1024 / 2048) */
+  LOAMX_ROUTE_ARGMAX4 = 1u << 12,       /* select_kernel<4> (arg-max, lines up to 1024 points) */
+  LOAMX_ROUTE_ARGMAX1 = 1u << 13,       /* select_kernel<1> (arg-max, longer lines) */
+  LOAMX_ROUTE_FUSED_COMPACT = 1u << 14, /* the selection wrote the final arrays itself (compact_kernel only as the conditional fallback) */
+  LOAMX_ROUTE_COMPACT = 1u << 15,       /* compact_kernel gathered every scan (unconditional launch) */
+  LOAMX_ROUTE_FUSED_EXTRACT = 1u << 16, /* extract_fused_kernel (option FUSED_EXTRACT) */
+  LOAMX_ROUTE_FUSED_ROWS = 1u << 17,    /* the fused form of select_rows_kernel (option FUSED_ROWS) */
+  LOAMX_ROUTE_BOXES = 1u << 18,         /* the selection's bounding boxes were handed on to the caller (the index builds) */
+  LOAMX_ROUTE_ROWS_R_SHIFT = 20,        /* 3 bits: R = neighbor_points - 1 of the row kernels (0 when they did not run) */
+  LOAMX_ROUTE_ROWS_CH_SHIFT = 24        /* 6 bits: points of a sector per lane of the row kernels (RowSelGeom::ch) */
+};
+int loamx_ctx_last_extract_route(loamx_ctx* ctx, uint32_t* bits);
 /* Debug / measurement switches of ONE context (no reference counterpart). loamx_ctx_create reads the environment
  * variables LOAMX_<NAME> once as the defaults (set = 1); no entry point looks at the environment afterwards, and a
  * switch only ever affects the context it was set on. None changes a result beyond the order in which a pair's residual

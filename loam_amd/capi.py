@@ -93,11 +93,36 @@ EXPORTS = [
     "loamx_target_index_insert", "loamx_target_index_size",
     "loamx_shard_range", "loamx_comm_get_unique_id", "loamx_comm_create", "loamx_comm_wrap", "loamx_comm_destroy",
     "loamx_comm_info", "loamx_gather_results_dev", "loamx_comm_barrier", "loamx_comm_stats", "loamx_ctx_extract_counters",
-    "loamx_ctx_set_option", "loamx_ctx_get_option",
+    "loamx_ctx_set_option", "loamx_ctx_get_option", "loamx_ctx_last_extract_route",
     "loamx_fit_lines", "loamx_fit_planes", "loamx_knn_search", "loamx_associate", "loamx_target_index_stats",
     "loamx_register_scan_sequence_dev", "loamx_register_scan_sequence_dev_f32", "loamx_register_scan_sequence",
     "loamx_register_scan_sequence_f32", "loamx_compose_trajectory_dev", "loamx_deskew_scans_dev", "loamx_deskew_scans_dev_f32",
 ]
+
+# bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
+ROUTE_BITS = ("SPLIT_CURV", "CURV2", "CURV_V1", "CURV_GENERIC", "ROWS", "ROWS_CH11", "ROWS_PASS2", "ROWS_LIST16", "MIS", "MIS_4LINES",
+              "MIS_TWO", "MIS_CONST_W", "ARGMAX4", "ARGMAX1", "FUSED_COMPACT", "COMPACT", "FUSED_EXTRACT", "FUSED_ROWS", "BOXES")
+
+
+class ExtractRoute:
+    """The route word of the last extraction: `"ROWS" in r`, r.names (the set bits), r.rows_R / r.rows_ch (geometry of the
+    row kernels: neighbor_points - 1 and points per lane; 0 when they did not run)."""
+
+    def __init__(self, bits):
+        self.bits = int(bits)
+        self.names = frozenset(n for i, n in enumerate(ROUTE_BITS) if self.bits >> i & 1)
+        self.rows_R = self.bits >> 20 & 7
+        self.rows_ch = self.bits >> 24 & 63
+
+    def __contains__(self, name):
+        if name not in ROUTE_BITS:
+            raise KeyError(name)
+        return name in self.names
+
+    def __repr__(self):
+        return "ExtractRoute(%s%s)" % ("|".join(n for n in ROUTE_BITS if n in self.names),
+                                       ", R=%d ch=%d" % (self.rows_R, self.rows_ch) if "ROWS" in self.names else "")
+
 
 _lib = None
 
@@ -206,6 +231,7 @@ def load(build_if_missing=True):
                                     C.POINTER(RegistrationParams), C.POINTER(AssocDump)]
     lib.loamx_ctx_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     lib.loamx_ctx_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int)]
+    lib.loamx_ctx_last_extract_route.argtypes = [vp, C.POINTER(C.c_uint32)]
     _lib = lib
     return lib
 
@@ -378,6 +404,12 @@ class Context:
         a, b = C.c_uint64(0), C.c_uint64(0)
         self._check(self.lib.loamx_ctx_extract_counters(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def last_extract_route(self):
+        """which kernels the last extraction on this context took (include/loamx.h: LOAMX_ROUTE_*), as an ExtractRoute"""
+        v = C.c_uint32(0)
+        self._check(self.lib.loamx_ctx_last_extract_route(self.h, C.byref(v)))
+        return ExtractRoute(v.value)
 
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)

@@ -1173,12 +1173,16 @@ static void launch_curvature_valid_t(const T* d_xyz, const dim3& grid, const Ext
     const dim3 grid2(grid.x, (P.W + kCurvTilesPerGroup * kTile - 1) / (kCurvTilesPerGroup * kTile));
     if (P.flags & kFlagSplitCurv) launch_kernel((curvature_valid2_kernel<3, T, true>), grid2, dim3(kCurvThreads), 0, s, d_xyz, P, d_curv, d_mask);
     else launch_kernel((curvature_valid2_kernel<3, T>), grid2, dim3(kCurvThreads), 0, s, d_xyz, P, d_curv, d_mask);
+    g_extract_route |= LOAMX_ROUTE_CURV2;
     return;
   }
-  if (P.np == 3)
+  if (P.np == 3) {
     launch_kernel((curvature_valid_kernel<3, T>), grid, dim3(kCurvThreads), 0, s, d_xyz, P, d_curv, d_mask);
-  else
+    g_extract_route |= LOAMX_ROUTE_CURV_V1;
+  } else {
     launch_kernel((curvature_valid_kernel<0, T>), grid, dim3(kCurvThreads), 0, s, d_xyz, P, d_curv, d_mask);
+    g_extract_route |= LOAMX_ROUTE_CURV_GENERIC;
+  }
 }
 
 void launch_curvature_valid(const void* d_xyz, bool f32, size_t n_scans, const ExtractParams& P, double* d_curv,
@@ -1194,17 +1198,21 @@ void launch_curvature_valid(const void* d_xyz, bool f32, size_t n_scans, const E
 template <int R, bool TWO>
 static void launch_select_mis2(const double* d_curv, const uint8_t* d_mask, size_t n_lines, const ExtractParams& P,
                                const ExtractStage& st, const ExtractFused& fz, hipStream_t s) {
+  g_extract_route |= LOAMX_ROUTE_MIS | (TWO ? LOAMX_ROUTE_MIS_TWO : 0u);
   const size_t per_wave = select_mis_lds_bytes((int)P.W, TWO ? 128 : 64);
 #if defined(LOAMX_SELECT_ONE_WAVE)
   if (false) {
 #else
   if (per_wave * 4 <= 48 * 1024) {
 #endif
+    g_extract_route |= LOAMX_ROUTE_MIS_4LINES;
     // (the reference's neighbor_points = 3 on the two usual line lengths: W compiled in)
     if (R == 2 && !TWO && P.W == 1024)
+      g_extract_route |= LOAMX_ROUTE_MIS_CONST_W,
       launch_kernel((select_mis_kernel<R, 4, TWO, (R == 2 && !TWO) ? 1024 : 0>), dim3((unsigned)((n_lines + 3) / 4)), dim3(256), per_wave * 4, s,
                          d_curv, d_mask, n_lines, P, st, fz);
     else if (R == 2 && TWO && P.W == 2048)
+      g_extract_route |= LOAMX_ROUTE_MIS_CONST_W,
       launch_kernel((select_mis_kernel<R, 4, TWO, (R == 2 && TWO) ? 2048 : 0>), dim3((unsigned)((n_lines + 3) / 4)), dim3(256), per_wave * 4, s,
                          d_curv, d_mask, n_lines, P, st, fz);
     else
@@ -1228,6 +1236,7 @@ static void launch_select_rows_r(const double* d_curv, const uint8_t* d_mask, si
                                  const ExtractFused& fz, const RowSelGeom& G, hipStream_t s) {
   const dim3 grid((unsigned)((n_lines + 15) / 16));
   if (fz.only_if) {  // the conditional second launch (launch_select_rows)
+    g_extract_route |= LOAMX_ROUTE_ROWS_PASS2;
     if (R == 2 && G.ch == 11 && (P.flags & kFlagSplitCurv))
       launch_kernel((select_rows_stage_kernel<R, R == 2 ? 11 : 0, R == 2>), grid, dim3(256), (size_t)G.bytes * 4, s, d_curv, d_mask, n_lines, P, st, fz, G);
     else if (R == 2 && G.ch == 11)
@@ -1236,9 +1245,12 @@ static void launch_select_rows_r(const double* d_curv, const uint8_t* d_mask, si
       launch_kernel((select_rows_stage_kernel<R, 0, false>), grid, dim3(256), (size_t)G.bytes * 4, s, d_curv, d_mask, n_lines, P, st, fz, G);
     return;
   }
+  g_extract_route |= LOAMX_ROUTE_ROWS | ((uint32_t)R << LOAMX_ROUTE_ROWS_R_SHIFT) | (G.ch << LOAMX_ROUTE_ROWS_CH_SHIFT) | (G.pk8 ? 0u : LOAMX_ROUTE_ROWS_LIST16);
   if (R == 2 && G.ch == 11 && (P.flags & kFlagSplitCurv))
+    g_extract_route |= LOAMX_ROUTE_ROWS_CH11,
     launch_kernel((select_rows_kernel<R, R == 2 ? 11 : 0, false, R == 2>), grid, dim3(256), (size_t)G.bytes * 4, s, d_curv, d_mask, n_lines, P, st, fz, G);
   else if (R == 2 && G.ch == 11)
+    g_extract_route |= LOAMX_ROUTE_ROWS_CH11,
     launch_kernel((select_rows_kernel<R, R == 2 ? 11 : 0>), grid, dim3(256), (size_t)G.bytes * 4, s, d_curv, d_mask, n_lines, P, st, fz, G);
   else
     launch_kernel((select_rows_kernel<R, 0>), grid, dim3(256), (size_t)G.bytes * 4, s, d_curv, d_mask, n_lines, P, st, fz, G);
@@ -1277,6 +1289,8 @@ bool launch_extract_rows_fused(const void* d_xyz, bool f32, size_t n_scans, cons
   ExtractFused fz = fz_in;
   fz.fuse = (P.S <= 64 && !(P.flags & kFlagNoFusedCompact)) ? 1u : 0u;
   fz.xyz = d_xyz, fz.f32 = f32 ? 1u : 0u;
+  g_extract_route |= LOAMX_ROUTE_FUSED_ROWS | LOAMX_ROUTE_ROWS | LOAMX_ROUTE_ROWS_CH11 | (2u << LOAMX_ROUTE_ROWS_R_SHIFT) | (G.ch << LOAMX_ROUTE_ROWS_CH_SHIFT) |
+                     (G.pk8 ? 0u : LOAMX_ROUTE_ROWS_LIST16);
   launch_kernel((select_rows_kernel<2, 11, true>), dim3((unsigned)((n_lines + 7) / 8)), dim3(128), (size_t)G.bytes * 2, s,
                 static_cast<const double*>(nullptr), static_cast<const uint8_t*>(nullptr), n_lines, P, st, fz, G);
   const unsigned grid = (unsigned)(n_lines < 4096 ? n_lines : 4096);
@@ -1337,9 +1351,11 @@ bool launch_select(const double* d_curv, const uint8_t* d_mask, size_t n_scans, 
   const size_t per_wave = (size_t)P.W * 8 + (((size_t)P.W + 7) & ~(size_t)7);
   if (P.W <= 1024) {
     constexpr int WAVES = 4;
+    g_extract_route |= LOAMX_ROUTE_ARGMAX4;
     launch_kernel(select_kernel<WAVES>, dim3((unsigned)((n_lines + WAVES - 1) / WAVES)), dim3(WAVES * 64),
                        per_wave * WAVES, s, d_curv, d_mask, n_lines, P, st, fz.line_tot, fz.error);
   } else {
+    g_extract_route |= LOAMX_ROUTE_ARGMAX1;
     launch_kernel(select_kernel<1>, dim3((unsigned)n_lines), dim3(64), per_wave, s, d_curv, d_mask, n_lines, P,
                        st, fz.line_tot, fz.error);
   }
@@ -1366,6 +1382,7 @@ bool launch_extract_fused(const void* d_xyz, bool f32, size_t n_scans, const Ext
   ExtractFused fz = fz_in;
   fz.fuse = 1u;
   const dim3 grid((unsigned)n_lines);
+  g_extract_route |= LOAMX_ROUTE_FUSED_EXTRACT;
   if (f32)
     launch_kernel((extract_fused_kernel<3, 2, float>), grid, dim3(64), lds, s, static_cast<const float*>(d_xyz), n_lines, P, st, fz, d_curv, d_mask);
   else

@@ -71,6 +71,8 @@ struct loamx_ctx {
   hipStream_t copy_stream = nullptr;  // uploads of loamx_register_scan_pairs (created on first use)
   hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
 
+  uint32_t last_extract_route = 0;  // LOAMX_ROUTE_* of the last extract_dev call (loamx_ctx_last_extract_route)
+
   unsigned long long sweep_slots_base[2] = {0, 0};
   unsigned long long features_base = 0;  // events[2] at the last loamx_ctx_reset_kernel_stats
   std::mutex mu;
@@ -101,6 +103,7 @@ struct loamx_target_index {
 namespace loamx {
 thread_local LaunchScope* g_launch_scope = nullptr;
 int g_debug_sync = getenv("LOAMX_DEBUG_SYNC") ? 1 : 0;
+thread_local uint32_t g_extract_route = 0;
 }
 
 namespace {
@@ -349,6 +352,12 @@ int extract_dev(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_scans, con
                 double* d_planar_xyz, bool only_curvature_mask, ExtractBoxes* boxes = nullptr) {
   const size_t N = (size_t)P.H * P.W;
   if (boxes) *boxes = ExtractBoxes{};
+  // the launchers note their choices in g_extract_route; whichever way this call returns, the context keeps them
+  struct RouteKeeper {
+    loamx_ctx* c;
+    explicit RouteKeeper(loamx_ctx* c_) : c(c_) { g_extract_route = 0; }
+    ~RouteKeeper() { c->last_extract_route = g_extract_route; }
+  } route_keeper(ctx);
   if (n_scans == 0) return LOAMX_OK;
   untimed(ctx);
   if (N == 0) {
@@ -408,6 +417,7 @@ int extract_dev(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_scans, con
       launch_replay(wsp<double>(ctx, WS_CURV), wsp<uint8_t>(ctx, WS_MASK), n_scans, P, st, fz, ctx->stream);
       launch_compact(d_xyz, f32, n_scans, P, st, d_edge_idx, d_n_edge, d_edge_xyz, edge_capacity(P), d_planar_idx, d_n_planar,
                      d_planar_xyz, planar_capacity(P), ctx->stream, d_gave_up, d_events + 1);
+      g_extract_route |= LOAMX_ROUTE_FUSED_COMPACT;
       return check_launch(ctx, "extract_fused_kernel");
     }
   }
@@ -420,13 +430,14 @@ int extract_dev(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_scans, con
       launch_replay(wsp<double>(ctx, WS_CURV), wsp<uint8_t>(ctx, WS_MASK), n_scans, P, st, fz, ctx->stream);
       launch_compact(d_xyz, f32, n_scans, P, st, d_edge_idx, d_n_edge, d_edge_xyz, edge_capacity(P), d_planar_idx, d_n_planar,
                      d_planar_xyz, planar_capacity(P), ctx->stream, fused_compact ? d_gave_up : nullptr, fused_compact ? d_events + 1 : nullptr);
+      g_extract_route |= fused_compact ? LOAMX_ROUTE_FUSED_COMPACT : LOAMX_ROUTE_COMPACT;
       return check_launch(ctx, "select_rows_kernel (fused)");
     }
   }
   // Round 5: between these two kernels the curvature travels as hi words | lo words with the validity in the sign bit where
   // both know that form (kFlagSplitCurv; the selection then reads 4 instead of 9 bytes per point)
   ExtractParams Pk = P;
-  if (launch_extract_split_ok(P, n_scans)) Pk.flags |= kFlagSplitCurv;
+  if (launch_extract_split_ok(P, n_scans)) Pk.flags |= kFlagSplitCurv, g_extract_route |= LOAMX_ROUTE_SPLIT_CURV;
   const bool split = (Pk.flags & kFlagSplitCurv) != 0u;
   {
     TimedScope t(ctx, LOAMX_K_CURVATURE, (double)n_scans * (double)N * ((f32 ? 21.0 : 33.0) - (split ? 1.0 : 0.0)), true);
@@ -442,20 +453,24 @@ int extract_dev(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_scans, con
     // A scan line whose wavefront gave up waiting for the lines before it (bounded wait: unusual scheduling) left its
     // features in the stage arrays; this launch then gathers the batch from them and is a no-op otherwise (every
     // workgroup reads the flag and leaves): the call stays asynchronous and never fails for that reason.
-    if (fused)
+    if (fused) {
       launch_compact(d_xyz, f32, n_scans, P, st, d_edge_idx, d_n_edge, d_edge_xyz, edge_capacity(P), d_planar_idx, d_n_planar,
                      d_planar_xyz, planar_capacity(P), ctx->stream, d_gave_up, d_events + 1);
+      g_extract_route |= LOAMX_ROUTE_FUSED_COMPACT;
+    }
   }
   CHECK_LAUNCH(ctx, "select_kernel");
   // (the split curvature form is understood by select_rows_kernel alone: had launch_select refused it on a condition
   // launch_extract_split_ok does not share, the other selection kernels would have read hi / lo words as doubles)
   if (split && !rows_ran) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "internal: split curvature form without the row selection");
-  if (fused && rows_ran && boxes && fz.box_min) boxes->min = fz.box_min, boxes->max = fz.box_max, boxes->bad = d_gave_up;
+  if (fused && rows_ran && boxes && fz.box_min)
+    boxes->min = fz.box_min, boxes->max = fz.box_max, boxes->bad = d_gave_up, g_extract_route |= LOAMX_ROUTE_BOXES;
   if (fused) return LOAMX_OK;
   {
     TimedScope t(ctx, LOAMX_K_COMPACT, 0.0, true);
     launch_compact(d_xyz, f32, n_scans, P, st, d_edge_idx, d_n_edge, d_edge_xyz, edge_capacity(P), d_planar_idx,
                    d_n_planar, d_planar_xyz, planar_capacity(P), ctx->stream);
+    g_extract_route |= LOAMX_ROUTE_COMPACT;
   }
   CHECK_LAUNCH(ctx, "compact_kernel");
   return LOAMX_OK;
@@ -983,6 +998,13 @@ int loamx_ctx_extract_counters(loamx_ctx* ctx, uint64_t* tie_replays, uint64_t* 
   }
   if (tie_replays) *tie_replays = ev[0];
   if (scan_fallbacks) *scan_fallbacks = ev[1];
+  return LOAMX_OK;
+}
+
+int loamx_ctx_last_extract_route(loamx_ctx* ctx, uint32_t* bits) {
+  if (!ctx || !bits) return LOAMX_ERR_BAD_PARAM;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  *bits = ctx->last_extract_route;
   return LOAMX_OK;
 }
 

@@ -45,6 +45,10 @@ inline void launch_kernel_named(const char* name, F kernel, const dim3& grid, co
 constexpr int kMaxNeighborPoints = 16;  // LDS halo bound of curvature_valid_kernel
 constexpr int kMaxLineWidth = 4096;     // select_kernel keeps one line's curvature + mask in LDS
 
+// LOAMX_ROUTE_* bits of the extraction the calling thread is enqueueing (loamx_ctx_last_extract_route): every launcher below
+// notes its choice here at the branch that makes it; extract_dev clears the word and keeps it on the context (host side only)
+extern thread_local uint32_t g_extract_route;
+
 // staging layout written by select_kernel: per (scan, line, sector) a fixed slot of cap entries
 struct ExtractStage {
   uint32_t* edge_stage;    // [n_scans][H][S][cap_edge]
