@@ -9,6 +9,7 @@
 #include <mutex>
 #include <utility>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include <dlfcn.h>
@@ -22,12 +23,18 @@ using namespace loamx;
 namespace {
 
 enum WsId {
-  WS_XYZ = 0, WS_CURV, WS_MASK, WS_EDGE_STAGE, WS_PLANAR_STAGE, WS_EDGE_CNT, WS_PLANAR_CNT,
-  WS_EDGE_IDX, WS_PLANAR_IDX, WS_N_EDGE, WS_N_PLANAR, WS_EDGE_XYZ, WS_PLANAR_XYZ,
-  WS_GRID_DESC_E, WS_GRID_DESC_P, WS_CELLS_E, WS_CELLS_P, WS_SORTED_E, WS_SORTED_P, WS_REL_E, WS_REL_P,
-  WS_SGRID_DESC_E, WS_SGRID_DESC_P, WS_SCELLS_E, WS_SCELLS_P, WS_SSORTED_E, WS_SSORTED_P, WS_SORT_SCRATCH, WS_SORT_SCRATCH_SRC, WS_ASSOC_E, WS_ASSOC_P, WS_NN_E, WS_NN_P, WS_RNN_E, WS_RNN_P, WS_NEAREST_E, WS_NEAREST_P, WS_REST_E, WS_REST_P, WS_EXACT_E, WS_EXACT_P, WS_NASSOC, WS_STATE, WS_PARTIALS, WS_MOM_PARTIALS, WS_MOMENTS, WS_FLAGGED_LIST, WS_FLAGGED_COUNT, WS_LINE_TOT, WS_EXTRACT_EVENTS, WS_BOX, WS_FINITE_FLAG,
-  WS_COUNTERS, WS_ITERINFO, WS_STREAM_IN0, WS_STREAM_IN1, WS_STREAM_RES, WS_DUMP_E, WS_DUMP_P, WS_FIT_IN, WS_FIT_OUT, WS_SRC_E, WS_SRC_P, WS_TGT_E, WS_TGT_P, WS_FCOUNTS, WS_RESULTS, WS_INIT, WS_STREAM_INIT,
+  WS_XYZ = 0, WS_CURV, WS_MASK,
+  WS_SORT_SCRATCH, WS_SORT_SCRATCH_SRC, WS_NASSOC, WS_STATE, WS_PARTIALS, WS_MOM_PARTIALS, WS_MOMENTS, WS_FLAGGED_LIST, WS_FLAGGED_COUNT,
+  WS_LINE_TOT, WS_EXTRACT_EVENTS, WS_BOX, WS_FINITE_FLAG, WS_COUNTERS, WS_ITERINFO, WS_STREAM_IN0, WS_STREAM_IN1, WS_STREAM_RES,
+  WS_FIT_IN, WS_FIT_OUT, WS_FCOUNTS, WS_RESULTS, WS_INIT, WS_STREAM_INIT,
   WS_COUNT
+};
+// the buffers that exist once per feature kind: loamx_ctx::wsk[id][kEdge | kPlane]
+enum WsKindId {
+  WSK_STAGE = 0, WSK_CNT, WSK_IDX, WSK_N, WSK_XYZ,
+  WSK_GRID_DESC, WSK_CELLS, WSK_SORTED, WSK_REL, WSK_SGRID_DESC, WSK_SCELLS, WSK_SSORTED, WSK_ASSOC, WSK_NN, WSK_RNN, WSK_NEAREST,
+  WSK_REST, WSK_EXACT, WSK_DUMP, WSK_SRC, WSK_TGT,
+  WSK_COUNT
 };
 
 struct Buf {
@@ -55,6 +62,7 @@ struct loamx_ctx {
   hipEvent_t ev_join2 = nullptr;
   std::string last_error;
   Buf ws[WS_COUNT];
+  Buf wsk[WSK_COUNT][2];
   uint32_t* h_pinned = nullptr;  // small pinned readback area
   bool timing = false;
   std::vector<PendingEvent> pending;
@@ -142,8 +150,7 @@ int fail(loamx_ctx* ctx, int code, const std::string& msg) {
       return fail(ctx, LOAMX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));           \
   } while (0)
 
-int ensure(loamx_ctx* ctx, int id, size_t bytes) {
-  Buf& b = ctx->ws[id];
+int ensure(loamx_ctx* ctx, Buf& b, size_t bytes) {
   if (bytes == 0) bytes = 8;
   if (b.cap >= bytes) return LOAMX_OK;
   if (b.p) {
@@ -155,6 +162,7 @@ int ensure(loamx_ctx* ctx, int id, size_t bytes) {
   b.cap = bytes;
   return LOAMX_OK;
 }
+int ensure(loamx_ctx* ctx, int id, size_t bytes) { return ensure(ctx, ctx->ws[id], bytes); }
 #define ENSURE(ctx, id, bytes)                       \
   do {                                               \
     int rc_ = ensure(ctx, id, bytes);                \
@@ -182,6 +190,10 @@ bool host_all_finite(const void* p, bool f32, size_t n_scalars) {
 template <typename T>
 T* wsp(loamx_ctx* ctx, int id) {
   return reinterpret_cast<T*>(ctx->ws[id].p);
+}
+template <typename T>
+T* wskp(loamx_ctx* ctx, int id, int kind) {
+  return reinterpret_cast<T*>(ctx->wsk[id][kind].p);
 }
 
 // timing helpers ------------------------------------------------------------------------------------
@@ -321,11 +333,11 @@ int make_reg_config(loamx_ctx* ctx, const loamx_reg_params* r, RegConfig& C) {
     return fail(ctx, LOAMX_ERR_BAD_PARAM, "min_line_fit_points must be >= 2");
   if (r->max_iterations > 1000) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "max_iterations > 1000");
   memset(&C, 0, sizeof(C));
-  C.k_edge = (int)r->num_edge_neighbors, C.k_plane = (int)r->num_plane_neighbors;
-  C.min_line_pts = (int)(r->min_line_fit_points > 64 ? 64 : r->min_line_fit_points);
-  C.min_plane_pts = (int)(r->min_plane_fit_points > 64 ? 64 : r->min_plane_fit_points);
-  C.r_edge = r->max_edge_neighbor_dist, C.r_plane = r->max_plane_neighbor_dist;
-  C.pass_edge = knn_radius_pass_max(C.r_edge), C.pass_plane = knn_radius_pass_max(C.r_plane);
+  auto kind_config = [](uint64_t k, double radius, uint64_t min_pts) {
+    return RegKindConfig{(int)k, radius, (int)(min_pts > 64 ? 64 : min_pts), knn_radius_pass_max(radius)};
+  };
+  C.kind[kEdge] = kind_config(r->num_edge_neighbors, r->max_edge_neighbor_dist, r->min_line_fit_points);
+  C.kind[kPlane] = kind_config(r->num_plane_neighbors, r->max_plane_neighbor_dist, r->min_plane_fit_points);
   C.min_line_cond = r->min_line_condition_number, C.max_avg_plane_dist = r->max_avg_point_plane_dist;
   C.max_iterations = (uint32_t)r->max_iterations;
   C.rot_thresh = r->rotation_convergence_thresh, C.pos_thresh = r->position_convergence_thresh;
@@ -379,12 +391,12 @@ int extract_dev(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_scans, con
     return LOAMX_OK;
   }
   const size_t groups = n_scans * P.H * P.S;
-  ENSURE(ctx, WS_EDGE_STAGE, groups * P.cap_edge * sizeof(uint32_t));
-  ENSURE(ctx, WS_PLANAR_STAGE, groups * P.cap_planar * sizeof(uint32_t));
-  ENSURE(ctx, WS_EDGE_CNT, groups * sizeof(uint32_t));
-  ENSURE(ctx, WS_PLANAR_CNT, groups * sizeof(uint32_t));
-  ExtractStage st{wsp<uint32_t>(ctx, WS_EDGE_STAGE), wsp<uint32_t>(ctx, WS_PLANAR_STAGE),
-                  wsp<uint32_t>(ctx, WS_EDGE_CNT), wsp<uint32_t>(ctx, WS_PLANAR_CNT)};
+  ENSURE(ctx, ctx->wsk[WSK_STAGE][kEdge], groups * P.cap_edge * sizeof(uint32_t));
+  ENSURE(ctx, ctx->wsk[WSK_STAGE][kPlane], groups * P.cap_planar * sizeof(uint32_t));
+  ENSURE(ctx, ctx->wsk[WSK_CNT][kEdge], groups * sizeof(uint32_t));
+  ENSURE(ctx, ctx->wsk[WSK_CNT][kPlane], groups * sizeof(uint32_t));
+  ExtractStage st{wskp<uint32_t>(ctx, WSK_STAGE, kEdge), wskp<uint32_t>(ctx, WSK_STAGE, kPlane),
+                  wskp<uint32_t>(ctx, WSK_CNT, kEdge), wskp<uint32_t>(ctx, WSK_CNT, kPlane)};
   // the selection writes the final feature arrays itself when it can (launch_select); its chained scan over the
   // lines of a scan needs the per-line slots zeroed
   // ... and one more word behind them: the give-up flag of that chained scan (zeroed by the same memset)
@@ -478,10 +490,13 @@ int extract_dev(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_scans, con
 
 // registration over device-resident feature sets ------------------------------------------------------
 struct RegInputs {
-  size_t n_pairs, edge_stride, planar_stride;
+  size_t n_pairs;
   uint32_t in_pitch;
-  const double *src_edge, *src_planar, *tgt_edge, *tgt_planar;
-  const uint32_t *n_src_edge, *n_src_planar, *n_tgt_edge, *n_tgt_planar;
+  struct Kind {  // as RegKind
+    size_t stride;
+    const double *src, *tgt;
+    const uint32_t *n_src, *n_tgt;
+  } kind[2];
   const double* init;
   ExtractBoxes boxes;  // (optional) bounding boxes of the sets, left by the extraction that produced them
   uint32_t src_box_offset;  // RegBatch::src_box_offset: scans from a pair's target box to its source box; 0: target boxes only
@@ -500,7 +515,7 @@ int enqueue_association(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, u
       // (a single scan-sized pair cannot fill the chip twice over: the forks and joins only add latency there —
       // one 64 x 1024 pair 1.15 ms with the auxiliary streams, 1.10 ms without; one 128 x 2048 scan against a
       // 1 M-point map the other way round: 5.9 vs 6.8 ms)
-      const bool side = (size_t)B.n_pairs * B.assoc_blocks_plane >= 128;
+      const bool side = (size_t)B.n_pairs * B.kind[kPlane].assoc_blocks >= 128;
       // sub-scope: the plane round-1 k-NN kernel alone (events attached to its own dispatch)
       PendingEvent knn{};
       LaunchScope knn_ls{nullptr, nullptr, true};
@@ -583,7 +598,7 @@ int enqueue_icf_iteration(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C,
 // host arrays of *dump (one pair); no solve, d_results untouched
 int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loamx_reg_result* d_results, bool want_iter_info,
                  AfterAssocHook hook, void* hook_user, const loamx_target_index* prebuilt = nullptr, const loamx_assoc_dump* dump = nullptr,
-                 size_t dump_n_se = 0, size_t dump_n_sp = 0) {
+                 const size_t* dump_n_src = nullptr) {
   if (in.n_pairs == 0) return LOAMX_OK;
   RegConfig C = C_in;
   // The reference's associateEdges / associatePlanes (registration.cpp:23-103) do not know max_iterations; here a pair with
@@ -592,90 +607,73 @@ int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loa
   if (dump && C.max_iterations == 0) C.max_iterations = 1;
   untimed(ctx);
   if (in.n_pairs > 0x7FFFFFFFull / 128) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "too many pairs in one call");
-  const size_t np = in.n_pairs, es = in.edge_stride ? in.edge_stride : 1, ps = in.planar_stride ? in.planar_stride : 1;
+  const size_t np = in.n_pairs, es = in.kind[kEdge].stride ? in.kind[kEdge].stride : 1, ps = in.kind[kPlane].stride ? in.kind[kPlane].stride : 1;
   if (es > 0x3FFFFFFFull || ps > 0x3FFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "feature set too large");  // (queue entries: 30-bit query index + 2 flags)
   RegBatch B{};
-  B.n_pairs = np, B.edge_stride = es, B.planar_stride = ps, B.in_pitch = in.in_pitch;
-  B.src_edge = in.src_edge, B.n_src_edge = in.n_src_edge, B.src_planar = in.src_planar, B.n_src_planar = in.n_src_planar;
-  B.tgt_edge = in.tgt_edge, B.n_tgt_edge = in.n_tgt_edge, B.tgt_planar = in.tgt_planar, B.n_tgt_planar = in.n_tgt_planar;
-  B.init = in.init;
+  B.n_pairs = np, B.in_pitch = in.in_pitch, B.init = in.init;
+  for (int k = 0; k < 2; k++) {
+    RegKind& K = B.kind[k];
+    K.stride = k ? ps : es;
+    K.src = in.kind[k].src, K.n_src = in.kind[k].n_src, K.tgt = in.kind[k].tgt, K.n_tgt = in.kind[k].n_tgt;
+    K.grid.stride = K.stride + kGridPad, K.src_grid.stride = K.stride;  // (src_grid.rel stays null: source sets are not searched)
+    K.assoc_blocks = 0xFFFFFFFFu, K.knn_mode = 0u;
+  }
   if (!(C.flags & kRegFlagNoExtractBoxes)) B.box_min = in.boxes.min, B.box_max = in.boxes.max, B.box_bad = in.boxes.bad, B.src_box_offset = in.src_box_offset;
-  ENSURE(ctx, WS_GRID_DESC_E, np * sizeof(GridDesc));
-  ENSURE(ctx, WS_GRID_DESC_P, np * sizeof(GridDesc));
-  ENSURE(ctx, WS_CELLS_E, (np * (size_t)(kGridCellsCap + 1) + 4) * sizeof(uint32_t));  // (+4: the search reads four entries at a time)
-  ENSURE(ctx, WS_CELLS_P, (np * (size_t)(kGridCellsCap + 1) + 4) * sizeof(uint32_t));
-  ENSURE(ctx, WS_SORTED_E, np * (es + kGridPad) * sizeof(GridPoint));
-  ENSURE(ctx, WS_SORTED_P, np * (ps + kGridPad) * sizeof(GridPoint));
-  ENSURE(ctx, WS_REL_E, np * 3 * (es + kGridPad) * sizeof(float));
-  ENSURE(ctx, WS_REL_P, np * 3 * (ps + kGridPad) * sizeof(float));
-  ENSURE(ctx, WS_SGRID_DESC_E, np * sizeof(GridDesc));
-  ENSURE(ctx, WS_SGRID_DESC_P, np * sizeof(GridDesc));
-  ENSURE(ctx, WS_SCELLS_E, np * (size_t)(kGridCellsCap + 1) * sizeof(uint32_t));
-  ENSURE(ctx, WS_SCELLS_P, np * (size_t)(kGridCellsCap + 1) * sizeof(uint32_t));
-  ENSURE(ctx, WS_SSORTED_E, np * es * sizeof(GridPoint));
-  ENSURE(ctx, WS_SSORTED_P, np * ps * sizeof(GridPoint));
-  ENSURE(ctx, WS_SORT_SCRATCH, np * (es > ps ? es : ps) * sizeof(GridPoint));
-  // (sets the packed build takes are ordered in LDS and need no scratch: the predicate is the launcher's own)
-  ENSURE(ctx, WS_SORT_SCRATCH_SRC, grid_small(es > ps ? es : ps, C.flags) ? sizeof(GridPoint) : np * (es > ps ? es : ps) * sizeof(GridPoint));
-  ENSURE(ctx, WS_ASSOC_E, 9 * np * es * sizeof(double));
-  ENSURE(ctx, WS_ASSOC_P, 7 * np * ps * sizeof(double));
-  // (neighbour lists: the count + as many positions as the kernel variant in use keeps: 5, 8 or 16 — launch_associate)
-  const size_t km_e = C.k_edge <= 5 ? 5 : (C.k_edge <= 8 ? 8 : kMaxK), km_p = C.k_plane <= 5 ? 5 : (C.k_plane <= 8 ? 8 : kMaxK);
-  ENSURE(ctx, WS_NN_E, (1 + km_e) * np * es * sizeof(uint32_t));
-  ENSURE(ctx, WS_NN_P, (1 + km_p) * np * ps * sizeof(uint32_t));
-  ENSURE(ctx, WS_RNN_E, (1 + km_e) * np * es * sizeof(uint32_t));
-  ENSURE(ctx, WS_RNN_P, (1 + km_p) * np * ps * sizeof(uint32_t));
-  ENSURE(ctx, WS_NEAREST_E, np * es * sizeof(uint32_t));
-  ENSURE(ctx, WS_NEAREST_P, np * ps * sizeof(uint32_t));
-  ENSURE(ctx, WS_REST_E, np * es * sizeof(uint32_t));
-  ENSURE(ctx, WS_REST_P, np * ps * sizeof(uint32_t));
-  ENSURE(ctx, WS_EXACT_E, np * es * sizeof(uint32_t));
-  ENSURE(ctx, WS_EXACT_P, np * ps * sizeof(uint32_t));
-  ENSURE(ctx, WS_NASSOC, np * 8 * sizeof(uint32_t));
-  ENSURE(ctx, WS_STATE, np * sizeof(PairState));
   B.blocks_per_pair = (uint32_t)((es + ps + kSweepChunk - 1) / kSweepChunk);
-  ENSURE(ctx, WS_PARTIALS, np * B.blocks_per_pair * kAccSize * sizeof(double));
   B.mom_blocks_per_pair = (uint32_t)((ps + kSweepChunk - 1) / kSweepChunk);
-  ENSURE(ctx, WS_MOM_PARTIALS, np * B.mom_blocks_per_pair * 4 * (size_t)(kMomSize + 2) * sizeof(double));
-  ENSURE(ctx, WS_MOMENTS, np * (size_t)(kMomSize + 2) * sizeof(double));
-  ENSURE(ctx, WS_FLAGGED_LIST, np * (size_t)B.mom_blocks_per_pair * kSweepChunk * sizeof(uint32_t));
-  ENSURE(ctx, WS_FLAGGED_COUNT, np * (size_t)B.mom_blocks_per_pair * 4 * sizeof(uint32_t));
+  // The registration's scratch, each buffer described once: where it lives, its size, the RegBatch field it binds to. SCRATCH
+  // allocates (one hipMalloc per buffer, grown as by ENSURE), fills with 0xFF bytes under DEBUG_POISON and binds.
+  auto scratch = [&](Buf& b, size_t bytes, auto*& field) -> int {
+    ENSURE(ctx, b, bytes);
+    if ((C.flags & kRegFlagPoison) && b.p) HIP_TRY(ctx, hipMemsetAsync(b.p, 0xFF, b.cap, ctx->stream));
+    field = reinterpret_cast<std::remove_reference_t<decltype(field)>>(b.p);
+    return LOAMX_OK;
+  };
+#define SCRATCH(buf, bytes, field)                \
+  do {                                            \
+    int rc_ = scratch(buf, bytes, field);         \
+    if (rc_ != LOAMX_OK) return rc_;              \
+  } while (0)
+  // per kind: K = the kind's RegKind, st = its stride, km = the neighbour list positions the kernel variant in use keeps (5, 8 or
+  // 16 — launch_associate), rec = the fields of its association record
+#define SCRATCH_K(id, bytes, field)                                                                        \
+  for (int k = 0; k < 2; k++) {                                                                            \
+    RegKind& K = B.kind[k];                                                                                \
+    const size_t st = K.stride, km = C.kind[k].k <= 5 ? 5 : (C.kind[k].k <= 8 ? 8 : kMaxK), rec = k ? 7 : 9; \
+    SCRATCH(ctx->wsk[id][k], bytes, K.field);                                                              \
+  }
+  SCRATCH_K(WSK_GRID_DESC, np * sizeof(GridDesc), grid.desc)
+  SCRATCH_K(WSK_CELLS, (np * (size_t)(kGridCellsCap + 1) + 4) * sizeof(uint32_t), grid.cell_start)  // (+4: the search reads four entries at a time)
+  SCRATCH_K(WSK_SORTED, np * (st + kGridPad) * sizeof(GridPoint), grid.sorted)
+  SCRATCH_K(WSK_REL, np * 3 * (st + kGridPad) * sizeof(float), grid.rel)
+  SCRATCH_K(WSK_SGRID_DESC, np * sizeof(GridDesc), src_grid.desc)
+  SCRATCH_K(WSK_SCELLS, np * (size_t)(kGridCellsCap + 1) * sizeof(uint32_t), src_grid.cell_start)
+  SCRATCH_K(WSK_SSORTED, np * st * sizeof(GridPoint), src_grid.sorted)
+  SCRATCH(ctx->ws[WS_SORT_SCRATCH], np * (es > ps ? es : ps) * sizeof(GridPoint), B.sort_scratch);
+  // (sets the packed build takes are ordered in LDS and need no scratch: the predicate is the launcher's own)
+  SCRATCH(ctx->ws[WS_SORT_SCRATCH_SRC], grid_small(es > ps ? es : ps, C.flags) ? sizeof(GridPoint) : np * (es > ps ? es : ps) * sizeof(GridPoint), B.sort_scratch_src);
+  SCRATCH_K(WSK_ASSOC, rec * np * st * sizeof(double), rec)
+  SCRATCH_K(WSK_NN, (1 + km) * np * st * sizeof(uint32_t), nn)
+  SCRATCH_K(WSK_RNN, (1 + km) * np * st * sizeof(uint32_t), rnn)
+  SCRATCH_K(WSK_NEAREST, np * st * sizeof(uint32_t), nearest)
+  SCRATCH_K(WSK_REST, np * st * sizeof(uint32_t), rest)
+  SCRATCH_K(WSK_EXACT, np * st * sizeof(uint32_t), exact)
+  SCRATCH(ctx->ws[WS_NASSOC], np * 8 * sizeof(uint32_t), B.n_assoc);
+  SCRATCH(ctx->ws[WS_STATE], np * sizeof(PairState), B.state);
+  SCRATCH(ctx->ws[WS_PARTIALS], np * B.blocks_per_pair * kAccSize * sizeof(double), B.partials);
+  SCRATCH(ctx->ws[WS_MOM_PARTIALS], np * B.mom_blocks_per_pair * 4 * (size_t)(kMomSize + 2) * sizeof(double), B.mom_partials);
+  SCRATCH(ctx->ws[WS_MOMENTS], np * (size_t)(kMomSize + 2) * sizeof(double), B.moments);
+  SCRATCH(ctx->ws[WS_FLAGGED_LIST], np * (size_t)B.mom_blocks_per_pair * kSweepChunk * sizeof(uint32_t), B.flagged_list);
+  SCRATCH(ctx->ws[WS_FLAGGED_COUNT], np * (size_t)B.mom_blocks_per_pair * 4 * sizeof(uint32_t), B.flagged_count);
+#undef SCRATCH_K
+#undef SCRATCH
   {
     const bool fresh = ctx->ws[WS_COUNTERS].cap == 0;
     ENSURE(ctx, WS_COUNTERS, 128);
     untimed(ctx);
     if (fresh) HIP_TRY(ctx, hipMemsetAsync(ctx->ws[WS_COUNTERS].p, 0, 128, ctx->stream));
   }
-  if (C.flags & kRegFlagPoison) {  // debugging: every scratch buffer of the registration starts as 0xFF bytes
-    static const int kScratch[] = {WS_GRID_DESC_E, WS_GRID_DESC_P, WS_CELLS_E, WS_CELLS_P, WS_SORTED_E, WS_SORTED_P, WS_REL_E, WS_REL_P,
-                                   WS_SGRID_DESC_E, WS_SGRID_DESC_P, WS_SCELLS_E, WS_SCELLS_P, WS_SSORTED_E, WS_SSORTED_P, WS_SORT_SCRATCH, WS_SORT_SCRATCH_SRC,
-                                   WS_ASSOC_E, WS_ASSOC_P, WS_NN_E, WS_NN_P, WS_RNN_E, WS_RNN_P, WS_NEAREST_E, WS_NEAREST_P, WS_REST_E,
-                                   WS_REST_P, WS_EXACT_E, WS_EXACT_P, WS_NASSOC, WS_STATE, WS_PARTIALS, WS_MOM_PARTIALS, WS_MOMENTS,
-                                   WS_FLAGGED_LIST, WS_FLAGGED_COUNT};
-    for (int id : kScratch)
-      if (ctx->ws[id].p) HIP_TRY(ctx, hipMemsetAsync(ctx->ws[id].p, 0xFF, ctx->ws[id].cap, ctx->stream));
-  }
   if (want_iter_info) ENSURE(ctx, WS_ITERINFO, np * (size_t)(C.max_iterations ? C.max_iterations : 1) * sizeof(loamx_iter_info));
-  B.grid_edge = GridSet{wsp<GridDesc>(ctx, WS_GRID_DESC_E), wsp<uint32_t>(ctx, WS_CELLS_E), wsp<GridPoint>(ctx, WS_SORTED_E), es + kGridPad,
-                        wsp<float>(ctx, WS_REL_E)};
-  B.grid_plane = GridSet{wsp<GridDesc>(ctx, WS_GRID_DESC_P), wsp<uint32_t>(ctx, WS_CELLS_P), wsp<GridPoint>(ctx, WS_SORTED_P), ps + kGridPad,
-                         wsp<float>(ctx, WS_REL_P)};
-  B.src_grid_edge = GridSet{wsp<GridDesc>(ctx, WS_SGRID_DESC_E), wsp<uint32_t>(ctx, WS_SCELLS_E), wsp<GridPoint>(ctx, WS_SSORTED_E), es, nullptr};
-  B.src_grid_plane = GridSet{wsp<GridDesc>(ctx, WS_SGRID_DESC_P), wsp<uint32_t>(ctx, WS_SCELLS_P), wsp<GridPoint>(ctx, WS_SSORTED_P), ps, nullptr};
-  B.sort_scratch = wsp<GridPoint>(ctx, WS_SORT_SCRATCH);
-  B.sort_scratch_src = wsp<GridPoint>(ctx, WS_SORT_SCRATCH_SRC);
-  B.assoc = AssocBuffers{wsp<double>(ctx, WS_ASSOC_E), wsp<double>(ctx, WS_ASSOC_P), wsp<uint32_t>(ctx, WS_NN_E),
-                         wsp<uint32_t>(ctx, WS_NN_P), wsp<uint32_t>(ctx, WS_RNN_E), wsp<uint32_t>(ctx, WS_RNN_P),
-                         wsp<uint32_t>(ctx, WS_NEAREST_E),
-                         wsp<uint32_t>(ctx, WS_NEAREST_P), wsp<uint32_t>(ctx, WS_REST_E), wsp<uint32_t>(ctx, WS_REST_P),
-                         wsp<uint32_t>(ctx, WS_EXACT_E), wsp<uint32_t>(ctx, WS_EXACT_P),
-                         wsp<uint32_t>(ctx, WS_NASSOC)};
-  B.state = wsp<PairState>(ctx, WS_STATE);
-  B.partials = wsp<double>(ctx, WS_PARTIALS);
-  B.mom_partials = wsp<double>(ctx, WS_MOM_PARTIALS);
-  B.moments = wsp<double>(ctx, WS_MOMENTS);
-  B.flagged_list = wsp<uint32_t>(ctx, WS_FLAGGED_LIST);
-  B.flagged_count = wsp<uint32_t>(ctx, WS_FLAGGED_COUNT);
   // counters: [0] n_active (u32), [8..48) sweep / association / moment slot counters (5 x u64), [48..56) index-build bytes
   B.n_active = wsp<uint32_t>(ctx, WS_COUNTERS);
   B.sweep_slots = reinterpret_cast<unsigned long long*>(wsp<unsigned char>(ctx, WS_COUNTERS) + 8);
@@ -685,8 +683,6 @@ int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loa
   B.want_nearest = hook ? 1u : 0u;
   B.ref_moments = (C.flags & (kRegFlagNoMoments | kRegFlagNoRefMoments)) ? 0u : 1u;
   B.max_counts = wsp<uint32_t>(ctx, WS_COUNTERS) + 16;  // bytes 64..88
-  B.assoc_blocks_edge = B.assoc_blocks_plane = 0xFFFFFFFFu;
-  B.knn_mode_edge = B.knn_mode_plane = 0u;
   B.small_edge_sets = (C.flags & kRegFlagNoSmallSets) ? 0u : (!prebuilt ? 1u : (prebuilt->n[0] <= kBruteMax ? 2u : 0u));
   hipStream_t s = ctx->stream;
   // The per-pair state first: its kernel also finds the largest source sets, which come back to the host while
@@ -705,8 +701,8 @@ int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loa
   HIP_TRY(ctx, hipEventRecord(ctx->ev_counts, s));
 
   if (prebuilt) {  // persistent target index: only the source sets are (re)ordered
-    B.grid_edge = GridSet{prebuilt->desc[0], prebuilt->cells[0], prebuilt->sorted[0], prebuilt->cap[0] + kGridPad, prebuilt->rel[0], prebuilt->cells_cap[0]};
-    B.grid_plane = GridSet{prebuilt->desc[1], prebuilt->cells[1], prebuilt->sorted[1], prebuilt->cap[1] + kGridPad, prebuilt->rel[1], prebuilt->cells_cap[1]};
+    for (int k = 0; k < 2; k++)
+      B.kind[k].grid = GridSet{prebuilt->desc[k], prebuilt->cells[k], prebuilt->sorted[k], prebuilt->cap[k] + kGridPad, prebuilt->rel[k], prebuilt->cells_cap[k]};
   }
   {
     TimedScope t(ctx, LOAMX_K_GRID, 0.0);
@@ -725,25 +721,24 @@ int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loa
   }
   CHECK_LAUNCH(ctx, "grid_build_kernel");
   HIP_TRY(ctx, hipEventSynchronize(ctx->ev_counts));
-  B.assoc_blocks_edge = (ctx->h_pinned[16] + 255u) / 256u;   // kAssocThreads queries per workgroup
-  B.assoc_blocks_plane = (ctx->h_pinned[17] + 255u) / 256u;
-  {  // which of the two k-NN kernels of a feature kind has work at all (target sizes relative to kBruteMax)
-    uint32_t tmax[2] = {ctx->h_pinned[18], ctx->h_pinned[19]}, tmin[2] = {ctx->h_pinned[20], ctx->h_pinned[21]};
-    if (prebuilt) tmax[0] = tmin[0] = (uint32_t)prebuilt->n[0], tmax[1] = tmin[1] = (uint32_t)prebuilt->n[1];
-    uint32_t* mode[2] = {&B.knn_mode_edge, &B.knn_mode_plane};
-    for (int k = 0; k < 2; k++) *mode[k] = tmin[k] > tmax[k] ? 0u : (tmin[k] > kBruteMax ? 1u : (tmax[k] <= kBruteMax ? 2u : 0u));
+  // the counts read back: [16, 17] largest source edge / planar set, [18, 19] largest and [20, 21] smallest target set
+  for (int k = 0; k < 2; k++) {
+    B.kind[k].assoc_blocks = (ctx->h_pinned[16 + k] + 255u) / 256u;  // kAssocThreads queries per workgroup
+    // which of the two k-NN kernels of a feature kind has work at all (target sizes relative to kBruteMax)
+    const uint32_t tmax = prebuilt ? (uint32_t)prebuilt->n[k] : ctx->h_pinned[18 + k], tmin = prebuilt ? tmax : ctx->h_pinned[20 + k];
+    B.kind[k].knn_mode = tmin > tmax ? 0u : (tmin > kBruteMax ? 1u : (tmax <= kBruteMax ? 2u : 0u));
   }
   if (dump) {
     if (np != 1) return fail(ctx, LOAMX_ERR_BAD_PARAM, "association dump: one pair at a time");
     int rc_a = enqueue_association(ctx, B, C);
     if (rc_a != LOAMX_OK) return rc_a;
     untimed(ctx);
-    const size_t n[2] = {dump_n_se, dump_n_sp}, kq[2] = {(size_t)C.k_edge, (size_t)C.k_plane}, pw[2] = {6, 4};
+    const size_t n[2] = {dump_n_src[kEdge], dump_n_src[kPlane]}, kq[2] = {(size_t)C.kind[kEdge].k, (size_t)C.kind[kPlane].k}, pw[2] = {6, 4};
     AssocDumpSet D[2] = {};
     for (int kind = 0; kind < 2; kind++) {
       const size_t bytes = n[kind] * (24 + 8 * pw[kind] + 4 + 4 * kq[kind] + 1) + 64;
-      ENSURE(ctx, kind ? WS_DUMP_P : WS_DUMP_E, bytes);
-      unsigned char* base = wsp<unsigned char>(ctx, kind ? WS_DUMP_P : WS_DUMP_E);
+      ENSURE(ctx, ctx->wsk[WSK_DUMP][kind], bytes);
+      unsigned char* base = wskp<unsigned char>(ctx, WSK_DUMP, kind);
       HIP_TRY(ctx, hipMemsetAsync(base, 0, bytes, s));  // (features beyond the capacity, if any, read as "no neighbours")
       D[kind].moved = reinterpret_cast<double*>(base);
       D[kind].prim = D[kind].moved + 3 * n[kind];
@@ -752,7 +747,7 @@ int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loa
       D[kind].valid = reinterpret_cast<uint8_t*>(D[kind].nn_idx + kq[kind] * n[kind]);
       if (n[kind] == 0) D[kind].nn_count = nullptr;
     }
-    launch_assoc_dump(B, C, D[0], D[1], s);
+    launch_assoc_dump(B, C, D, s);
     CHECK_LAUNCH(ctx, "assoc_dump_kernel");
     struct Out { void* host; const void* dev; size_t bytes; };
     const Out outs[10] = {
@@ -762,7 +757,7 @@ int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loa
         {dump->plane_moved, D[1].moved, 24 * n[1]}, {dump->plane_planes, D[1].prim, 32 * n[1]}};
     for (const Out& o : outs)
       if (o.host && o.bytes && o.dev) HIP_TRY(ctx, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, s));
-    if (dump->queue_lengths) HIP_TRY(ctx, hipMemcpyAsync(dump->queue_lengths, B.assoc.n_assoc + 2, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (dump->queue_lengths) HIP_TRY(ctx, hipMemcpyAsync(dump->queue_lengths, B.n_assoc + 2, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     return LOAMX_OK;
   }
@@ -905,6 +900,9 @@ void loamx_ctx_destroy(loamx_ctx* ctx) {
   for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
   for (Buf& b : ctx->ws)
     if (b.p) (void)hipFree(b.p);
+  for (Buf(&bk)[2] : ctx->wsk)
+    for (Buf& b : bk)
+      if (b.p) (void)hipFree(b.p);
   if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
   if (ctx->aux_stream) {
     (void)hipStreamSynchronize(ctx->aux_stream);
@@ -1094,24 +1092,23 @@ static int host_extract(loamx_ctx* ctx, const void* xyz, bool f32, size_t n_poin
   const size_t scalar = f32 ? sizeof(float) : sizeof(double);
   if (!xyz) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
   ENSURE(ctx, WS_XYZ, n_points * 3 * scalar);
-  ENSURE(ctx, WS_EDGE_IDX, ecap * sizeof(uint32_t));
-  ENSURE(ctx, WS_PLANAR_IDX, pcap * sizeof(uint32_t));
-  ENSURE(ctx, WS_N_EDGE, sizeof(uint32_t));
-  ENSURE(ctx, WS_N_PLANAR, sizeof(uint32_t));
+  ENSURE(ctx, ctx->wsk[WSK_IDX][kEdge], ecap * sizeof(uint32_t));
+  ENSURE(ctx, ctx->wsk[WSK_IDX][kPlane], pcap * sizeof(uint32_t));
+  for (int k = 0; k < 2; k++) ENSURE(ctx, ctx->wsk[WSK_N][k], sizeof(uint32_t));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_XYZ].p, xyz, n_points * 3 * scalar, hipMemcpyHostToDevice, ctx->stream));
   rc = dev_check_finite(ctx, ctx->ws[WS_XYZ].p, f32, nullptr, 1, n_points, 1, true);
   if (rc != LOAMX_OK) return rc;
-  rc = extract_dev(ctx, ctx->ws[WS_XYZ].p, f32, 1, P, wsp<uint32_t>(ctx, WS_EDGE_IDX), wsp<uint32_t>(ctx, WS_N_EDGE), nullptr,
-                   wsp<uint32_t>(ctx, WS_PLANAR_IDX), wsp<uint32_t>(ctx, WS_N_PLANAR), nullptr, false);
+  rc = extract_dev(ctx, ctx->ws[WS_XYZ].p, f32, 1, P, wskp<uint32_t>(ctx, WSK_IDX, kEdge), wskp<uint32_t>(ctx, WSK_N, kEdge), nullptr,
+                   wskp<uint32_t>(ctx, WSK_IDX, kPlane), wskp<uint32_t>(ctx, WSK_N, kPlane), nullptr, false);
   if (rc != LOAMX_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(&ctx->h_pinned[0], ctx->ws[WS_N_EDGE].p, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(&ctx->h_pinned[1], ctx->ws[WS_N_PLANAR].p, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&ctx->h_pinned[0], ctx->wsk[WSK_N][kEdge].p, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&ctx->h_pinned[1], ctx->wsk[WSK_N][kPlane].p, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   const size_t ne = ctx->h_pinned[0], npl = ctx->h_pinned[1];
   *n_edge = ne, *n_planar = npl;
   if (ne > edge_cap || npl > planar_cap) return fail(ctx, LOAMX_ERR_CAPACITY, "feature index capacity too small");
-  if (ne) HIP_TRY(ctx, hipMemcpy(edge_idx, ctx->ws[WS_EDGE_IDX].p, ne * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (npl) HIP_TRY(ctx, hipMemcpy(planar_idx, ctx->ws[WS_PLANAR_IDX].p, npl * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (ne) HIP_TRY(ctx, hipMemcpy(edge_idx, ctx->wsk[WSK_IDX][kEdge].p, ne * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (npl) HIP_TRY(ctx, hipMemcpy(planar_idx, ctx->wsk[WSK_IDX][kPlane].p, npl * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return LOAMX_OK;
 }
 
@@ -1130,14 +1127,14 @@ int loamx_extract_features_f32(loamx_ctx* ctx, const float* xyz, size_t n_points
 namespace {
 struct DetailHook {
   loamx_reg_detail* detail;
-  size_t n_se, n_sp;
+  size_t n_src[2];
 };
 int detail_hook(loamx_ctx* ctx, const RegBatch& B, uint32_t it, void* user) {
   DetailHook* h = static_cast<DetailHook*>(user);
   loamx_reg_detail* d = h->detail;
   if (!d) return LOAMX_OK;
   for (int kind = 0; kind < 2; kind++) {
-    const size_t n = kind ? h->n_sp : h->n_se;
+    const size_t n = h->n_src[kind];
     uint32_t* base = kind ? d->plane_pairs : d->edge_pairs;
     const size_t cap = kind ? d->pairs_cap_plane : d->pairs_cap_edge;
     uint32_t* out_n = kind ? d->n_plane_pairs : d->n_edge_pairs;
@@ -1146,7 +1143,7 @@ int detail_hook(loamx_ctx* ctx, const RegBatch& B, uint32_t it, void* user) {
     if (cap == 0 || n == 0) continue;
     uint32_t* out = base + (size_t)it * 2 * cap;
     std::vector<uint32_t> nearest(n);
-    HIP_TRY(ctx, hipMemcpyAsync(nearest.data(), kind ? B.assoc.nearest_plane : B.assoc.nearest_edge, n * sizeof(uint32_t),
+    HIP_TRY(ctx, hipMemcpyAsync(nearest.data(), B.kind[kind].nearest, n * sizeof(uint32_t),
                                 hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     size_t m = 0;
@@ -1161,9 +1158,11 @@ int detail_hook(loamx_ctx* ctx, const RegBatch& B, uint32_t it, void* user) {
 }
 }  // namespace
 
-static int register_features_impl(loamx_ctx* ctx, const loamx_target_index* index, const double* src_edge, size_t n_se,
-                                  const double* src_planar, size_t n_sp, const double* tgt_edge, size_t n_te,
-                                  const double* tgt_planar, size_t n_tp, const double init_pose[7],
+struct HostSets {  // one scan's feature sets in host memory, [edge, plane]
+  const double* pts[2];
+  size_t n[2];
+};
+static int register_features_impl(loamx_ctx* ctx, const loamx_target_index* index, const HostSets& src, HostSets tgt, const double init_pose[7],
                                   const loamx_reg_params* reg, loamx_reg_result* result, loamx_reg_detail* detail,
                                   const loamx_assoc_dump* dump = nullptr) {
   if (!ctx) return LOAMX_ERR_BAD_PARAM;
@@ -1174,36 +1173,38 @@ static int register_features_impl(loamx_ctx* ctx, const loamx_target_index* inde
   int rc = make_reg_config(ctx, reg, C);
   if (rc != LOAMX_OK) return rc;
   if (index) {
-    if (index->radius[0] != C.r_edge || index->radius[1] != C.r_plane)
+    if (index->radius[kEdge] != C.kind[kEdge].r || index->radius[kPlane] != C.kind[kPlane].r)
       return fail(ctx, LOAMX_ERR_BAD_PARAM, "registration params do not match the ones the target index was built with");
     // (an insert that failed between growing a set and rebuilding its grid leaves n ahead of the grid)
     for (int k = 0; k < 2; k++)
       if (index->n[k] != 0 && !index->grid_valid[k])
         return fail(ctx, LOAMX_ERR_BAD_PARAM, "the target index is inconsistent (an insert into it failed): insert again or build a new one");
-    n_te = 0, n_tp = 0;  // the target lives in the index
+    tgt.n[kEdge] = tgt.n[kPlane] = 0;  // the target lives in the index
   }
-  const size_t es = n_se > n_te ? n_se : n_te, ps = n_sp > n_tp ? n_sp : n_tp;
-  if (es > 0x3FFFFFFFull || ps > 0x3FFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "feature set too large");  // (queue entries: 30-bit query index + 2 flags)
+  size_t stride[2];
+  for (int k = 0; k < 2; k++) {
+    stride[k] = src.n[k] > tgt.n[k] ? src.n[k] : tgt.n[k];
+    if (stride[k] > 0x3FFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "feature set too large");  // (queue entries: 30-bit query index + 2 flags)
+  }
   if (!host_all_finite(init_pose, false, 7)) return fail(ctx, LOAMX_ERR_BAD_PARAM, kNonFiniteMsg);
   hipStream_t s = ctx->stream;
-  const size_t esz = (es ? es : 1) * 3 * sizeof(double), psz = (ps ? ps : 1) * 3 * sizeof(double);
-  ENSURE(ctx, WS_SRC_E, esz);
-  ENSURE(ctx, WS_TGT_E, esz);
-  ENSURE(ctx, WS_SRC_P, psz);
-  ENSURE(ctx, WS_TGT_P, psz);
+  for (int k = 0; k < 2; k++) {
+    ENSURE(ctx, ctx->wsk[WSK_SRC][k], (stride[k] ? stride[k] : 1) * 3 * sizeof(double));
+    ENSURE(ctx, ctx->wsk[WSK_TGT][k], (stride[k] ? stride[k] : 1) * 3 * sizeof(double));
+  }
   ENSURE(ctx, WS_FCOUNTS, 4 * sizeof(uint32_t));
   ENSURE(ctx, WS_RESULTS, sizeof(loamx_reg_result));
   ENSURE(ctx, WS_INIT, 7 * sizeof(double));
-  if (n_se) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_SRC_E].p, src_edge, n_se * 24, hipMemcpyHostToDevice, s));
-  if (n_te) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_TGT_E].p, tgt_edge, n_te * 24, hipMemcpyHostToDevice, s));
-  if (n_sp) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_SRC_P].p, src_planar, n_sp * 24, hipMemcpyHostToDevice, s));
-  if (n_tp) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_TGT_P].p, tgt_planar, n_tp * 24, hipMemcpyHostToDevice, s));
-  const uint32_t counts[4] = {(uint32_t)n_se, (uint32_t)n_sp, (uint32_t)n_te, (uint32_t)n_tp};
+  for (int k = 0; k < 2; k++) {
+    if (src.n[k]) HIP_TRY(ctx, hipMemcpyAsync(ctx->wsk[WSK_SRC][k].p, src.pts[k], src.n[k] * 24, hipMemcpyHostToDevice, s));
+    if (tgt.n[k]) HIP_TRY(ctx, hipMemcpyAsync(ctx->wsk[WSK_TGT][k].p, tgt.pts[k], tgt.n[k] * 24, hipMemcpyHostToDevice, s));
+  }
+  const uint32_t counts[4] = {(uint32_t)src.n[kEdge], (uint32_t)src.n[kPlane], (uint32_t)tgt.n[kEdge], (uint32_t)tgt.n[kPlane]};
   {  // non-finite coordinates are refused before anything else is launched (loamx.h: "Non-finite input")
     rc = finite_begin(ctx);
     if (rc != LOAMX_OK) return rc;
-    finite_add(ctx, ctx->ws[WS_SRC_E].p, false, nullptr, 1, n_se, 1), finite_add(ctx, ctx->ws[WS_TGT_E].p, false, nullptr, 1, n_te, 1);
-    finite_add(ctx, ctx->ws[WS_SRC_P].p, false, nullptr, 1, n_sp, 1), finite_add(ctx, ctx->ws[WS_TGT_P].p, false, nullptr, 1, n_tp, 1);
+    for (int k = 0; k < 2; k++)
+      finite_add(ctx, ctx->wsk[WSK_SRC][k].p, false, nullptr, 1, src.n[k], 1), finite_add(ctx, ctx->wsk[WSK_TGT][k].p, false, nullptr, 1, tgt.n[k], 1);
     rc = finite_end(ctx);
     if (rc != LOAMX_OK) return rc;
   }
@@ -1211,16 +1212,15 @@ static int register_features_impl(loamx_ctx* ctx, const loamx_target_index* inde
   HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_INIT].p, init_pose, 7 * sizeof(double), hipMemcpyHostToDevice, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));  // `counts` is a stack array
   RegInputs in{};
-  in.n_pairs = 1, in.edge_stride = es, in.planar_stride = ps, in.in_pitch = 1;
-  in.src_edge = wsp<double>(ctx, WS_SRC_E), in.src_planar = wsp<double>(ctx, WS_SRC_P);
-  in.tgt_edge = wsp<double>(ctx, WS_TGT_E), in.tgt_planar = wsp<double>(ctx, WS_TGT_P);
+  in.n_pairs = 1, in.in_pitch = 1;
   const uint32_t* fc = wsp<uint32_t>(ctx, WS_FCOUNTS);
-  in.n_src_edge = fc, in.n_src_planar = fc + 1, in.n_tgt_edge = fc + 2, in.n_tgt_planar = fc + 3;
+  for (int k = 0; k < 2; k++)
+    in.kind[k] = RegInputs::Kind{stride[k], wskp<double>(ctx, WSK_SRC, k), wskp<double>(ctx, WSK_TGT, k), fc + k, fc + 2 + k};
   in.init = wsp<double>(ctx, WS_INIT);
-  DetailHook hook{detail, n_se, n_sp};
+  DetailHook hook{detail, {src.n[kEdge], src.n[kPlane]}};
   if (detail) detail->n_iter_info = 0;
   rc = register_dev(ctx, in, C, wsp<loamx_reg_result>(ctx, WS_RESULTS), detail && detail->iter_info,
-                    detail ? detail_hook : nullptr, &hook, index, dump, n_se, n_sp);
+                    detail ? detail_hook : nullptr, &hook, index, dump, src.n);
   if (rc != LOAMX_OK || dump) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(result, ctx->ws[WS_RESULTS].p, sizeof(loamx_reg_result), hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -1236,7 +1236,7 @@ int loamx_register_features(loamx_ctx* ctx, const double* src_edge, size_t n_se,
                             const double* tgt_edge, size_t n_te, const double* tgt_planar, size_t n_tp,
                             const double init_pose[7], const loamx_reg_params* reg, loamx_reg_result* result,
                             loamx_reg_detail* detail) {
-  return register_features_impl(ctx, nullptr, src_edge, n_se, src_planar, n_sp, tgt_edge, n_te, tgt_planar, n_tp, init_pose,
+  return register_features_impl(ctx, nullptr, {{src_edge, src_planar}, {n_se, n_sp}}, {{tgt_edge, tgt_planar}, {n_te, n_tp}}, init_pose,
                                 reg, result, detail);
 }
 
@@ -1244,7 +1244,7 @@ int loamx_register_features_indexed(loamx_ctx* ctx, const loamx_target_index* in
                                     const double* src_planar, size_t n_sp, const double init_pose[7],
                                     const loamx_reg_params* reg, loamx_reg_result* result, loamx_reg_detail* detail) {
   if (!index) return LOAMX_ERR_BAD_PARAM;
-  return register_features_impl(ctx, index, src_edge, n_se, src_planar, n_sp, nullptr, 0, nullptr, 0, init_pose, reg, result,
+  return register_features_impl(ctx, index, {{src_edge, src_planar}, {n_se, n_sp}}, {{nullptr, nullptr}, {0, 0}}, init_pose, reg, result,
                                 detail);
 }
 
@@ -1253,7 +1253,7 @@ int loamx_associate(loamx_ctx* ctx, const double* src_edge, size_t n_se, const d
                     size_t n_te, const double* tgt_planar, size_t n_tp, const double pose[7], const loamx_reg_params* reg,
                     loamx_assoc_dump* out) {
   if (!out) return LOAMX_ERR_BAD_PARAM;
-  return register_features_impl(ctx, nullptr, src_edge, n_se, src_planar, n_sp, tgt_edge, n_te, tgt_planar, n_tp, pose, reg, nullptr,
+  return register_features_impl(ctx, nullptr, {{src_edge, src_planar}, {n_se, n_sp}}, {{tgt_edge, tgt_planar}, {n_te, n_tp}}, pose, reg, nullptr,
                                 nullptr, out);
 }
 
@@ -1386,13 +1386,13 @@ int index_build(loamx_ctx* ctx, loamx_target_index* idx, unsigned kinds = 3u) {
   const uint32_t counts[2] = {(uint32_t)idx->n[0], (uint32_t)idx->n[1]};
   HIP_TRY(ctx, hipMemcpyAsync(idx->counts, counts, sizeof(counts), hipMemcpyHostToDevice, s));
   RegConfig C{};
-  C.r_edge = idx->radius[0], C.r_plane = idx->radius[1];
   C.flags = ctx->reg_flags;
   RegBatch B{};
   B.n_pairs = 1, B.in_pitch = 1;
-  B.edge_stride = idx->cap[0], B.planar_stride = idx->cap[1];
-  B.tgt_edge = idx->pts[0], B.tgt_planar = idx->pts[1];
-  B.n_tgt_edge = idx->counts, B.n_tgt_planar = idx->counts + 1;
+  for (int k = 0; k < 2; k++) {
+    C.kind[k].r = idx->radius[k];
+    B.kind[k].stride = idx->cap[k], B.kind[k].tgt = idx->pts[k], B.kind[k].n_tgt = idx->counts + k;
+  }
   // map-sized sets get a cell table of up to kGridMapCellsCap entries (the scan-sized table of 65 536 would put
   // hundreds of points of a million-point map into every cell); tables and cursors grow with the set
   size_t scratch_need = kGridBigScratchBytes;
@@ -1425,13 +1425,13 @@ int index_build(loamx_ctx* ctx, loamx_target_index* idx, unsigned kinds = 3u) {
     idx->scratch_alloc = scratch_need;
   }
   B.sort_scratch = static_cast<GridPoint*>(idx->scratch);
-  B.grid_edge = GridSet{idx->desc[0], idx->cells[0], idx->sorted[0], idx->cap[0] + kGridPad, idx->rel[0], idx->cells_cap[0]};
-  B.grid_plane = GridSet{idx->desc[1], idx->cells[1], idx->sorted[1], idx->cap[1] + kGridPad, idx->rel[1], idx->cells_cap[1]};
+  for (int k = 0; k < 2; k++)
+    B.kind[k].grid = GridSet{idx->desc[k], idx->cells[k], idx->sorted[k], idx->cap[k] + kGridPad, idx->rel[k], idx->cells_cap[k]};
   untimed(ctx);
   {
     TimedScope t(ctx, LOAMX_K_GRID, 0.0);
     for (int k = 0; k < 2; k++)
-      if (kinds & (1u << k)) launch_grid_build_target(B, C, k == 1, s);
+      if (kinds & (1u << k)) launch_grid_build_target(B, C, k, s);
   }
   int rc = check_launch(ctx, "grid_build_kernel");
   if (rc != LOAMX_OK) return rc;
@@ -1571,7 +1571,7 @@ int loamx_target_index_create(loamx_ctx* ctx, const double* tgt_edge, size_t n_t
   int rc = make_reg_config(ctx, reg, C);
   if (rc != LOAMX_OK) return rc;
   loamx_target_index* idx = new loamx_target_index;
-  idx->radius[0] = C.r_edge, idx->radius[1] = C.r_plane;
+  idx->radius[kEdge] = C.kind[kEdge].r, idx->radius[kPlane] = C.kind[kPlane].r;
   bool ok = hipMalloc(reinterpret_cast<void**>(&idx->counts), 2 * sizeof(uint32_t)) == hipSuccess;
   for (int k = 0; k < 2 && ok; k++) ok = hipMalloc(reinterpret_cast<void**>(&idx->desc[k]), sizeof(GridDesc)) == hipSuccess;  // (tables: index_build)
   rc = ok ? index_append(ctx, idx, tgt_edge, n_te, tgt_planar, n_tp) : fail(ctx, LOAMX_ERR_HIP, "hipMalloc failed for the target index");
@@ -1647,15 +1647,16 @@ int loamx_register_features_batch_dev(loamx_ctx* ctx, size_t n_pairs, const doub
   RegConfig C;
   int rc = make_reg_config(ctx, reg, C);
   if (rc != LOAMX_OK) return rc;
-  RegInputs in{n_pairs, edge_stride, planar_stride, 1, d_src_edge, d_src_planar, d_tgt_edge, d_tgt_planar,
-               d_n_src_edge, d_n_src_planar, d_n_tgt_edge, d_n_tgt_planar, d_init};
+  RegInputs in{};
+  in.n_pairs = n_pairs, in.in_pitch = 1, in.init = d_init;
+  in.kind[kEdge] = RegInputs::Kind{edge_stride, d_src_edge, d_tgt_edge, d_n_src_edge, d_n_tgt_edge};
+  in.kind[kPlane] = RegInputs::Kind{planar_stride, d_src_planar, d_tgt_planar, d_n_src_planar, d_n_tgt_planar};
   if (ctx->reg_flags & kRegFlagCheckFinite) {
-    const struct { const double* p; const uint32_t* n; size_t stride; } sets[4] = {{d_src_edge, d_n_src_edge, edge_stride}, {d_src_planar, d_n_src_planar, planar_stride},
-                                                                                   {d_tgt_edge, d_n_tgt_edge, edge_stride}, {d_tgt_planar, d_n_tgt_planar, planar_stride}};
-    for (const auto& st : sets) {
-      rc = dev_check_finite(ctx, st.p, false, st.n, n_pairs, st.stride, 1);
-      if (rc != LOAMX_OK) return rc;
-    }
+    for (int role = 0; role < 2; role++)  // the source sets, then the target sets
+      for (const RegInputs::Kind& K : in.kind) {
+        rc = dev_check_finite(ctx, role ? K.tgt : K.src, false, role ? K.n_tgt : K.n_src, n_pairs, K.stride, 1);
+        if (rc != LOAMX_OK) return rc;
+      }
     if (d_init && n_pairs) {  // (7 doubles per pair, counted as scalars: the buffer need not end on a whole point)
       rc = finite_begin(ctx);
       if (rc != LOAMX_OK) return rc;
@@ -1693,24 +1694,24 @@ static int register_scan_pairs_locked(loamx_ctx* ctx, const void* d_xyz, bool f3
     rc = finite_end(ctx);
     if (rc != LOAMX_OK) return rc;
   }
-  ENSURE(ctx, WS_N_EDGE, n_scans * sizeof(uint32_t));
-  ENSURE(ctx, WS_N_PLANAR, n_scans * sizeof(uint32_t));
-  ENSURE(ctx, WS_EDGE_XYZ, n_scans * ecap * 3 * sizeof(double));
-  ENSURE(ctx, WS_PLANAR_XYZ, n_scans * pcap * 3 * sizeof(double));
+  const size_t cap[2] = {ecap, pcap};
+  for (int k = 0; k < 2; k++) ENSURE(ctx, ctx->wsk[WSK_N][k], n_scans * sizeof(uint32_t));
+  for (int k = 0; k < 2; k++) ENSURE(ctx, ctx->wsk[WSK_XYZ][k], n_scans * cap[k] * 3 * sizeof(double));
   ExtractBoxes boxes;
   // (no index arrays: the registration reads the features' points, and 4 bytes per feature are 0.15 GB per 1 024-pair step)
-  rc = extract_dev(ctx, d_xyz, f32, n_scans, P, nullptr, wsp<uint32_t>(ctx, WS_N_EDGE), wsp<double>(ctx, WS_EDGE_XYZ), nullptr,
-                   wsp<uint32_t>(ctx, WS_N_PLANAR), wsp<double>(ctx, WS_PLANAR_XYZ), false, &boxes);
+  rc = extract_dev(ctx, d_xyz, f32, n_scans, P, nullptr, wskp<uint32_t>(ctx, WSK_N, kEdge), wskp<double>(ctx, WSK_XYZ, kEdge), nullptr,
+                   wskp<uint32_t>(ctx, WSK_N, kPlane), wskp<double>(ctx, WSK_XYZ, kPlane), false, &boxes);
   if (rc != LOAMX_OK) return rc;
   // interleaved: scan 2p = target, scan 2p + 1 = source (in_pitch 2); sequence: scan p = target, scan p + 1 = source (in_pitch 1).
   // Either way a pair's source lies ONE scan behind its target: features, counts and boxes alike.
   RegInputs in{};
   in.boxes = boxes, in.src_box_offset = 1;
-  in.n_pairs = n_pairs, in.edge_stride = ecap, in.planar_stride = pcap, in.in_pitch = seq ? 1 : 2;
-  in.tgt_edge = wsp<double>(ctx, WS_EDGE_XYZ), in.src_edge = in.tgt_edge + ecap * 3;
-  in.tgt_planar = wsp<double>(ctx, WS_PLANAR_XYZ), in.src_planar = in.tgt_planar + pcap * 3;
-  in.n_tgt_edge = wsp<uint32_t>(ctx, WS_N_EDGE), in.n_src_edge = in.n_tgt_edge + 1;
-  in.n_tgt_planar = wsp<uint32_t>(ctx, WS_N_PLANAR), in.n_src_planar = in.n_tgt_planar + 1;
+  in.n_pairs = n_pairs, in.in_pitch = seq ? 1 : 2;
+  for (int k = 0; k < 2; k++) {
+    const double* xyz = wskp<double>(ctx, WSK_XYZ, k);
+    const uint32_t* count = wskp<uint32_t>(ctx, WSK_N, k);
+    in.kind[k] = RegInputs::Kind{cap[k], xyz + cap[k] * 3, xyz, count + 1, count};
+  }
   in.init = d_init;
   return register_dev(ctx, in, C, d_results, false, nullptr, nullptr);
 }

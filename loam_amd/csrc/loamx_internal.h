@@ -126,11 +126,16 @@ void launch_compact(const void* d_xyz, bool f32, size_t n_scans, const ExtractPa
                     hipStream_t s, const uint32_t* only_if = nullptr, unsigned long long* fallback_counter = nullptr);
 
 /* ---- registration (register_kernels.hip) ------------------------------------------------------- */
+constexpr int kEdge = 0, kPlane = 1;  // feature kinds, in the order of loamx_target_index, kAssocEdges / kAssocPlanes and n_assoc[8 * pair + ...]
+struct RegKindConfig {
+  // (members in the order at which the queue kernels keep their scalar-register spill counts: allocation follows the kernel argument's layout)
+  int k;        // neighbours searched
+  double r;     // search radius
+  int min_pts;  // fewest neighbours inside the radius a line / plane fit takes
+  double pass;  // knn_radius_pass_max(r): largest squared distance that passes the strict radius filter
+};
 struct RegConfig {
-  int k_edge, k_plane;
-  int min_line_pts, min_plane_pts;
-  double r_edge, r_plane;
-  double pass_edge, pass_plane;  // knn_radius_pass_max(r_*): largest squared distance that passes the strict radius filter
+  RegKindConfig kind[2];
   double min_line_cond, max_avg_plane_dist;
   uint32_t max_iterations;
   double rot_thresh, pos_thresh;
@@ -164,26 +169,30 @@ struct GridSet {
                          // cell table: a million-point map at the scan's cell edge puts hundreds of points in a cell
 };
 
-// Association records, structure-of-arrays over the whole batch (field-major) so the residual
+// What the registration holds once per feature kind (RegBatch::kind[kEdge], [kPlane]).
+// Association records: structure-of-arrays over the whole batch (field-major) so the residual
 // sweep streams each field with fully coalesced 8-byte loads.
-//   edges : 9 fields (moved point xyz, line a xyz, line b xyz) x n_pairs x edge_stride
-//   planes: 7 fields (moved point xyz, normal xyz, d)          x n_pairs x planar_stride
+//   edges : 9 fields (moved point xyz, line a xyz, line b xyz) x n_pairs x stride
+//   planes: 7 fields (moved point xyz, normal xyz, d)          x n_pairs x stride
 // An invalid slot has NaN in field 0.
-struct AssocBuffers {
-  double* edge;       // [9][n_pairs * edge_stride]
-  double* plane;      // [7][n_pairs * planar_stride]
-  uint32_t* nn_edge;        // [1 + kMaxK][n_pairs * edge_stride]   neighbour count, then positions in the sorted target
-  uint32_t* nn_plane;       // [1 + kMaxK][n_pairs * planar_stride]
-  uint32_t* rnn_edge;       // as nn_*, for the queued queries, indexed by queue position
-  uint32_t* rnn_plane;
-  uint32_t* nearest_edge;   // [n_pairs * edge_stride]   nearest target index (detail capture)
-  uint32_t* nearest_plane;  // [n_pairs * planar_stride]
-  uint32_t* rest_edge;      // [n_pairs * edge_stride]   queue of the queries round 1 of the k-NN did not finish
-  uint32_t* rest_plane;     // [n_pairs * planar_stride]
-  uint32_t* exact_edge;     // queues of the queries the keyed collector could not decide (exact collector re-runs them)
-  uint32_t* exact_plane;
-  uint32_t* n_assoc;  // [n_pairs][8]: valid edge / plane associations of the current iteration [0,1], lengths of the
-                      // queues rest_* [2,3] and exact_* [4,5]
+struct RegKind {
+  size_t stride;  // capacity (points) of one feature set; also the slot pitch of the association / grid arrays
+  // Input feature sets of pair p start at base + p * in_pitch * stride * 3 and their counts at n[p * in_pitch] (RegBatch::in_pitch)
+  const double* src;
+  const uint32_t* n_src;
+  const double* tgt;
+  const uint32_t* n_tgt;
+  GridSet grid;      // target sets: searched
+  GridSet src_grid;  // source sets: only their cell-sorted order is used (coherent queries)
+  uint32_t knn_mode;      // 0: grid and brute-force k-NN kernels both launched (target sizes on both sides of kBruteMax, or
+                          // unknown); 1: grid only; 2: brute force only
+  uint32_t assoc_blocks;  // workgroups per pair of the association kernels; 0xFFFFFFFF = by capacity
+  double* rec;        // [9 | 7][n_pairs * stride] association records
+  uint32_t* nn;       // [1 + kMaxK][n_pairs * stride] neighbour count, then positions in the sorted target
+  uint32_t* rnn;      // as nn, for the queued queries, indexed by queue position
+  uint32_t* nearest;  // [n_pairs * stride] nearest target index (detail capture)
+  uint32_t* rest;     // [n_pairs * stride] queue of the queries round 1 of the k-NN did not finish
+  uint32_t* exact;    // queue of the queries the keyed collector could not decide (exact collector re-runs them)
 };
 
 struct PairState {
@@ -210,24 +219,13 @@ constexpr int kSweepChunk = kSweepThreads * kSweepItems;
 
 struct RegBatch {
   size_t n_pairs;
-  size_t edge_stride, planar_stride;  // capacity (points) of one feature set; also the slot pitch of assoc/grid arrays
-  // Input feature sets of pair p start at base + p * in_pitch * stride * 3 and their counts at
-  // n[p * in_pitch]: in_pitch = 1 for separate arrays, 2 when source and target scans are interleaved.
-  uint32_t in_pitch;
-  const double* src_edge;
-  const uint32_t* n_src_edge;
-  const double* src_planar;
-  const uint32_t* n_src_planar;
-  const double* tgt_edge;
-  const uint32_t* n_tgt_edge;
-  const double* tgt_planar;
-  const uint32_t* n_tgt_planar;
+  uint32_t in_pitch;  // 1 for separate input arrays, 2 when source and target scans are interleaved (RegKind::src)
+  RegKind kind[2];
   const double* init;  // may be null
-  GridSet grid_edge, grid_plane;          // target sets: searched
-  GridSet src_grid_edge, src_grid_plane;  // source sets: only their cell-sorted order is used (coherent queries)
-  GridPoint* sort_scratch;      // [n_pairs][max(edge_stride, planar_stride)] scratch of the multi-workgroup target builds
+  GridPoint* sort_scratch;      // [n_pairs][largest stride] scratch of the multi-workgroup target builds
   GridPoint* sort_scratch_src;  // the same for the ordered source builds (they run next to the target builds on another stream)
-  AssocBuffers assoc;
+  uint32_t* n_assoc;  // [n_pairs][8]: valid edge / plane associations of the current iteration [0,1], lengths of the
+                      // queues rest [2,3] and exact [4,5]
   PairState* state;      // [n_pairs]
   double* partials;      // [n_pairs][blocks_per_pair][kAccSize]
   double* mom_partials;  // [n_pairs][mom_blocks_per_pair][4][kMomSize + 2] wavefront tiles of the moment pass
@@ -244,10 +242,7 @@ struct RegBatch {
   loamx_iter_info* iter_info;  // optional [n_pairs][max_iterations]
   uint32_t* max_counts;   // [6] over the active pairs (state_init_kernel; read back by the host): largest source edge / planar
                           // count, largest target edge / planar count, smallest target edge / planar count
-  uint32_t knn_mode_edge, knn_mode_plane;  // 0: grid and brute-force k-NN kernels both launched (target sizes on both
-                                           // sides of kBruteMax, or unknown); 1: grid only; 2: brute force only
-  uint32_t assoc_blocks_edge, assoc_blocks_plane;  // workgroups per pair of the association kernels; 0xFFFFFFFF = by capacity
-  uint32_t want_nearest;  // 1: a detail hook will read nearest_* (RegistrationDetail pairs); 0: the fit kernels skip that write
+  uint32_t want_nearest;  // 1: a detail hook will read RegKind::nearest (RegistrationDetail pairs); 0: the fit kernels skip that write
   uint32_t ref_moments;   // 1: the first ICF iteration takes its moments at its first candidate after ONE sweep (enqueue_icf_iteration)
   // optional: bounding boxes of the input feature sets, computed by the extraction that produced them (ExtractFused::box_*):
   // [scan][kind][axis] keys, scan = pair * in_pitch (+ src_box_offset for the pair's source scan). Used by the index builds
@@ -275,8 +270,8 @@ constexpr uint32_t kGridMapCellsCap = 1u << 18;
 inline bool grid_small(size_t stride, uint32_t reg_flags) { return stride <= kGridSmallCap && !(reg_flags & kRegFlagNoPackedGrid); }
 void launch_grid_build_targets(const RegBatch& B, const RegConfig& C, hipStream_t s);
 void launch_grid_build_sources(const RegBatch& B, const RegConfig& C, hipStream_t s);
-void launch_grid_build_target(const RegBatch& B, const RegConfig& C, bool plane, hipStream_t s);  // one feature kind
-void launch_grid_build_source(const RegBatch& B, const RegConfig& C, bool plane, hipStream_t s);
+void launch_grid_build_target(const RegBatch& B, const RegConfig& C, int kind, hipStream_t s);  // one feature kind
+void launch_grid_build_source(const RegBatch& B, const RegConfig& C, int kind, hipStream_t s);
 void launch_state_init(const RegBatch& B, const RegConfig& C, hipStream_t s);
 // aux == nullptr: everything on s; aux2 == nullptr: the plane queue chain follows the edge chain on aux
 // knn_scope != nullptr: the plane round-1 k-NN kernel is launched with that timing scope attached
@@ -313,7 +308,7 @@ struct AssocDumpSet {  // device arrays of one feature kind, indexed by the call
 void launch_fit_sets(bool plane, const double* d_pts, size_t n_sets, int k, double* d_prim, double* d_aux, hipStream_t s);
 void launch_knn_queries(const GridSet& gs, const double* d_q, size_t n_q, int k, double max_dist, uint32_t* d_idx, uint32_t* d_count,
                         hipStream_t s);
-void launch_assoc_dump(const RegBatch& B, const RegConfig& C, const AssocDumpSet& edge, const AssocDumpSet& plane, hipStream_t s);
+void launch_assoc_dump(const RegBatch& B, const RegConfig& C, const AssocDumpSet (&out)[2], hipStream_t s);
 
 /* ---- non-finite input check of the "_dev" entry points (context option CHECK_FINITE; synth_kernels.hip) --------- */
 // sets of `stride` points, `pitch` sets apart; d_n: points held by set i at d_n[i * pitch], or nullptr = all `stride`

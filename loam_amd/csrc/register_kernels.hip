@@ -715,14 +715,15 @@ __global__ void state_init_kernel(RegBatch B, RegConfig C) {
   S.use_moments = 0;
   S.mom_ref_on = 0;
   S.lm.active = 0;
-  for (int c = 0; c < 6; c++) B.assoc.n_assoc[8 * pair + c] = 0;
+  for (int c = 0; c < 6; c++) B.n_assoc[8 * pair + c] = 0;
   if (B.max_counts) {  // the host sizes the association grids by the largest set instead of by the capacity
-    const uint32_t ne = B.n_src_edge[pair * B.in_pitch], np = B.n_src_planar[pair * B.in_pitch];
-    atomicMax(&B.max_counts[0], ne < B.edge_stride ? ne : (uint32_t)B.edge_stride);
-    atomicMax(&B.max_counts[1], np < B.planar_stride ? np : (uint32_t)B.planar_stride);
-    if (B.n_tgt_edge && B.n_tgt_planar) {  // (a persistent index has its sizes on the host)
-      uint32_t te = B.n_tgt_edge[pair * B.in_pitch], tp = B.n_tgt_planar[pair * B.in_pitch];
-      te = te < B.edge_stride ? te : (uint32_t)B.edge_stride, tp = tp < B.planar_stride ? tp : (uint32_t)B.planar_stride;
+    const RegKind &E = B.kind[kEdge], &P = B.kind[kPlane];
+    const uint32_t ne = E.n_src[pair * B.in_pitch], np = P.n_src[pair * B.in_pitch];
+    atomicMax(&B.max_counts[0], ne < E.stride ? ne : (uint32_t)E.stride);
+    atomicMax(&B.max_counts[1], np < P.stride ? np : (uint32_t)P.stride);
+    if (E.n_tgt && P.n_tgt) {  // (a persistent index has its sizes on the host)
+      uint32_t te = E.n_tgt[pair * B.in_pitch], tp = P.n_tgt[pair * B.in_pitch];
+      te = te < E.stride ? te : (uint32_t)E.stride, tp = tp < P.stride ? tp : (uint32_t)P.stride;
       atomicMax(&B.max_counts[2], te), atomicMax(&B.max_counts[3], tp);
       atomicMin(&B.max_counts[4], te), atomicMin(&B.max_counts[5], tp);
     }
@@ -792,32 +793,34 @@ __device__ __forceinline__ void knn_brute_body(const RegBatch& B, const RegConfi
   if (!xcd_pair_map(block, blocks_per_pair, B.n_pairs, pair, chunk)) return;
   const PairState& S = B.state[pair];
   if (!S.active) return;  // uniform per workgroup
-  const GridSet& gs = PLANE ? B.grid_plane : B.grid_edge;
+  const RegKind& K = B.kind[PLANE];
+  const RegKindConfig& CK = C.kind[PLANE];
+  const GridSet& gs = K.grid;
   const uint32_t n_tgt = gs.desc[pair].n_points;
   if (n_tgt > kBruteMax) return;  // uniform: the grid kernels take this pair
-  const size_t stride = PLANE ? B.planar_stride : B.edge_stride;
-  const uint32_t n_src = PLANE ? B.n_src_planar[pair * B.in_pitch] : B.n_src_edge[pair * B.in_pitch];
-  if ((PLANE ? B.knn_mode_plane : B.knn_mode_edge) == 2u && chunk == 0 && threadIdx.x == 0 && B.assoc_slots)  // (the grid kernel was not launched)
+  const size_t stride = K.stride;
+  const uint32_t n_src = K.n_src[pair * B.in_pitch];
+  if (K.knn_mode == 2u && chunk == 0 && threadIdx.x == 0 && B.assoc_slots)  // (the grid kernel was not launched)
     atomicAdd(&B.assoc_slots[PLANE ? 1 : 0], (unsigned long long)(n_src < stride ? n_src : stride));
   if (chunk * kAssocThreads >= n_src || chunk * kAssocThreads >= stride) return;  // uniform: no query here
   const uint32_t i = chunk * kAssocThreads + threadIdx.x;
   const bool has = i < n_src && i < stride;
-  const GridSet& src_gs = PLANE ? B.src_grid_plane : B.src_grid_edge;
+  const GridSet& src_gs = K.src_grid;
   const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
   Vec3 p = v3(0, 0, 0);
   if (has) {
     const GridPoint sq = src_gs.sorted[pair * src_gs.stride + i];
     p = pose_act(S.est, v3(sq.x, sq.y, sq.z));  // registration.cpp:34 / :75
   }
-  int k = PLANE ? C.k_plane : C.k_edge;
+  int k = CK.k;
   k = k < KM ? k : KM;
-  const double max_dist = PLANE ? C.r_plane : C.r_edge;
+  const double max_dist = CK.r;
   uint32_t pos[KM];
 #pragma unroll
   for (int j = 0; j < KM; j++) pos[j] = 0;
   int kept = 0;
   if (k > 0 && n_tgt > 0) {
-    const double pass_max = PLANE ? C.pass_plane : C.pass_edge;
+    const double pass_max = CK.pass;
     // ---- FP32 pre-selection, as in the grid kernel: 32-bit keys (float bits of d2, the low 9 bits = the candidate's
     // position: the set has at most 512 points) through the v_med3_u32 collector, 10 instructions per candidate instead
     // of 25; then the k selected are fetched in FP64 and the usual three checks (strictly ascending exact distances, best
@@ -914,7 +917,7 @@ __device__ __forceinline__ void knn_brute_body(const RegBatch& B, const RegConfi
   }
   if (!has) return;
   const size_t field = B.n_pairs * stride, slot = pair * stride + i;
-  uint32_t* __restrict__ nn = PLANE ? B.assoc.nn_plane : B.assoc.nn_edge;
+  uint32_t* __restrict__ nn = K.nn;
   nn[slot] = (uint32_t)kept;
 #pragma unroll
   for (int j = 0; j < KM; j++) nn[(1 + j) * field + slot] = pos[j];
@@ -942,10 +945,11 @@ __device__ __forceinline__ void knn_round1_body(const RegBatch& B, const RegConf
   const uint32_t i = chunk * kAssocThreads + threadIdx.x;
   const PairState& S = B.state[pair];
   if (!S.active) return;  // uniform per workgroup
-  const size_t stride = PLANE ? B.planar_stride : B.edge_stride;
-  const uint32_t n_src = PLANE ? B.n_src_planar[pair * B.in_pitch] : B.n_src_edge[pair * B.in_pitch];
-  const GridSet& gs = PLANE ? B.grid_plane : B.grid_edge;
-  const GridSet& src_gs = PLANE ? B.src_grid_plane : B.src_grid_edge;
+  const RegKind& K = B.kind[PLANE];
+  const RegKindConfig& CK = C.kind[PLANE];
+  const size_t stride = K.stride;
+  const uint32_t n_src = K.n_src[pair * B.in_pitch];
+  const GridSet &gs = K.grid, &src_gs = K.src_grid;
   if (chunk == 0 && threadIdx.x == 0 && B.assoc_slots)
     atomicAdd(&B.assoc_slots[PLANE ? 1 : 0], (unsigned long long)(n_src < stride ? n_src : stride));
   const GridDesc g = gs.desc[pair];
@@ -970,22 +974,20 @@ __device__ __forceinline__ void knn_round1_body(const RegBatch& B, const RegConf
     const GridPoint s2 = src_pts[ii];
     return pose_act(S.est, v3(s2.x, s2.y, s2.z));
   };
-  const int kept = knn_search_f32_round1<KM, false, decltype(requery)>(g, cs, sp, rel, (uint32_t)gs.stride, p, PLANE ? C.k_plane : C.k_edge,
-                                             PLANE ? C.r_plane : C.r_edge, PLANE ? C.pass_plane : C.pass_edge, pos,
-                                             s_rows + threadIdx.x, kAssocThreads, requery);
+  const int kept = knn_search_f32_round1<KM, false, decltype(requery)>(g, cs, sp, rel, (uint32_t)gs.stride, p, CK.k,
+                                             CK.r, CK.pass, pos, s_rows + threadIdx.x, kAssocThreads, requery);
 #else
-  const int kept = knn_search_f32_round1<KM>(g, cs, sp, rel, (uint32_t)gs.stride, p, PLANE ? C.k_plane : C.k_edge,
-                                             PLANE ? C.r_plane : C.r_edge, PLANE ? C.pass_plane : C.pass_edge, pos,
+  const int kept = knn_search_f32_round1<KM>(g, cs, sp, rel, (uint32_t)gs.stride, p, CK.k, CK.r, CK.pass, pos,
                                              s_rows + threadIdx.x, kAssocThreads);
 #endif
   const size_t field = B.n_pairs * stride, slot = pair * stride + i;
-  uint32_t* __restrict__ nn = PLANE ? B.assoc.nn_plane : B.assoc.nn_edge;  // [1 + KM][n_pairs * stride]
+  uint32_t* __restrict__ nn = K.nn;  // [1 + KM][n_pairs * stride]
   nn[slot] = kept < 0 ? 0xFFFFFFFFu : (uint32_t)kept;
   if (kept < 0) {  // not finished by round 1: queued for associate_knn_rest_kernel
-    const uint32_t at = atomicAdd(&B.assoc.n_assoc[8 * pair + (PLANE ? 3 : 2)], 1u);
+    const uint32_t at = atomicAdd(&B.n_assoc[8 * pair + (PLANE ? 3 : 2)], 1u);
     // (bit 31: the query only ran out of 8-bit running numbers — a dense block: the queue kernel retries the FP32
     // pre-selection with wide numbers; bit 30: its FP32 keys were tied — an ordinary neighbourhood the FP64 keys decide)
-    (PLANE ? B.assoc.rest_plane : B.assoc.rest_edge)[pair * stride + at] = i | (kept == -2 ? kQueueWide : kept == -3 ? kQueueTied : 0u);
+    K.rest[pair * stride + at] = i | (kept == -2 ? kQueueWide : kept == -3 ? kQueueTied : 0u);
   }
 #pragma unroll
   for (int j = 0; j < KM; j++) nn[(1 + j) * field + slot] = pos[j];  // neighbour j is slot (KM - k) + j
@@ -1029,17 +1031,16 @@ constexpr int kRestThreads = LOAMX_REST_THREADS;  // small workgroups: the queue
 // The listed leftovers of a queue: one WAVEFRONT per entry (associate_knn_coop_kernel) or one lane per entry
 // (associate_knn_left_kernel)? The cooperative search walks shells up to the one the radius closes; without a radius it falls
 // back to lane 0 alone, 63 lanes idle — such searches take the one-lane kernel's dense packing instead.
-__host__ __device__ inline bool queue_leftovers_coop(const RegConfig& C, bool plane) {
-  return !(C.flags & kRegFlagNoCoopLeft) && (plane ? C.r_plane : C.r_edge) > 0.0;
+__host__ __device__ inline bool queue_leftovers_coop(const RegConfig& C, int kind) {
+  return !(C.flags & kRegFlagNoCoopLeft) && C.kind[kind].r > 0.0;
 }
 #ifndef LOAMX_COOP_WAVES
 #define LOAMX_COOP_WAVES 4
 #endif
-#ifndef LOAMX_REST_WAVES
 // (round 2 measured 4 -> 2.12 ms, 5 -> 2.11, 6 -> 2.14 of association scope on the one-stage form; since the two-stage chain every
 // instance settles at 3 wavefronts per SIMD (k <= 8) or 2 (k = 16) whatever is asked: the attribute now says what the compiler does)
 #define LOAMX_REST_WAVES(KM) ((KM) <= 8 ? 3 : 2)
-#endif
+constexpr int kLeftWaves = 5;  // associate_knn_left_kernel: long walks on few wavefronts, next to the plane fit kernel
 template <bool PLANE, int KM, bool ONE_STAGE>
 __global__ __launch_bounds__(kRestThreads, LOAMX_REST_WAVES(KM)) void associate_knn_rest_kernel(RegBatch B, RegConfig C,
                                                                                               uint32_t blocks_per_pair) {
@@ -1049,16 +1050,17 @@ __global__ __launch_bounds__(kRestThreads, LOAMX_REST_WAVES(KM)) void associate_
   if (!xcd_pair_map(blockIdx.x, blocks_per_pair, B.n_pairs, pair, chunk0)) return;
   const PairState& S = B.state[pair];
   if (!S.active) return;                                              // uniform per workgroup
-  const uint32_t queued = B.assoc.n_assoc[8 * pair + (PLANE ? 3 : 2)];
+  const uint32_t queued = B.n_assoc[8 * pair + (PLANE ? 3 : 2)];
   if (queued == 0u) return;                                           // uniform per workgroup
   __shared__ uint32_t s_rows[(ONE_STAGE ? kLeanRowWords : kLean2RowWords) * kRestThreads];  // (the largest per-thread row list used below)
-  const size_t stride = PLANE ? B.planar_stride : B.edge_stride;
+  const RegKind& K = B.kind[PLANE];
+  const RegKindConfig& CK = C.kind[PLANE];
+  const size_t stride = K.stride;
   const size_t field = B.n_pairs * stride;
-  uint32_t* __restrict__ rnn = PLANE ? B.assoc.rnn_plane : B.assoc.rnn_edge;  // results by queue position
-  const uint32_t* __restrict__ rest = (PLANE ? B.assoc.rest_plane : B.assoc.rest_edge) + pair * stride;
-  uint32_t* __restrict__ left = (PLANE ? B.assoc.exact_plane : B.assoc.exact_edge) + pair * stride;
-  const GridSet& gs = PLANE ? B.grid_plane : B.grid_edge;
-  const GridSet& src_gs = PLANE ? B.src_grid_plane : B.src_grid_edge;
+  uint32_t* __restrict__ rnn = K.rnn;  // results by queue position
+  const uint32_t* __restrict__ rest = K.rest + pair * stride;
+  uint32_t* __restrict__ left = K.exact + pair * stride;
+  const GridSet &gs = K.grid, &src_gs = K.src_grid;
   const GridDesc g = gs.desc[pair];
   const uint32_t* __restrict__ cs = gs.cell_start + pair * (size_t)(kGridCellsCap + 1);
   const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
@@ -1070,8 +1072,8 @@ __global__ __launch_bounds__(kRestThreads, LOAMX_REST_WAVES(KM)) void associate_
   const uint32_t t0 = spread ? chunk0 + blocks_per_pair * threadIdx.x : chunk0 * kRestThreads + threadIdx.x;
   const uint32_t dt = spread ? 0xFFFFFFFFu - t0 : blocks_per_pair * kRestThreads;  // (spread: one entry per lane)
   const bool lean_set = g.n_points <= kLeanMaxPoints;  // (uniform: a property of the set; positions travel as 16-bit halves)
-  const int kq = PLANE ? C.k_plane : C.k_edge;
-  const double max_dist = PLANE ? C.r_plane : C.r_edge, pass_max = PLANE ? C.pass_plane : C.pass_edge;
+  const int kq = CK.k;
+  const double max_dist = CK.r, pass_max = CK.pass;
   for (uint32_t t = t0; t < queued; t += dt) {
     const uint32_t entry = rest[t], i = entry & kQueueIndex;
     const size_t slot = pair * stride + t;  // (queue position, not query index)
@@ -1094,7 +1096,7 @@ __global__ __launch_bounds__(kRestThreads, LOAMX_REST_WAVES(KM)) void associate_
         kept = knn_search_keyed<KM>(g, cs, sp, p, kq, max_dist, pass_max, pos, s_rows + threadIdx.x, kRestThreads);
     }
     rnn[slot] = (uint32_t)kept;
-    if (kept < 0) left[atomicAdd(&B.assoc.n_assoc[8 * pair + (PLANE ? 5 : 4)], 1u)] = t;  // (one stage: counted only)
+    if (kept < 0) left[atomicAdd(&B.n_assoc[8 * pair + (PLANE ? 5 : 4)], 1u)] = t;  // (one stage: counted only)
 #pragma unroll
     for (int j = 0; j < KM; j++) rnn[(1 + j) * field + slot] = pos[j];
   }
@@ -1103,23 +1105,24 @@ __global__ __launch_bounds__(kRestThreads, LOAMX_REST_WAVES(KM)) void associate_
 // The listed queue entries (see above): the FP64 keyed collector — each candidate ONE double, the bits of d2 with the
 // low mantissa bits replaced by the position — over all rounds. What its keys cannot decide keeps its negative count.
 template <bool PLANE, int KM>
-__global__ __launch_bounds__(kRestThreads, 5) void associate_knn_left_kernel(RegBatch B, RegConfig C,
+__global__ __launch_bounds__(kRestThreads, kLeftWaves) void associate_knn_left_kernel(RegBatch B, RegConfig C,
                                                                                               uint32_t blocks_per_pair) {
   size_t pair;
   uint32_t chunk0;
   if (!xcd_pair_map(blockIdx.x, blocks_per_pair, B.n_pairs, pair, chunk0)) return;
   const PairState& S = B.state[pair];
   if (!S.active) return;                                              // uniform per workgroup
-  const uint32_t listed = B.assoc.n_assoc[8 * pair + (PLANE ? 5 : 4)];
+  const uint32_t listed = B.n_assoc[8 * pair + (PLANE ? 5 : 4)];
   if (listed == 0u) return;                                           // uniform per workgroup
   __shared__ uint32_t s_rows[kLeanRowWords * kRestThreads];
-  const size_t stride = PLANE ? B.planar_stride : B.edge_stride;
+  const RegKind& K = B.kind[PLANE];
+  const RegKindConfig& CK = C.kind[PLANE];
+  const size_t stride = K.stride;
   const size_t field = B.n_pairs * stride;
-  uint32_t* __restrict__ rnn = PLANE ? B.assoc.rnn_plane : B.assoc.rnn_edge;
-  const uint32_t* __restrict__ rest = (PLANE ? B.assoc.rest_plane : B.assoc.rest_edge) + pair * stride;
-  const uint32_t* __restrict__ left = (PLANE ? B.assoc.exact_plane : B.assoc.exact_edge) + pair * stride;
-  const GridSet& gs = PLANE ? B.grid_plane : B.grid_edge;
-  const GridSet& src_gs = PLANE ? B.src_grid_plane : B.src_grid_edge;
+  uint32_t* __restrict__ rnn = K.rnn;
+  const uint32_t* __restrict__ rest = K.rest + pair * stride;
+  const uint32_t* __restrict__ left = K.exact + pair * stride;
+  const GridSet &gs = K.grid, &src_gs = K.src_grid;
   const GridDesc g = gs.desc[pair];
   const uint32_t* __restrict__ cs = gs.cell_start + pair * (size_t)(kGridCellsCap + 1);
   const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
@@ -1132,8 +1135,7 @@ __global__ __launch_bounds__(kRestThreads, 5) void associate_knn_left_kernel(Reg
     const GridPoint sq = src_gs.sorted[pair * src_gs.stride + i];
     const Vec3 p = pose_act(S.est, v3(sq.x, sq.y, sq.z));
     uint32_t pos[KM];
-    const int kept = knn_search_keyed<KM>(g, cs, sp, p, PLANE ? C.k_plane : C.k_edge, PLANE ? C.r_plane : C.r_edge,
-                                          PLANE ? C.pass_plane : C.pass_edge, pos, s_rows + threadIdx.x, kRestThreads);
+    const int kept = knn_search_keyed<KM>(g, cs, sp, p, CK.k, CK.r, CK.pass, pos, s_rows + threadIdx.x, kRestThreads);
     rnn[slot] = (uint32_t)kept;
 #pragma unroll
     for (int j = 0; j < KM; j++) rnn[(1 + j) * field + slot] = pos[j];
@@ -1351,21 +1353,22 @@ __global__ __launch_bounds__(kRestThreads, LOAMX_COOP_WAVES) void associate_knn_
   if (!xcd_pair_map(blockIdx.x, blocks_per_pair, B.n_pairs, pair, chunk0)) return;
   const PairState& S = B.state[pair];
   if (!S.active) return;                                              // uniform per workgroup
-  const uint32_t listed = B.assoc.n_assoc[8 * pair + (PLANE ? 5 : 4)];
+  const uint32_t listed = B.n_assoc[8 * pair + (PLANE ? 5 : 4)];
   if (listed == 0u) return;                                           // uniform per workgroup
   __shared__ uint32_t s_rows[kLeanRowWords];
-  const size_t stride = PLANE ? B.planar_stride : B.edge_stride;
+  const RegKind& K = B.kind[PLANE];
+  const RegKindConfig& CK = C.kind[PLANE];
+  const size_t stride = K.stride;
   const size_t field = B.n_pairs * stride;
-  uint32_t* __restrict__ rnn = PLANE ? B.assoc.rnn_plane : B.assoc.rnn_edge;
-  const uint32_t* __restrict__ rest = (PLANE ? B.assoc.rest_plane : B.assoc.rest_edge) + pair * stride;
-  const uint32_t* __restrict__ left = (PLANE ? B.assoc.exact_plane : B.assoc.exact_edge) + pair * stride;
-  const GridSet& gs = PLANE ? B.grid_plane : B.grid_edge;
-  const GridSet& src_gs = PLANE ? B.src_grid_plane : B.src_grid_edge;
+  uint32_t* __restrict__ rnn = K.rnn;
+  const uint32_t* __restrict__ rest = K.rest + pair * stride;
+  const uint32_t* __restrict__ left = K.exact + pair * stride;
+  const GridSet &gs = K.grid, &src_gs = K.src_grid;
   const GridDesc g = gs.desc[pair];
   const uint32_t* __restrict__ cs = gs.cell_start + pair * (size_t)(kGridCellsCap + 1);
   const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
-  const int kq = PLANE ? C.k_plane : C.k_edge;
-  const double max_dist = PLANE ? C.r_plane : C.r_edge, pass_max = PLANE ? C.pass_plane : C.pass_edge;
+  const int kq = CK.k;
+  const double max_dist = CK.r, pass_max = CK.pass;
   for (uint32_t t = chunk0; t < listed; t += blocks_per_pair) {  // (wave-uniform: one entry per wavefront and turn)
     const uint32_t qpos = left[t], i = rest[qpos] & kQueueIndex;
     const size_t slot = pair * stride + qpos;
@@ -1395,19 +1398,20 @@ __global__ __launch_bounds__(kRestThreads, LOAMX_COOP_WAVES) void associate_knn_
 template <bool PLANE, int KM>
 __device__ __forceinline__ void knn_exact_one(const RegBatch& B, const RegConfig& C, const PairState& S, size_t pair, uint32_t i,
                                               size_t slot, uint32_t* rnn, uint32_t* s_rows, int rows_stride) {
-  const size_t stride = PLANE ? B.planar_stride : B.edge_stride;
+  const RegKind& K = B.kind[PLANE];
+  const RegKindConfig& CK = C.kind[PLANE];
+  const size_t stride = K.stride;
   const size_t field = B.n_pairs * stride;
-  const GridSet& gs = PLANE ? B.grid_plane : B.grid_edge;
-  const GridSet& src_gs = PLANE ? B.src_grid_plane : B.src_grid_edge;
+  const GridSet &gs = K.grid, &src_gs = K.src_grid;
   const GridDesc g = gs.desc[pair];
   const uint32_t* __restrict__ cs = gs.cell_start + pair * (size_t)(kGridCellsCap + 1);
   const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
-  int k = PLANE ? C.k_plane : C.k_edge;
+  int k = CK.k;
   k = k < KM ? k : KM;
   const GridPoint sq = src_gs.sorted[pair * src_gs.stride + i];
   const Vec3 p = pose_act(S.est, v3(sq.x, sq.y, sq.z));
   KnnResult<KM> r;
-  const int kept = knn_search(g, cs, sp, p, k, PLANE ? C.r_plane : C.r_edge, r, s_rows, rows_stride);
+  const int kept = knn_search(g, cs, sp, p, k, CK.r, r, s_rows, rows_stride);
   uint32_t pos[KM];
   knn_shift_positions<KM>(r.pos, k, pos);  // neighbour j is slot (KM - k) + j
   rnn[slot] = (uint32_t)kept;
@@ -1420,15 +1424,16 @@ __device__ __forceinline__ void knn_exact_one(const RegBatch& B, const RegConfig
 template <bool PLANE, int KM, bool QUEUED = false>
 __device__ __forceinline__ bool fit_one(const RegBatch& B, const RegConfig& C, const PairState& S, size_t pair, uint32_t i,
                                         const uint32_t* __restrict__ nnsrc, size_t nidx) {
-  const size_t stride = PLANE ? B.planar_stride : B.edge_stride;
-  const GridSet& gs = PLANE ? B.grid_plane : B.grid_edge;
-  const GridSet& src_gs = PLANE ? B.src_grid_plane : B.src_grid_edge;
+  const RegKind& K = B.kind[PLANE];
+  const RegKindConfig& CK = C.kind[PLANE];
+  const size_t stride = K.stride;
+  const GridSet &gs = K.grid, &src_gs = K.src_grid;
   const GridPoint sq = src_gs.sorted[pair * src_gs.stride + i];
   const Vec3 p = pose_act(S.est, v3(sq.x, sq.y, sq.z));
   const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
   const size_t field = B.n_pairs * stride, slot = pair * stride + i;
   const int kept = (int)nnsrc[nidx];
-  const int kq = PLANE ? C.k_plane : C.k_edge;
+  const int kq = CK.k;
   const int shift = KM - (kq < KM ? kq : KM);  // neighbour j is slot shift + j (knn_search_positions)
   double prim[6] = {0, 0, 0, 0, 0, 0};
   uint32_t nearest = 0xFFFFFFFFu;
@@ -1443,7 +1448,7 @@ __device__ __forceinline__ bool fit_one(const RegBatch& B, const RegConfig& C, c
   GridPoint tp[KM];
 #pragma unroll
   for (int j = 0; j < KM; j++) tp[j] = sp[at[j] < (uint32_t)gs.stride ? at[j] : 0u];
-  if (kept >= (PLANE ? C.min_plane_pts : C.min_line_pts)) {  // registration.cpp:39 / :80
+  if (kept >= CK.min_pts) {  // registration.cpp:39 / :80
     Vec3 nb[KM];
 #pragma unroll
     for (int j = 0; j < KM; j++) nb[j] = j < kept ? v3(tp[j].x, tp[j].y, tp[j].z) : v3(0, 0, 0);
@@ -1461,14 +1466,14 @@ __device__ __forceinline__ bool fit_one(const RegBatch& B, const RegConfig& C, c
       prim[0] = a.x, prim[1] = a.y, prim[2] = a.z, prim[3] = b.x, prim[4] = b.y, prim[5] = b.z;
     }
   }
-  double* __restrict__ rec = PLANE ? B.assoc.plane : B.assoc.edge;
+  double* __restrict__ rec = K.rec;
   rec[slot] = valid ? p.x : __longlong_as_double(0x7FF8000000000000ll);
   rec[field + slot] = p.y;
   rec[2 * field + slot] = p.z;
 #pragma unroll
   for (int f = 0; f < (PLANE ? 4 : 6); f++) rec[(3 + f) * field + slot] = prim[f];
   // detail capture is indexed by the caller's source index
-  if (B.want_nearest) (PLANE ? B.assoc.nearest_plane : B.assoc.nearest_edge)[pair * stride + sq.orig] = valid ? nearest : 0xFFFFFFFFu;
+  if (B.want_nearest) K.nearest[pair * stride + sq.orig] = valid ? nearest : 0xFFFFFFFFu;
   return valid;
 }
 
@@ -1484,14 +1489,15 @@ __device__ __forceinline__ void fit_body(const RegBatch& B, const RegConfig& C, 
   const uint32_t i = chunk * kAssocThreads + threadIdx.x;
   const PairState& S = B.state[pair];
   if (!S.active) return;  // uniform per workgroup
-  const size_t stride = PLANE ? B.planar_stride : B.edge_stride;
-  const uint32_t n_src = PLANE ? B.n_src_planar[pair * B.in_pitch] : B.n_src_edge[pair * B.in_pitch];
-  const uint32_t* __restrict__ nn = PLANE ? B.assoc.nn_plane : B.assoc.nn_edge;
+  const RegKind& K = B.kind[PLANE];
+  const size_t stride = K.stride;
+  const uint32_t n_src = K.n_src[pair * B.in_pitch];
+  const uint32_t* __restrict__ nn = K.nn;
   bool valid = false;
   if (i < n_src && i < stride) valid = fit_one<PLANE, KM>(B, C, S, pair, i, nn, pair * stride + i);  // (queued queries: skipped inside)
   // (one atomic per wavefront, no barrier: a wavefront that is done leaves)
   const unsigned long long m = __ballot(valid);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&B.assoc.n_assoc[8 * pair + (PLANE ? 1 : 0)], (uint32_t)__popcll(m));
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&B.n_assoc[8 * pair + (PLANE ? 1 : 0)], (uint32_t)__popcll(m));
 }
 template <bool PLANE, int KM>
 __global__ __launch_bounds__(kAssocThreads, LOAMX_FIT_WAVES) void associate_fit_kernel(RegBatch B, RegConfig C,
@@ -1514,12 +1520,13 @@ __global__ __launch_bounds__(kRestThreads, 3) void associate_fit_queued_kernel(R
   if (!xcd_pair_map(blockIdx.x, blocks_per_pair, B.n_pairs, pair, chunk0)) return;
   const PairState& S = B.state[pair];
   if (!S.active) return;                                              // uniform per workgroup
-  const uint32_t queued = B.assoc.n_assoc[8 * pair + (PLANE ? 3 : 2)];
+  const uint32_t queued = B.n_assoc[8 * pair + (PLANE ? 3 : 2)];
   if (queued == 0u) return;                                           // uniform per workgroup
   __shared__ uint32_t s_rows[18 * kRestThreads];
-  const size_t stride = PLANE ? B.planar_stride : B.edge_stride;
-  uint32_t* rnn = PLANE ? B.assoc.rnn_plane : B.assoc.rnn_edge;  // (written and read back here: no __restrict__)
-  const uint32_t* __restrict__ rest = (PLANE ? B.assoc.rest_plane : B.assoc.rest_edge) + pair * stride;
+  const RegKind& K = B.kind[PLANE];
+  const size_t stride = K.stride;
+  uint32_t* rnn = K.rnn;  // (written and read back here: no __restrict__)
+  const uint32_t* __restrict__ rest = K.rest + pair * stride;
   uint32_t count = 0;
   for (uint32_t t = chunk0 * kRestThreads + threadIdx.x; t < queued; t += blocks_per_pair * kRestThreads) {
     const uint32_t i = rest[t] & kQueueIndex;
@@ -1529,7 +1536,7 @@ __global__ __launch_bounds__(kRestThreads, 3) void associate_fit_queued_kernel(R
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) count += __shfl_xor(count, off);
-  if ((threadIdx.x & 63) == 0 && count) atomicAdd(&B.assoc.n_assoc[8 * pair + (PLANE ? 1 : 0)], count);
+  if ((threadIdx.x & 63) == 0 && count) atomicAdd(&B.n_assoc[8 * pair + (PLANE ? 1 : 0)], count);
 }
 
 // (the ICF iteration number of an active pair is S.iterations, the iterations it has completed: no kernel argument
@@ -1541,8 +1548,8 @@ __global__ __launch_bounds__(64) void lm_begin_kernel(RegBatch B, RegConfig C) {
   PairState& S = B.state[pair];
   if (!S.active) return;
   const uint32_t iteration = S.iterations;
-  const uint32_t ne = B.assoc.n_assoc[8 * pair], np = B.assoc.n_assoc[8 * pair + 1];
-  for (int c = 0; c < 6; c++) B.assoc.n_assoc[8 * pair + c] = 0;
+  const uint32_t ne = B.n_assoc[8 * pair], np = B.n_assoc[8 * pair + 1];
+  for (int c = 0; c < 6; c++) B.n_assoc[8 * pair + c] = 0;
   if ((uint64_t)ne + np < C.min_associations) {  // registration-inl.h:45-48
     S.termination = LOAMX_INSUFFICIENT_ASSOCIATIONS;
     S.active = 0;
@@ -1573,12 +1580,12 @@ __global__ __launch_bounds__(kSweepThreads, LOAMX_SWEEP_WAVES) void sweep_kernel
   double x[7];
 #pragma unroll
   for (int i = 0; i < 7; i++) x[i] = S.lm.xeval[i];
-  const uint32_t n_se_raw = B.n_src_edge[pair * B.in_pitch], n_sp_raw = B.n_src_planar[pair * B.in_pitch];
-  const uint32_t n_se = n_se_raw < B.edge_stride ? n_se_raw : (uint32_t)B.edge_stride;
-  const uint32_t n_sp = n_sp_raw < B.planar_stride ? n_sp_raw : (uint32_t)B.planar_stride;
-  const size_t efield = B.n_pairs * B.edge_stride, pfield = B.n_pairs * B.planar_stride;
-  const double* __restrict__ E = B.assoc.edge + pair * B.edge_stride;
-  const double* __restrict__ Pl = B.assoc.plane + pair * B.planar_stride;
+  const uint32_t n_se_raw = B.kind[kEdge].n_src[pair * B.in_pitch], n_sp_raw = B.kind[kPlane].n_src[pair * B.in_pitch];
+  const uint32_t n_se = n_se_raw < B.kind[kEdge].stride ? n_se_raw : (uint32_t)B.kind[kEdge].stride;
+  const uint32_t n_sp = n_sp_raw < B.kind[kPlane].stride ? n_sp_raw : (uint32_t)B.kind[kPlane].stride;
+  const size_t efield = B.n_pairs * B.kind[kEdge].stride, pfield = B.n_pairs * B.kind[kPlane].stride;
+  const double* __restrict__ E = B.kind[kEdge].rec + pair * B.kind[kEdge].stride;
+  const double* __restrict__ Pl = B.kind[kPlane].rec + pair * B.kind[kPlane].stride;
   double acc[kAccSize];
 #pragma unroll
   for (int j = 0; j < kAccSize; j++) acc[j] = 0.0;
@@ -1673,9 +1680,9 @@ __device__ __forceinline__ double light_eval(const RegBatch& B, size_t pair, con
                                              const double* mom, LightLds& L, const double (*s_edge)[kEdgeCache], const uint32_t* s_listed,
                                              const double (*s_frec)[kFlatCache], uint32_t n_flat) {
   const int lane = threadIdx.x;  // (64-thread workgroup)
-  const size_t efield = B.n_pairs * B.edge_stride, pfield = B.n_pairs * B.planar_stride;
-  const double* __restrict__ E = B.assoc.edge + pair * B.edge_stride;
-  const double* __restrict__ Pl = B.assoc.plane + pair * B.planar_stride;
+  const size_t efield = B.n_pairs * B.kind[kEdge].stride, pfield = B.n_pairs * B.kind[kPlane].stride;
+  const double* __restrict__ E = B.kind[kEdge].rec + pair * B.kind[kEdge].stride;
+  const double* __restrict__ Pl = B.kind[kPlane].rec + pair * B.kind[kPlane].stride;
   double acc[kAccSize];
 #pragma unroll
   for (int j = 0; j < kAccSize; j++) acc[j] = 0.0;
@@ -1803,9 +1810,9 @@ __device__ __forceinline__ double light_eval(const RegBatch& B, size_t pair, con
  * candidate has left their validity bound — rare). Lanes 0..kAccSize-1 return their entry of the sums. */
 __device__ __forceinline__ double stream_eval_wave(const RegBatch& B, size_t pair, const double x[7], uint32_t n_se, uint32_t n_sp) {
   const int lane = threadIdx.x;
-  const size_t efield = B.n_pairs * B.edge_stride, pfield = B.n_pairs * B.planar_stride;
-  const double* __restrict__ E = B.assoc.edge + pair * B.edge_stride;
-  const double* __restrict__ Pl = B.assoc.plane + pair * B.planar_stride;
+  const size_t efield = B.n_pairs * B.kind[kEdge].stride, pfield = B.n_pairs * B.kind[kPlane].stride;
+  const double* __restrict__ E = B.kind[kEdge].rec + pair * B.kind[kEdge].stride;
+  const double* __restrict__ Pl = B.kind[kPlane].rec + pair * B.kind[kPlane].stride;
   double acc[kAccSize];
 #pragma unroll
   for (int j = 0; j < kAccSize; j++) acc[j] = 0.0;
@@ -1866,9 +1873,9 @@ __global__ __launch_bounds__(64) void lm_step_kernel(RegBatch B) {  // one wavef
   if (pair >= B.n_pairs) return;
   PairState& S = B.state[pair];
   if (!S.active || !S.lm.active) return;
-  const uint32_t n_se_raw = B.n_src_edge[pair * B.in_pitch], n_sp_raw = B.n_src_planar[pair * B.in_pitch];
-  const uint32_t n_se = n_se_raw < B.edge_stride ? n_se_raw : (uint32_t)B.edge_stride;
-  const uint32_t n_sp = n_sp_raw < B.planar_stride ? n_sp_raw : (uint32_t)B.planar_stride;
+  const uint32_t n_se_raw = B.kind[kEdge].n_src[pair * B.in_pitch], n_sp_raw = B.kind[kPlane].n_src[pair * B.in_pitch];
+  const uint32_t n_se = n_se_raw < B.kind[kEdge].stride ? n_se_raw : (uint32_t)B.kind[kEdge].stride;
+  const uint32_t n_sp = n_sp_raw < B.kind[kPlane].stride ? n_sp_raw : (uint32_t)B.kind[kPlane].stride;
   const uint32_t used = S.stream_planes ? (n_se + n_sp + kSweepChunk - 1) / kSweepChunk : 1u;  // blocks that wrote a partial
   double acc[kAccSize];
   for (int j = 0; j < kAccSize; j++) acc[j] = 0.0;
@@ -1942,12 +1949,12 @@ __global__ __launch_bounds__(64) void lm_pair_loop_kernel(RegBatch B, RegConfig 
   }
   wave_lds_fence();
   PairState& S = s_S;
-  const uint32_t n_se_raw = B.n_src_edge[pair * B.in_pitch], n_sp_raw = B.n_src_planar[pair * B.in_pitch];
-  const uint32_t n_se = n_se_raw < B.edge_stride ? n_se_raw : (uint32_t)B.edge_stride;
-  const uint32_t n_sp = n_sp_raw < B.planar_stride ? n_sp_raw : (uint32_t)B.planar_stride;
+  const uint32_t n_se_raw = B.kind[kEdge].n_src[pair * B.in_pitch], n_sp_raw = B.kind[kPlane].n_src[pair * B.in_pitch];
+  const uint32_t n_se = n_se_raw < B.kind[kEdge].stride ? n_se_raw : (uint32_t)B.kind[kEdge].stride;
+  const uint32_t n_sp = n_sp_raw < B.kind[kPlane].stride ? n_sp_raw : (uint32_t)B.kind[kPlane].stride;
   {  // the pair's edge records and listed-record counts into LDS (independent loads: one round trip)
-    const size_t efield = B.n_pairs * B.edge_stride;
-    const double* __restrict__ E = B.assoc.edge + pair * B.edge_stride;
+    const size_t efield = B.n_pairs * B.kind[kEdge].stride;
+    const double* __restrict__ E = B.kind[kEdge].rec + pair * B.kind[kEdge].stride;
     const uint32_t nc = n_se < kEdgeCache ? n_se : kEdgeCache;
     for (uint32_t v = lane; v < nc; v += 64) {
 #pragma unroll
@@ -2010,8 +2017,8 @@ __global__ __launch_bounds__(64) void lm_pair_loop_kernel(RegBatch B, RegConfig 
     if (total <= kFlatCache) {  // uniform
       s_pref[lane] = incl - mine;  // first flat entry of tile `lane`
       wave_lds_fence();
-      const size_t pfield = B.n_pairs * B.planar_stride;
-      const double* __restrict__ Pl = B.assoc.plane + pair * B.planar_stride;
+      const size_t pfield = B.n_pairs * B.kind[kPlane].stride;
+      const double* __restrict__ Pl = B.kind[kPlane].rec + pair * B.kind[kPlane].stride;
       for (uint32_t e = lane; e < total; e += 64) {
         uint32_t lb = 0;  // the tile of flat entry e: the last one whose first entry is <= e (tiles <= 64: a short scan of LDS words)
         for (uint32_t t = 1; t < tiles; t++) lb = s_pref[t] <= e ? t : lb;
@@ -2080,13 +2087,13 @@ __global__ __launch_bounds__(64) void moment_kernel(RegBatch B) {  // one wavefr
   const uint32_t blk = (blockIdx.x >> 2) % B.mom_blocks_per_pair;
   const PairState& S = B.state[pair];
   if (!S.active || !S.lm.active || !S.use_moments) return;  // uniform per workgroup
-  const uint32_t n_sp_raw = B.n_src_planar[pair * B.in_pitch];
-  const uint32_t n_sp = n_sp_raw < B.planar_stride ? n_sp_raw : (uint32_t)B.planar_stride;
+  const uint32_t n_sp_raw = B.kind[kPlane].n_src[pair * B.in_pitch];
+  const uint32_t n_sp = n_sp_raw < B.kind[kPlane].stride ? n_sp_raw : (uint32_t)B.kind[kPlane].stride;
   const uint32_t base = blk * kSweepChunk;
   if (base >= n_sp) return;  // uniform per workgroup
   if (blk == 0 && tix == 0 && B.sweep_slots) atomicAdd(&B.sweep_slots[4], (unsigned long long)n_sp);
-  const size_t pfield = B.n_pairs * B.planar_stride;
-  const double* __restrict__ Pl = B.assoc.plane + pair * B.planar_stride;
+  const size_t pfield = B.n_pairs * B.kind[kPlane].stride;
+  const double* __restrict__ Pl = B.kind[kPlane].rec + pair * B.kind[kPlane].stride;
   double(*tile)[kMomLdsRow] = s_c;
 #pragma unroll
   for (int j = kMomDim; j < kMomStride; j++) tile[j][lane] = 0.0;  // padding rows
@@ -2270,17 +2277,18 @@ __global__ __launch_bounds__(64) void knn_queries_kernel(GridSet gs, const doubl
 // Threads [0, n_src) read the round-1 results, threads [n_src, n_src + queued) the queue's.
 template <bool PLANE, int KM>
 __global__ __launch_bounds__(256) void assoc_dump_kernel(RegBatch B, RegConfig C, AssocDumpSet D) {
-  const size_t stride = PLANE ? B.planar_stride : B.edge_stride;
-  const uint32_t n_raw = PLANE ? B.n_src_planar[0] : B.n_src_edge[0];
+  const RegKind& K = B.kind[PLANE];
+  const RegKindConfig& CK = C.kind[PLANE];
+  const size_t stride = K.stride;
+  const uint32_t n_raw = K.n_src[0];
   const uint32_t n_src = n_raw < stride ? n_raw : (uint32_t)stride;
-  const uint32_t queued = B.assoc.n_assoc[PLANE ? 3 : 2];
+  const uint32_t queued = B.n_assoc[PLANE ? 3 : 2];
   const uint32_t t = blockIdx.x * 256 + threadIdx.x;
   if (t >= n_src + queued) return;
-  const GridSet& gs = PLANE ? B.grid_plane : B.grid_edge;
-  const GridSet& src_gs = PLANE ? B.src_grid_plane : B.src_grid_edge;
-  const uint32_t* __restrict__ nn = PLANE ? B.assoc.nn_plane : B.assoc.nn_edge;
-  const uint32_t* __restrict__ rnn = PLANE ? B.assoc.rnn_plane : B.assoc.rnn_edge;
-  const uint32_t* __restrict__ rest = PLANE ? B.assoc.rest_plane : B.assoc.rest_edge;
+  const GridSet &gs = K.grid, &src_gs = K.src_grid;
+  const uint32_t* __restrict__ nn = K.nn;
+  const uint32_t* __restrict__ rnn = K.rnn;
+  const uint32_t* __restrict__ rest = K.rest;
   uint32_t i, at;
   const uint32_t* __restrict__ src;
   if (t < n_src) {
@@ -2290,14 +2298,14 @@ __global__ __launch_bounds__(256) void assoc_dump_kernel(RegBatch B, RegConfig C
     at = t - n_src, i = rest[at] & kQueueIndex, src = rnn;
   }
   const uint32_t orig = src_gs.sorted[i].orig;
-  const int kq = PLANE ? C.k_plane : C.k_edge, kk = kq < KM ? kq : KM, shift = KM - kk;
+  const int kq = CK.k, kk = kq < KM ? kq : KM, shift = KM - kk;
   const uint32_t kept = src[at];
   D.nn_count[orig] = kept;
   for (int j = 0; j < kk; j++) {
     const uint32_t pos = src[(size_t)(1 + shift + j) * stride + at];
     D.nn_idx[(size_t)orig * (size_t)kq + j] = (uint32_t)j < kept && pos < gs.stride ? gs.sorted[pos].orig : 0xFFFFFFFFu;
   }
-  const double* __restrict__ rec = PLANE ? B.assoc.plane : B.assoc.edge;
+  const double* __restrict__ rec = K.rec;
   const double f0 = rec[i];
   D.valid[orig] = f0 == f0 ? 1 : 0;
   // (an invalid slot holds NaN in field 0: the moved point's x is recomputed from the source point)
@@ -2334,19 +2342,17 @@ void launch_knn_queries(const GridSet& gs, const double* d_q, size_t n_q, int k,
   else launch_kernel((knn_queries_kernel<16>), grid, dim3(64), 0, s, gs, d_q, n_q, k, max_dist, pass_max, d_idx, d_count);
 }
 
-void launch_assoc_dump(const RegBatch& B, const RegConfig& C, const AssocDumpSet& edge, const AssocDumpSet& plane, hipStream_t s) {
-  // (both queues can be as long as the sets: threads for n_src + queued)
-  const dim3 ge((unsigned)((2 * B.edge_stride + 255) / 256)), gp((unsigned)((2 * B.planar_stride + 255) / 256));
-  if (edge.nn_count) {
-    if (C.k_edge <= 5) launch_kernel((assoc_dump_kernel<false, 5>), ge, dim3(256), 0, s, B, C, edge);
-    else if (C.k_edge <= 8) launch_kernel((assoc_dump_kernel<false, 8>), ge, dim3(256), 0, s, B, C, edge);
-    else launch_kernel((assoc_dump_kernel<false, 16>), ge, dim3(256), 0, s, B, C, edge);
+void launch_assoc_dump(const RegBatch& B, const RegConfig& C, const AssocDumpSet (&out)[2], hipStream_t s) {
+#define LOAMX_DUMP(PL)                                                                                                                  \
+  if (out[PL].nn_count) {                                                                                                               \
+    const dim3 grid((unsigned)((2 * B.kind[PL].stride + 255) / 256)); /* the queue can be as long as the set: threads for n_src + queued */ \
+    if (C.kind[PL].k <= 5) launch_kernel((assoc_dump_kernel<PL, 5>), grid, dim3(256), 0, s, B, C, out[PL]);                               \
+    else if (C.kind[PL].k <= 8) launch_kernel((assoc_dump_kernel<PL, 8>), grid, dim3(256), 0, s, B, C, out[PL]);                          \
+    else launch_kernel((assoc_dump_kernel<PL, 16>), grid, dim3(256), 0, s, B, C, out[PL]);                                                \
   }
-  if (plane.nn_count) {
-    if (C.k_plane <= 5) launch_kernel((assoc_dump_kernel<true, 5>), gp, dim3(256), 0, s, B, C, plane);
-    else if (C.k_plane <= 8) launch_kernel((assoc_dump_kernel<true, 8>), gp, dim3(256), 0, s, B, C, plane);
-    else launch_kernel((assoc_dump_kernel<true, 16>), gp, dim3(256), 0, s, B, C, plane);
-  }
+  LOAMX_DUMP(false)
+  LOAMX_DUMP(true)
+#undef LOAMX_DUMP
 }
 
 // map-sized target sets: the multi-workgroup build (needs kBigScratchBytes of scratch per pair)
@@ -2437,52 +2443,48 @@ static void launch_grid_build(size_t n_pairs, const double* pts, const uint32_t*
                        in_pitch, max_dist, gs, scratch, bytes, box_min, box_max, box_bad, small_if);
 }
 
-void launch_grid_build_target(const RegBatch& B, const RegConfig& C, bool plane, hipStream_t s) {
+void launch_grid_build_target(const RegBatch& B, const RegConfig& C, int kind, hipStream_t s) {
   if (B.n_pairs == 0) return;
+  const RegKind& K = B.kind[kind];
   // (boxes: [scan][kind][axis]; the target scan of pair p is scan p * in_pitch of the arrays in B)
-  const unsigned long long* bmin = B.box_min ? B.box_min + (plane ? 3 : 0) : nullptr;
-  const unsigned long long* bmax = B.box_max ? B.box_max + (plane ? 3 : 0) : nullptr;
-  if (plane) launch_grid_build<false>(B.n_pairs, B.tgt_planar, B.n_tgt_planar, B.planar_stride, B.in_pitch, C.r_plane, B.grid_plane, B.sort_scratch, C.flags, s, B.grid_bytes, bmin, bmax, B.box_bad);
-  else {
-    launch_grid_build<false>(B.n_pairs, B.tgt_edge, B.n_tgt_edge, B.edge_stride, B.in_pitch, C.r_edge, B.grid_edge, B.sort_scratch, C.flags, s, B.grid_bytes, bmin, bmax, B.box_bad,
-                             B.small_edge_sets == 1u ? B.n_tgt_edge : nullptr);
-    if (B.small_edge_sets == 1u)  // (both edge sets of the pairs whose target edge set is brute-force sized)
-      launch_kernel(small_sets_build_kernel, dim3((unsigned)B.n_pairs), dim3(kSmallThreads), 0, s, B.tgt_edge, B.n_tgt_edge, B.src_edge, B.n_src_edge, B.edge_stride,
-                    B.in_pitch, C.r_edge, B.grid_edge, B.src_grid_edge, B.grid_bytes, bmin, bmax, B.box_bad);
-  }
+  const unsigned long long* bmin = B.box_min ? B.box_min + 3 * kind : nullptr;
+  const unsigned long long* bmax = B.box_max ? B.box_max + 3 * kind : nullptr;
+  const bool small_edges = kind == kEdge && B.small_edge_sets == 1u;
+  launch_grid_build<false>(B.n_pairs, K.tgt, K.n_tgt, K.stride, B.in_pitch, C.kind[kind].r, K.grid, B.sort_scratch, C.flags, s, B.grid_bytes, bmin, bmax, B.box_bad,
+                           small_edges ? K.n_tgt : nullptr);
+  if (small_edges)  // (both edge sets of the pairs whose target edge set is brute-force sized)
+    launch_kernel(small_sets_build_kernel, dim3((unsigned)B.n_pairs), dim3(kSmallThreads), 0, s, K.tgt, K.n_tgt, K.src, K.n_src, K.stride,
+                  B.in_pitch, C.kind[kind].r, K.grid, K.src_grid, B.grid_bytes, bmin, bmax, B.box_bad);
 }
 void launch_grid_build_targets(const RegBatch& B, const RegConfig& C, hipStream_t s) {
-  launch_grid_build_target(B, C, false, s);
-  launch_grid_build_target(B, C, true, s);
+  for (int kind = 0; kind < 2; kind++) launch_grid_build_target(B, C, kind, s);
 }
 
 // source sets: only the cell-sorted (Morton) order is used
 // (the scratch copy is shared by the two source sets: build + rank of one complete before the next one's build starts — both
 // on ONE stream. It is NOT the target builds' scratch: those run on another stream at the same time, and the multi-workgroup
 // build of a target set above kGridSmallCap points keeps its box keys and cursors there)
-void launch_grid_build_source(const RegBatch& B, const RegConfig& C, bool plane, hipStream_t s) {
+void launch_grid_build_source(const RegBatch& B, const RegConfig& C, int kind, hipStream_t s) {
   if (B.n_pairs == 0) return;
-  const size_t stride = plane ? B.planar_stride : B.edge_stride;
-  const uint32_t* n_src = plane ? B.n_src_planar : B.n_src_edge;
-  const GridSet& gs = plane ? B.src_grid_plane : B.src_grid_edge;
-  // (boxes: a pair's source scan lies src_box_offset scans behind its target scan; 0: the caller has no boxes for the sources)
-  if (!plane && B.small_edge_sets == 2u) {  // (persistent index with a brute-force sized edge set: the sources in their given order, as in a plain call)
+  const RegKind& K = B.kind[kind];
+  if (kind == kEdge && B.small_edge_sets == 2u) {  // (persistent index with a brute-force sized edge set: the sources in their given order, as in a plain call)
     launch_kernel(small_sets_build_kernel, dim3((unsigned)B.n_pairs), dim3(kSmallThreads), 0, s, static_cast<const double*>(nullptr), static_cast<const uint32_t*>(nullptr),
-                  B.src_edge, B.n_src_edge, B.edge_stride, B.in_pitch, C.r_edge, B.grid_edge, B.src_grid_edge, B.grid_bytes, static_cast<const unsigned long long*>(nullptr),
+                  K.src, K.n_src, K.stride, B.in_pitch, C.kind[kind].r, K.grid, K.src_grid, B.grid_bytes, static_cast<const unsigned long long*>(nullptr),
                   static_cast<const unsigned long long*>(nullptr), static_cast<const uint32_t*>(nullptr));
     return;
   }
-  const unsigned long long* bmin = (B.box_min && B.src_box_offset) ? B.box_min + 6 * B.src_box_offset + (plane ? 3 : 0) : nullptr;
-  const unsigned long long* bmax = (B.box_max && B.src_box_offset) ? B.box_max + 6 * B.src_box_offset + (plane ? 3 : 0) : nullptr;
-  launch_grid_build<true>(B.n_pairs, plane ? B.src_planar : B.src_edge, n_src, stride, B.in_pitch, plane ? C.r_plane : C.r_edge, gs,
-                          B.sort_scratch_src, C.flags, s, B.grid_bytes, bmin, bmax, B.box_bad, (!plane && B.small_edge_sets == 1u) ? B.n_tgt_edge : nullptr);
-  if (stride && !grid_small(stride, C.flags))
-    launch_kernel(grid_rank_kernel, dim3((unsigned)((stride + kRankThreads - 1) / kRankThreads), (unsigned)B.n_pairs), dim3(kRankThreads), 0, s,
-                  n_src, stride, B.in_pitch, gs, B.sort_scratch_src, (!plane && B.small_edge_sets == 1u) ? B.n_tgt_edge : nullptr);
+  // (boxes: a pair's source scan lies src_box_offset scans behind its target scan; 0: the caller has no boxes for the sources)
+  const unsigned long long* bmin = (B.box_min && B.src_box_offset) ? B.box_min + 6 * B.src_box_offset + 3 * kind : nullptr;
+  const unsigned long long* bmax = (B.box_max && B.src_box_offset) ? B.box_max + 6 * B.src_box_offset + 3 * kind : nullptr;
+  const uint32_t* small_if = (kind == kEdge && B.small_edge_sets == 1u) ? K.n_tgt : nullptr;
+  launch_grid_build<true>(B.n_pairs, K.src, K.n_src, K.stride, B.in_pitch, C.kind[kind].r, K.src_grid, B.sort_scratch_src, C.flags, s, B.grid_bytes, bmin, bmax,
+                          B.box_bad, small_if);
+  if (K.stride && !grid_small(K.stride, C.flags))
+    launch_kernel(grid_rank_kernel, dim3((unsigned)((K.stride + kRankThreads - 1) / kRankThreads), (unsigned)B.n_pairs), dim3(kRankThreads), 0, s,
+                  K.n_src, K.stride, B.in_pitch, K.src_grid, B.sort_scratch_src, small_if);
 }
 void launch_grid_build_sources(const RegBatch& B, const RegConfig& C, hipStream_t s) {
-  launch_grid_build_source(B, C, false, s);
-  launch_grid_build_source(B, C, true, s);
+  for (int kind = 0; kind < 2; kind++) launch_grid_build_source(B, C, kind, s);
 }
 
 void launch_state_init(const RegBatch& B, const RegConfig& C, hipStream_t s) {
@@ -2501,11 +2503,11 @@ void launch_state_init(const RegBatch& B, const RegConfig& C, hipStream_t s) {
 // runs at least that long hides them. Measured (same box, 64 x 1024 scan pairs): 256 pairs 3.73 (one) vs 3.88 ms (two),
 // 512 / 1 024 pairs equal, 2 048 / 4 096 pairs 22.7 / 45.2 vs 22.5 / 44.3 ms; a single pair 0.92 vs 0.98 ms.
 constexpr size_t kQueueTwoStageMin = 16u << 20;  // source features in the batch (1 024 pairs of 64 x 1024: 20 M slots)
-static bool queue_one_stage(const RegBatch& B, const RegConfig& C, bool plane) {
+static bool queue_one_stage(const RegBatch& B, const RegConfig& C, int kind) {
   if (C.flags & kRegFlagQueueTwoStage) return false;
   if (C.flags & kRegFlagQueueOneStage) return true;
   if (!(C.flags & kRegFlagNoCoopLeft)) return false;  // the cooperative leftover kernel is short at every batch size
-  return B.n_pairs * (plane ? B.planar_stride : B.edge_stride) < kQueueTwoStageMin;
+  return B.n_pairs * B.kind[kind].stride < kQueueTwoStageMin;
 }
 // wavefronts per pair of associate_knn_coop_kernel (one listed entry per wavefront and turn): a batch lists 15-35 entries per pair,
 // a single scan-to-map registration up to half of its queries
@@ -2524,8 +2526,8 @@ static uint32_t rest_blocks(size_t n_pairs, uint32_t nblk) {
 void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipStream_t aux, hipStream_t aux2, hipEvent_t ev_fork,
                       hipEvent_t ev_mid, hipEvent_t ev_join, hipEvent_t ev_join2, LaunchScope* knn_scope, uint32_t what) {
   if (B.n_pairs == 0) return;
-  const uint32_t be = B.assoc_blocks_edge != 0xFFFFFFFFu ? B.assoc_blocks_edge : (uint32_t)((B.edge_stride + kAssocThreads - 1) / kAssocThreads);
-  const uint32_t bp = B.assoc_blocks_plane != 0xFFFFFFFFu ? B.assoc_blocks_plane : (uint32_t)((B.planar_stride + kAssocThreads - 1) / kAssocThreads);
+  auto blocks = [](const RegKind& K) { return K.assoc_blocks != 0xFFFFFFFFu ? K.assoc_blocks : (uint32_t)((K.stride + kAssocThreads - 1) / kAssocThreads); };
+  const uint32_t be = blocks(B.kind[kEdge]), bp = blocks(B.kind[kPlane]);
   const size_t pair_groups = (B.n_pairs + 7) / 8;  // grid covers 8 XCD lanes x pair_groups x chunks
   // register-resident neighbour lists are instantiated for K <= 5 (the reference's default), K <= 8 and K <= 16
   // Per feature kind, two chains: A = brute force (small target sets) | round-1 k-NN -> fit of the
@@ -2536,7 +2538,7 @@ void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipS
 #define LOAMX_ASSOC_A1(PL, KMV, nblk, st)                                                                         \
   do {                                                                                                            \
     const dim3 grid_((unsigned)(pair_groups * 8 * (nblk)));                                                       \
-    const uint32_t mode_ = (PL) ? B.knn_mode_plane : B.knn_mode_edge; /* a kernel no pair needs is not launched */   \
+    const uint32_t mode_ = B.kind[PL].knn_mode; /* a kernel no pair needs is not launched */                      \
     if (mode_ != 2u) {                                                                                            \
       LaunchScope* outer_ = g_launch_scope;                                                                       \
       if ((PL) && knn_scope) g_launch_scope = knn_scope;                                                          \
@@ -2573,15 +2575,15 @@ void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipS
   } while (0)
 #define LOAMX_ASSOC_K(STEP, PL, nblk, st)                \
   do {                                                   \
-    if ((PL ? C.k_plane : C.k_edge) <= 5) STEP(PL, 5, nblk, st); \
-    else if ((PL ? C.k_plane : C.k_edge) <= 8) STEP(PL, 8, nblk, st); \
+    if (C.kind[PL].k <= 5) STEP(PL, 5, nblk, st);        \
+    else if (C.kind[PL].k <= 8) STEP(PL, 8, nblk, st);   \
     else STEP(PL, 16, nblk, st);                         \
   } while (0)
   const bool edges = (what & kAssocEdges) != 0u && be != 0u, planes = (what & kAssocPlanes) != 0u && bp != 0u;
   // The usual case — every edge set small enough for brute force, every planar set searched through its grid, the
   // reference's five neighbours — runs the first kernels of both kinds as ONE launch each (associate_knn_mixed_kernel,
   // associate_fit_mixed_kernel): no edge chain on a side stream.
-  if (edges && planes && B.knn_mode_edge == 2u && B.knn_mode_plane == 1u && C.k_edge <= 5 && C.k_plane <= 5 &&
+  if (edges && planes && B.kind[kEdge].knn_mode == 2u && B.kind[kPlane].knn_mode == 1u && C.kind[kEdge].k <= 5 && C.kind[kPlane].k <= 5 &&
       !(C.flags & kRegFlagNoMixedAssoc)) {
     const uint32_t edge_blocks = (uint32_t)(pair_groups * 8 * be);
     const dim3 grid((unsigned)(edge_blocks + pair_groups * 8 * bp));
@@ -2608,7 +2610,7 @@ void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipS
     LOAMX_ASSOC_K(LOAMX_ASSOC_A1, false, be, sa);
     LOAMX_ASSOC_K(LOAMX_ASSOC_A2, false, be, sa);
     // (the brute-force kernel finishes every query itself: with no grid search in the batch nothing is ever queued)
-    if (B.knn_mode_edge != 2u) LOAMX_ASSOC_K(LOAMX_ASSOC_B, false, be, sa);
+    if (B.kind[kEdge].knn_mode != 2u) LOAMX_ASSOC_K(LOAMX_ASSOC_B, false, be, sa);
   }
   if (planes) {
     LOAMX_ASSOC_K(LOAMX_ASSOC_A1, true, bp, s);
@@ -2618,7 +2620,7 @@ void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipS
     hipStream_t sb = aux2 ? aux2 : aux;
     const bool fork2 = use_aux && (aux2 || fork) && hipEventRecord(ev_mid, s) == hipSuccess && hipStreamWaitEvent(sb, ev_mid, 0) == hipSuccess;
     LOAMX_ASSOC_K(LOAMX_ASSOC_A2, true, bp, s);
-    if (B.knn_mode_plane != 2u) LOAMX_ASSOC_K(LOAMX_ASSOC_B, true, bp, (fork2 ? sb : s));
+    if (B.kind[kPlane].knn_mode != 2u) LOAMX_ASSOC_K(LOAMX_ASSOC_B, true, bp, (fork2 ? sb : s));
     if (fork2 && aux2 && hipEventRecord(ev_join2, aux2) == hipSuccess) (void)hipStreamWaitEvent(s, ev_join2, 0);
   }
   if (fork && hipEventRecord(ev_join, aux) == hipSuccess) (void)hipStreamWaitEvent(s, ev_join, 0);
@@ -2633,12 +2635,12 @@ void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipS
 __global__ void nn_same_kernel(RegBatch B, uint32_t* prev, unsigned long long* stats, uint32_t it) {
   const size_t pair = blockIdx.y;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t n = B.n_src_planar[pair * B.in_pitch];
-  if (i >= n || i >= B.planar_stride || !B.state[pair].active) return;
-  const size_t field = B.n_pairs * B.planar_stride, slot = pair * B.planar_stride + i;
-  bool same = it > 0, queued = B.assoc.nn_plane[slot] == 0xFFFFFFFFu;
+  const uint32_t n = B.kind[kPlane].n_src[pair * B.in_pitch];
+  if (i >= n || i >= B.kind[kPlane].stride || !B.state[pair].active) return;
+  const size_t field = B.n_pairs * B.kind[kPlane].stride, slot = pair * B.kind[kPlane].stride + i;
+  bool same = it > 0, queued = B.kind[kPlane].nn[slot] == 0xFFFFFFFFu;
   for (int f = 0; f < 6; f++) {
-    const uint32_t v = B.assoc.nn_plane[f * field + slot];
+    const uint32_t v = B.kind[kPlane].nn[f * field + slot];
     if (prev[f * field + slot] != v) same = false;
     prev[f * field + slot] = v;
   }
@@ -2649,10 +2651,10 @@ __global__ void nn_same_kernel(RegBatch B, uint32_t* prev, unsigned long long* s
 void debug_nn_same(const RegBatch& B, uint32_t it, hipStream_t s) {
   static uint32_t* prev = nullptr;
   static unsigned long long* stats = nullptr;
-  const size_t words = 6 * B.n_pairs * B.planar_stride;
+  const size_t words = 6 * B.n_pairs * B.kind[kPlane].stride;
   if (!prev) { (void)hipMalloc(&prev, words * 4); (void)hipMalloc(&stats, 24); }
   (void)hipMemsetAsync(stats, 0, 24, s);
-  launch_kernel(nn_same_kernel, dim3((unsigned)((B.planar_stride + 255) / 256), (unsigned)B.n_pairs), dim3(256), 0, s, B, prev, stats, it);
+  launch_kernel(nn_same_kernel, dim3((unsigned)((B.kind[kPlane].stride + 255) / 256), (unsigned)B.n_pairs), dim3(256), 0, s, B, prev, stats, it);
   unsigned long long h[3];
   (void)hipMemcpyAsync(h, stats, 24, hipMemcpyDeviceToHost, s);
   (void)hipStreamSynchronize(s);

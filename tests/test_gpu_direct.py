@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import reference_kats as K
-from gpu_common import ctx, option
+from gpu_common import ctx, option, pose_diff, to_capi_reg
 from loam_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -98,6 +98,42 @@ def test_associate_lists_and_fits_on_scan_pairs(oracle, H, W, seed, pair):
         ne = check_kind(oracle, "scan-edge", dump, B[eb], A[ea], pose, False, oreg)
         npl = check_kind(oracle, "scan-plane", dump, B[pb], A[pa], pose, True, oreg)
         assert ne > 50 and npl > 2000
+
+
+def test_every_per_kind_parameter_different_under_poison(oracle):
+    """k, radius and the fewest fit points all differ between edges and planes (min_plane_fit_points off its default as
+    well), scratch starting as 0xFF bytes: a parameter or buffer of one kind read for the other shows in the lists, the
+    valid sets or the iteration counts."""
+    H, W, seed, pair = 32, 512, 3, 2
+    A = capi.synth_scan_host(seed, pair, 0, H, W, 0.01)
+    B = capi.synth_scan_host(seed, pair, 1, H, W, 0.01)
+    ea, pa = oracle.extract_features(A, H, W, 1.0, 120.0)
+    eb, pb = oracle.extract_features(B, H, W, 1.0, 120.0)
+    oreg = oracle.RegParams()
+    oreg.num_edge_neighbors, oreg.num_plane_neighbors = 3, 7
+    oreg.max_edge_neighbor_dist, oreg.max_plane_neighbor_dist = 0.6, 1.5
+    oreg.min_line_fit_points, oreg.min_plane_fit_points = 2, 6
+    reg = to_capi_reg(oreg)
+    # not vacuous: both kinds associate, and in both the oracle turns a query away for too few neighbours inside the radius
+    for src, tgt, is_plane in ((B[eb], A[ea], False), (B[pb], A[pa], True)):
+        valid, _, moved, _ = oracle.associate(src, tgt, IDENT, is_plane, oreg)
+        tree = oracle.KDTree(tgt)
+        k, radius, fewest = (7, 1.5, 6) if is_plane else (3, 0.6, 2)
+        assert valid.sum() >= 20 and any(len(tree.knn(m, k, radius)) < fewest for m in moved)
+    po, to, io, info = oracle.register_features(B[eb], B[pb], A[ea], A[pa], params=oreg, want_info=True)
+    with option("DEBUG_POISON"):
+        dump = ctx().associate(B[eb], B[pb], A[ea], A[pa], IDENT, reg)
+        pg, tg, ig, det = ctx().register_features(B[eb], B[pb], A[ea], A[pa], reg=reg, want_detail=True)
+    assert check_kind(oracle, "scan-edge", dump, B[eb], A[ea], IDENT, False, oreg) >= 20
+    assert check_kind(oracle, "scan-plane", dump, B[pb], A[pa], IDENT, True, oreg) >= 20
+    assert (tg, ig) == (to, io)
+    assert [(a.n_edge_assoc, a.n_plane_assoc) for a in info] == [(d["n_edge"], d["n_plane"]) for d in det["iterations"]]
+    rot, trans = pose_diff(oracle, po, pg)
+    assert rot < 1e-5 and trans < 1e-5, (rot, trans)  # (SE3_TOL of test_gpu_register.py)
+    for pairs, src, tgt, is_plane in ((det["iterations"][0]["edge_pairs"], B[eb], A[ea], False),
+                                      (det["iterations"][0]["plane_pairs"], B[pb], A[pa], True)):
+        valid, nearest, _, _ = oracle.associate(src, tgt, IDENT, is_plane, oreg)
+        assert np.array_equal(pairs[:, 0], np.nonzero(valid)[0]) and np.array_equal(pairs[:, 1], nearest[valid])
 
 
 def test_associate_does_not_depend_on_max_iterations(oracle):
