@@ -57,6 +57,42 @@ inline loamx_reg_params toC(const RegistrationParams& p) {
                           p.min_plane_fit_points,   p.max_avg_point_plane_dist,    p.max_iterations,
                           p.rotation_convergence_thresh, p.position_convergence_thresh, p.min_associations};
 }
+/// The buffers behind a loamx_reg_detail for one registration, and their way back into a RegistrationDetail
+/// (nothing is allocated or captured when `detail` is null).
+class DetailCapture {
+ public:
+  DetailCapture(std::shared_ptr<RegistrationDetail> detail, size_t n_se, size_t n_sp, size_t mi) : detail_(std::move(detail)) {
+    if (!detail_) return;
+    info_.resize(mi ? mi : 1);
+    edge_pairs_.resize(2 * (n_se ? n_se : 1) * (mi ? mi : 1));
+    plane_pairs_.resize(2 * (n_sp ? n_sp : 1) * (mi ? mi : 1));
+    n_edge_pairs_.assign(mi ? mi : 1, 0);
+    n_plane_pairs_.assign(mi ? mi : 1, 0);
+    c_.iter_info = info_.data();
+    c_.edge_pairs = edge_pairs_.data(), c_.pairs_cap_edge = n_se ? n_se : 1, c_.n_edge_pairs = n_edge_pairs_.data();
+    c_.plane_pairs = plane_pairs_.data(), c_.pairs_cap_plane = n_sp ? n_sp : 1, c_.n_plane_pairs = n_plane_pairs_.data();
+  }
+  loamx_reg_detail* arg() { return detail_ ? &c_ : nullptr; }
+  void finish(const loamx_reg_result& result) {
+    if (!detail_) return;
+    for (uint32_t it = 0; it < c_.n_iter_info; it++) {
+      std::vector<std::pair<size_t, size_t>> ea, pa;
+      const uint32_t* e = edge_pairs_.data() + (size_t)it * 2 * c_.pairs_cap_edge;
+      const uint32_t* p = plane_pairs_.data() + (size_t)it * 2 * c_.pairs_cap_plane;
+      for (uint32_t k = 0; k < n_edge_pairs_[it]; k++) ea.emplace_back(e[2 * k], e[2 * k + 1]);
+      for (uint32_t k = 0; k < n_plane_pairs_[it]; k++) pa.emplace_back(p[2 * k], p[2 * k + 1]);
+      detail_->iteration_info.emplace_back(Pose3d::fromArray(info_[it].target_T_source_init), ea, pa,
+                                           Pose3d::fromArray(info_[it].estimate_update));
+    }
+    detail_->termination_type = static_cast<RegistrationDetail::TerminationType>(result.termination);
+  }
+
+ private:
+  std::shared_ptr<RegistrationDetail> detail_;
+  std::vector<loamx_iter_info> info_;
+  std::vector<uint32_t> edge_pairs_, plane_pairs_, n_edge_pairs_, n_plane_pairs_;
+  loamx_reg_detail c_{};
+};
 }  // namespace gpu
 
 /// Registers source to target, returning target_T_source (reference registration.h:128-131)
@@ -71,42 +107,20 @@ Pose3d registerFeatures(const LoamFeatures<PointType, Alloc>& source, const Loam
   double init[7];
   target_T_source_init.toArray(init);
   loamx_reg_result result{};
-  const size_t n_se = source.edge_points.size(), n_sp = source.planar_points.size(), mi = params.max_iterations;
-  std::vector<loamx_iter_info> info;
-  std::vector<uint32_t> edge_pairs, plane_pairs, n_edge_pairs, n_plane_pairs;
-  loamx_reg_detail cdetail{};
-  if (detail) {
-    info.resize(mi ? mi : 1);
-    edge_pairs.resize(2 * (n_se ? n_se : 1) * (mi ? mi : 1));
-    plane_pairs.resize(2 * (n_sp ? n_sp : 1) * (mi ? mi : 1));
-    n_edge_pairs.assign(mi ? mi : 1, 0);
-    n_plane_pairs.assign(mi ? mi : 1, 0);
-    cdetail.iter_info = info.data();
-    cdetail.edge_pairs = edge_pairs.data(), cdetail.pairs_cap_edge = n_se ? n_se : 1, cdetail.n_edge_pairs = n_edge_pairs.data();
-    cdetail.plane_pairs = plane_pairs.data(), cdetail.pairs_cap_plane = n_sp ? n_sp : 1, cdetail.n_plane_pairs = n_plane_pairs.data();
-  }
-  gpu::check(ctx, loamx_register_features(ctx, se.data(), n_se, sp.data(), n_sp, te.data(), target.edge_points.size(),
-                                          tp.data(), target.planar_points.size(), init, &rp, &result,
-                                          detail ? &cdetail : nullptr));
-  if (detail) {
-    for (uint32_t it = 0; it < cdetail.n_iter_info; it++) {
-      std::vector<std::pair<size_t, size_t>> ea, pa;
-      const uint32_t* e = edge_pairs.data() + (size_t)it * 2 * cdetail.pairs_cap_edge;
-      const uint32_t* p = plane_pairs.data() + (size_t)it * 2 * cdetail.pairs_cap_plane;
-      for (uint32_t k = 0; k < n_edge_pairs[it]; k++) ea.emplace_back(e[2 * k], e[2 * k + 1]);
-      for (uint32_t k = 0; k < n_plane_pairs[it]; k++) pa.emplace_back(p[2 * k], p[2 * k + 1]);
-      detail->iteration_info.emplace_back(Pose3d::fromArray(info[it].target_T_source_init), ea, pa,
-                                          Pose3d::fromArray(info[it].estimate_update));
-    }
-    detail->termination_type = static_cast<RegistrationDetail::TerminationType>(result.termination);
-  }
+  gpu::DetailCapture capture(detail, source.edge_points.size(), source.planar_points.size(), params.max_iterations);
+  gpu::check(ctx, loamx_register_features(ctx, se.data(), source.edge_points.size(), sp.data(), source.planar_points.size(), te.data(),
+                                          target.edge_points.size(), tp.data(), target.planar_points.size(), init, &rp, &result,
+                                          capture.arg()));
+  capture.finish(result);
   return Pose3d::fromArray(result.pose);
 }
 
 
 /** @brief Extension (not in the reference): the spatial index of a target feature set built once and
  * kept on the device, for scan-to-map registration against a slowly changing local map. The
- * reference rebuilds both KD-trees on every call (registration-inl.h:20-23). */
+ * reference rebuilds both KD-trees on every call (registration-inl.h:20-23). The map is kept up on the device as
+ * well: insert / insertFiltered add a registered scan's features, crop drops what has left the local window,
+ * edgePoints / planarPoints read it back. */
 class TargetIndex {
  public:
   template <template <typename> class Accessor = FieldAccessor, typename PointType, template <typename> class Alloc>
@@ -127,6 +141,35 @@ class TargetIndex {
     gpu::check(gpu::defaultContext(), loamx_target_index_insert(gpu::defaultContext(), handle_.get(), e.data(), more.edge_points.size(),
                                                                 p.data(), more.planar_points.size()));
   }
+  /// Map upkeep after a registration (loamx.h, "map upkeep"): moves the scan's features into the map frame with
+  /// world_T_scan (the arithmetic of Pose3d::act), thins them on a voxel grid — a point is added unless its voxel (edge
+  /// length edge_leaf / planar_leaf; <= 0: no filter for that kind) already holds a point of the map or an earlier point
+  /// of this call — and appends the rest as `insert` would. Returns the points added {edge, planar}.
+  template <template <typename> class Accessor = FieldAccessor, typename PointType, template <typename> class Alloc>
+  std::pair<size_t, size_t> insertFiltered(const LoamFeatures<PointType, Alloc>& more, const Pose3d& world_T_scan, double edge_leaf,
+                                           double planar_leaf) {
+    const std::vector<double> e = gpu::pack<Accessor>(more.edge_points), p = gpu::pack<Accessor>(more.planar_points);
+    double pose[7];
+    world_T_scan.toArray(pose);
+    size_t ne = 0, np = 0;
+    gpu::check(gpu::defaultContext(),
+               loamx_target_index_insert_filtered(gpu::defaultContext(), handle_.get(), e.data(), more.edge_points.size(), p.data(),
+                                                  more.planar_points.size(), pose, edge_leaf, planar_leaf, &ne, &np));
+    return {ne, np};
+  }
+  /// Keeps the points with lo <= p <= hi on every axis (the local window around the vehicle); the index afterwards is the
+  /// one `build` gives for the survivors in their order. Returns the points removed {edge, planar}.
+  std::pair<size_t, size_t> crop(const Vector3d& lo, const Vector3d& hi) {
+    const double l[3] = {lo(0), lo(1), lo(2)}, h[3] = {hi(0), hi(1), hi(2)};
+    size_t ne = 0, np = 0;
+    gpu::check(gpu::defaultContext(), loamx_target_index_crop(gpu::defaultContext(), handle_.get(), l, h, &ne, &np));
+    return {ne, np};
+  }
+  /// The map's points in index order (read back from the device); the *Rows forms return them packed row-major (n x 3).
+  std::vector<double> edgePointRows() const { return pointRows(0); }
+  std::vector<double> planarPointRows() const { return pointRows(1); }
+  std::vector<Vector3d> edgePoints() const { return unpack(pointRows(0)); }
+  std::vector<Vector3d> planarPoints() const { return unpack(pointRows(1)); }
   size_t numEdgePoints() const {
     size_t n = 0;
     loamx_target_index_size(handle_.get(), &n, nullptr);
@@ -142,21 +185,36 @@ class TargetIndex {
  private:
   explicit TargetIndex(loamx_target_index* h)
       : handle_(h, [](loamx_target_index* p) { loamx_target_index_destroy(gpu::defaultContext(), p); }) {}
+  std::vector<double> pointRows(int which_set) const {
+    const size_t n = which_set ? numPlanarPoints() : numEdgePoints();
+    std::vector<double> xyz(3 * n);
+    gpu::check(gpu::defaultContext(), loamx_target_index_points(gpu::defaultContext(), handle_.get(), which_set, 0, n, xyz.data()));
+    return xyz;
+  }
+  static std::vector<Vector3d> unpack(const std::vector<double>& xyz) {
+    std::vector<Vector3d> out;
+    out.reserve(xyz.size() / 3);
+    for (size_t i = 0; i + 2 < xyz.size(); i += 3) out.emplace_back(xyz[i], xyz[i + 1], xyz[i + 2]);
+    return out;
+  }
   std::shared_ptr<loamx_target_index> handle_;
 };
 
 /// registerFeatures against a prebuilt TargetIndex (params must carry the neighbour radii the index was built with)
 template <template <typename> class Accessor = FieldAccessor, typename PointType, template <typename> class Alloc>
 Pose3d registerFeatures(const LoamFeatures<PointType, Alloc>& source, const TargetIndex& target,
-                        const Pose3d& target_T_source_init, const RegistrationParams& params = RegistrationParams()) {
+                        const Pose3d& target_T_source_init, const RegistrationParams& params = RegistrationParams(),
+                        std::shared_ptr<RegistrationDetail> detail = nullptr) {
   loamx_ctx* ctx = gpu::defaultContext();
   const std::vector<double> se = gpu::pack<Accessor>(source.edge_points), sp = gpu::pack<Accessor>(source.planar_points);
   const loamx_reg_params rp = gpu::toC(params);
   double init[7];
   target_T_source_init.toArray(init);
   loamx_reg_result result{};
+  gpu::DetailCapture capture(detail, source.edge_points.size(), source.planar_points.size(), params.max_iterations);
   gpu::check(ctx, loamx_register_features_indexed(ctx, target.handle(), se.data(), source.edge_points.size(), sp.data(),
-                                                  source.planar_points.size(), init, &rp, &result, nullptr));
+                                                  source.planar_points.size(), init, &rp, &result, capture.arg()));
+  capture.finish(result);
   return Pose3d::fromArray(result.pose);
 }
 

@@ -179,7 +179,7 @@ int loamx_ctx_last_extract_route(loamx_ctx* ctx, uint32_t* bits);
  * curvatures computed from them; a NaN range passes every comparison of loam/src/features.cpp:30-68; nanoflann and Ceres
  * receive them as they are). Here: every HOST entry point (loamx_compute_curvature / _valid_points, loamx_extract_features,
  * loamx_register_features / _indexed, loamx_register_scan_pairs, loamx_register_scan_sequence, loamx_associate, loamx_fit_lines / _planes, loamx_knn_search, loamx_target_index_create /
- * _insert, and their _f32 forms) refuses such input with LOAMX_ERR_BAD_PARAM: its uploaded copy is looked at by one small
+ * _insert / _insert_filtered (points and pose), and their _f32 forms) refuses such input with LOAMX_ERR_BAD_PARAM: its uploaded copy is looked at by one small
  * kernel before anything else is launched (a 4-byte read-back, one extra stream synchronisation; an index is left as it was). The "_dev" entry points (loamx_extract_features_batch_dev, loamx_register_features_batch_dev,
  * loamx_register_scan_pairs_dev, loamx_register_scan_sequence_dev, and their _f32 forms) do not look unless the context option CHECK_FINITE is set: then one
  * small kernel and a 4-byte read-back precede the call (it synchronises) and non-finite input is refused the same way.
@@ -248,6 +248,50 @@ int loamx_register_features_indexed(loamx_ctx* ctx, const loamx_target_index* in
                                     size_t n_src_edge, const double* src_planar, size_t n_src_planar,
                                     const double init_pose[7], const loamx_reg_params* reg, loamx_reg_result* result,
                                     loamx_reg_detail* detail);
+
+/* ---- map upkeep (no reference counterpart: the reference registers scan to scan and leaves the map to its users). What a
+ * LOAM mapper does after every registration, on the device: move the scan's features into the map frame, thin them on a
+ * voxel grid so that a slow or standing vehicle does not pile points into the same cells, add them, and drop what has left
+ * the local window.
+ *   transform  p' = pose.act(p) with the arithmetic of the association's *_moved (Pose3d::act; the quaternion is used as given,
+ *              not normalised). An identity pose (NULL, or exactly {0,0,0,1,0,0,0}) returns the input bit for bit.
+ *   voxel      v[c] = floor(p'[c] / leaf) (an IEEE FP64 division, so a point on a voxel face lands where numpy.floor(p / leaf)
+ *              puts it); |v[c]| < 2^20; key = (v.x + 2^20) << 42 | (v.y + 2^20) << 21 | (v.z + 2^20).
+ *   kept set   of all points of a call that share a voxel the one with the LOWEST input index is kept — for an index, only if
+ *              no point of the map lies in that voxel; the kept points leave in input order. The result does not depend on
+ *              how the threads are scheduled: two runs give the same bytes. */
+
+/* Points first .. first + count - 1 of one set (which_set: 0 edge, 1 planar) in index order, to HOST memory. first + count
+ * beyond the set: LOAMX_ERR_BAD_PARAM; count == 0: LOAMX_OK. */
+int loamx_target_index_points(loamx_ctx* ctx, const loamx_target_index* index, int which_set, size_t first, size_t count,
+                              double* xyz_out);
+/* Transform + voxel filter of n DEVICE points; pose: HOST pointer, NULL = identity. d_n_out: the number kept; d_xyz_out[j]
+ * (room for n points): the j-th kept point, transformed; d_src_idx[j] (n entries, may be NULL): its input index; entries past
+ * the count are unspecified. leaf <= 0: no filter — every point is kept and the call is the transform alone. Otherwise a
+ * point with a non-finite coordinate or a voxel coordinate out of range is dropped. d_xyz_out == d_xyz, a NaN leaf or a
+ * non-finite pose: LOAMX_ERR_BAD_PARAM (any other overlap is undefined); n == 0 writes a zero count. Asynchronous on the
+ * context's stream. */
+int loamx_voxel_filter_dev(loamx_ctx* ctx, const double* d_xyz, size_t n, const double pose[7], double leaf, double* d_xyz_out,
+                           uint32_t* d_src_idx, uint32_t* d_n_out);
+/* loamx_target_index_insert of the points the voxel filter keeps: p' = world_T_scan.act(p) (NULL = identity) is added unless
+ * its voxel already holds a point of the map — however that point got there: at create, by a plain or by a filtered insert;
+ * judged at this call's leaf — or an earlier point of this call. The index afterwards is, byte for byte, what
+ * loamx_target_index_insert of exactly the kept points makes of it (merges, rebuilds and the counters of
+ * loamx_target_index_stats included); a kind to which the call adds nothing is left alone. A kind whose leaf is <= 0 is
+ * transformed and inserted unfiltered. n_*_added (either may be NULL): points added per kind. Non-finite points or pose, or
+ * a NaN leaf: LOAMX_ERR_BAD_PARAM; a point (of the call, or of the map at this leaf) whose voxel is out of range:
+ * LOAMX_ERR_UNSUPPORTED; the index stays as it was. Each kind keeps an occupancy table (12 B per slot, 2 - 6 slots per map
+ * point) built by the first filtered insert, so later calls hash the new points only; it is built again when the leaf
+ * differs from the last call's, when the map has outgrown it, and after a crop. */
+int loamx_target_index_insert_filtered(loamx_ctx* ctx, loamx_target_index* index, const double* edge, size_t n_edge,
+                                       const double* planar, size_t n_planar, const double world_T_scan[7], double edge_leaf,
+                                       double planar_leaf, size_t* n_edge_added, size_t* n_planar_added);
+/* Keeps the points with lo[c] <= p[c] <= hi[c] for c = x, y, z; the survivors keep their relative order, and the index
+ * afterwards equals one created over them. A kind that loses points is rebuilt (counted as a full build), a kind that loses
+ * none is not touched; a kind may become empty. n_*_removed: either may be NULL. lo[c] > hi[c] or a NaN bound:
+ * LOAMX_ERR_BAD_PARAM; infinite bounds are allowed. */
+int loamx_target_index_crop(loamx_ctx* ctx, loamx_target_index* index, const double lo[3], const double hi[3],
+                            size_t* n_edge_removed, size_t* n_planar_removed);
 
 /* ---- rows a16-a19 one by one (round 3): the reference's internal functions behind registerFeatures, callable from the
  * host. Same device functions the association kernels run; used by the header shim's geometry_internal / kdtree_internal

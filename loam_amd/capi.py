@@ -97,6 +97,7 @@ EXPORTS = [
     "loamx_fit_lines", "loamx_fit_planes", "loamx_knn_search", "loamx_associate", "loamx_target_index_stats",
     "loamx_register_scan_sequence_dev", "loamx_register_scan_sequence_dev_f32", "loamx_register_scan_sequence",
     "loamx_register_scan_sequence_f32", "loamx_compose_trajectory_dev", "loamx_deskew_scans_dev", "loamx_deskew_scans_dev_f32",
+    "loamx_target_index_points", "loamx_voxel_filter_dev", "loamx_target_index_insert_filtered", "loamx_target_index_crop",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -170,6 +171,11 @@ def load(build_if_missing=True):
     lib.loamx_target_index_insert.argtypes = [vp, vp, dp, C.c_size_t, dp, C.c_size_t]
     lib.loamx_target_index_size.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     lib.loamx_target_index_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.loamx_target_index_points.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, dp]
+    lib.loamx_voxel_filter_dev.argtypes = [vp, vp, C.c_size_t, dp, C.c_double, vp, vp, vp]
+    lib.loamx_target_index_insert_filtered.argtypes = [vp, vp, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_double, C.c_double,
+                                                       C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    lib.loamx_target_index_crop.argtypes = [vp, vp, dp, dp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     lib.loamx_target_index_destroy.argtypes = [vp, vp]
     lib.loamx_target_index_destroy.restype = None
     lib.loamx_register_features_indexed.argtypes = [vp, vp, dp, C.c_size_t, dp, C.c_size_t, dp, C.POINTER(RegistrationParams),
@@ -548,6 +554,67 @@ class Context:
         a, b = C.c_uint64(0), C.c_uint64(0)
         self._check(self.lib.loamx_target_index_stats(index, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # ---- map upkeep: voxel-filtered insert, crop, read-back (include/loamx.h, "map upkeep") ----------------
+    @staticmethod
+    def _pose_arg(pose):
+        """None (identity) or a contiguous pose7 -> what the C ABI takes (keep the array alive during the call)"""
+        if pose is None:
+            return None, None
+        p = np.ascontiguousarray(pose, dtype=np.float64)
+        if p.size != 7:
+            raise ValueError("a pose has 7 values: qx, qy, qz, qw, tx, ty, tz")
+        return p, _dp(p)
+
+    def target_index_points(self, index, which_set, first=0, count=None):
+        """the points of one set (0 edge, 1 planar) in index order, as an (n, 3) array"""
+        if count is None:
+            count = self.target_index_size(index)[which_set] - first
+        out = np.empty((max(int(count), 0), 3))
+        self._check(self.lib.loamx_target_index_points(self.h, index, which_set, first, count, _dp(out)))
+        return out
+
+    def voxel_filter_dev(self, d_xyz, n, leaf, d_xyz_out, d_n_out, d_src_idx=0, pose=None):
+        """transform + voxel filter of n device points (loamx_voxel_filter_dev); asynchronous on the context's stream"""
+        keep, p = self._pose_arg(pose)
+        self._check(self.lib.loamx_voxel_filter_dev(self.h, d_xyz or None, n, p, float(leaf), d_xyz_out or None, d_src_idx or None, d_n_out))
+
+    def voxel_filter(self, points, leaf, pose=None):
+        """Host convenience: uploads the points, runs voxel_filter_dev and returns (kept points (m, 3), src_idx (m,))."""
+        pts = _pts(points)
+        n = len(pts)
+        d_in, d_out, d_idx, d_n = self.alloc(max(pts.nbytes, 8)), self.alloc(max(pts.nbytes, 8)), self.alloc(max(4 * n, 8)), self.alloc(8)
+        try:
+            if n:
+                d_in.upload(pts)
+            self.voxel_filter_dev(d_in.ptr, n, leaf, d_out.ptr, d_n.ptr, d_idx.ptr, pose)
+            self.synchronize()
+            m = int(d_n.download(np.uint32, 1)[0])
+            if m == 0:
+                return np.empty((0, 3)), np.empty(0, dtype=np.uint32)
+            return d_out.download(np.float64, 3 * m).reshape(-1, 3), d_idx.download(np.uint32, m)
+        finally:
+            for b in (d_in, d_out, d_idx, d_n):
+                b.free()
+
+    def target_index_insert_filtered(self, index, edge, planar, pose=None, edge_leaf=0.2, planar_leaf=0.4):
+        """Adds pose.act(point) for every point whose voxel (edge_leaf / planar_leaf; <= 0: unfiltered) holds neither a
+        point of the map nor an earlier point of this call. Returns (n_edge_added, n_planar_added)."""
+        e, p = _pts(edge), _pts(planar)
+        keep, pp = self._pose_arg(pose)
+        ne, npl = C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.loamx_target_index_insert_filtered(self.h, index, _dp(e), len(e), _dp(p), len(p), pp, float(edge_leaf),
+                                                                float(planar_leaf), C.byref(ne), C.byref(npl)))
+        return ne.value, npl.value
+
+    def target_index_crop(self, index, lo, hi):
+        """Keeps the points inside the box [lo, hi] (inclusive). Returns (edge points removed, planar points removed)."""
+        lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+        if lo.size != 3 or hi.size != 3:
+            raise ValueError("target_index_crop: lo and hi have 3 values each")
+        ne, npl = C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.loamx_target_index_crop(self.h, index, _dp(lo), _dp(hi), C.byref(ne), C.byref(npl)))
+        return ne.value, npl.value
 
     def target_index_destroy(self, index):
         self.lib.loamx_target_index_destroy(self.h, index)

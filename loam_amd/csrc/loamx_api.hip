@@ -16,6 +16,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: the library itself is opened on first use (struct Rccl below)
 
 #include "loamx_internal.h"
+#include "map_math.h"
 #include "synth.h"
 
 using namespace loamx;
@@ -27,13 +28,14 @@ enum WsId {
   WS_SORT_SCRATCH, WS_SORT_SCRATCH_SRC, WS_NASSOC, WS_STATE, WS_PARTIALS, WS_MOM_PARTIALS, WS_MOMENTS, WS_FLAGGED_LIST, WS_FLAGGED_COUNT,
   WS_LINE_TOT, WS_EXTRACT_EVENTS, WS_BOX, WS_FINITE_FLAG, WS_COUNTERS, WS_ITERINFO, WS_STREAM_IN0, WS_STREAM_IN1, WS_STREAM_RES,
   WS_FIT_IN, WS_FIT_OUT, WS_FCOUNTS, WS_RESULTS, WS_INIT, WS_STREAM_INIT,
+  WS_VOX_TABLE, WS_MAP_WORDS,
   WS_COUNT
 };
 // the buffers that exist once per feature kind: loamx_ctx::wsk[id][kEdge | kPlane]
 enum WsKindId {
   WSK_STAGE = 0, WSK_CNT, WSK_IDX, WSK_N, WSK_XYZ,
   WSK_GRID_DESC, WSK_CELLS, WSK_SORTED, WSK_REL, WSK_SGRID_DESC, WSK_SCELLS, WSK_SSORTED, WSK_ASSOC, WSK_NN, WSK_RNN, WSK_NEAREST,
-  WSK_REST, WSK_EXACT, WSK_DUMP, WSK_SRC, WSK_TGT,
+  WSK_REST, WSK_EXACT, WSK_DUMP, WSK_SRC, WSK_TGT, WSK_MAP_TMP, WSK_MAP_OUT,
   WSK_COUNT
 };
 
@@ -106,6 +108,13 @@ struct loamx_target_index {
   size_t n_at_build[2] = {0, 0};
   bool grid_valid[2] = {false, false};  // the kind's cell-sorted arrays + table describe idx->pts[k][0 .. n[k]) (full build or merges since)
   uint64_t full_builds = 0, merges = 0;  // per kind: a call that rebuilds both kinds counts two
+  // occupancy table of the filtered insert, one per kind (loamx_internal.h: VoxelTable; built by the first filtered insert).
+  // While vox_valid[k]: owner[slot] = lowest index in pts[k] of any point of that voxel at leaf vox_leaf[k], over the
+  // points [0, vox_n[k]) — plain inserts leave vox_n behind n, the next filtered insert catches up.
+  VoxelTable vox[2] = {{nullptr, nullptr, 0u}, {nullptr, nullptr, 0u}};
+  double vox_leaf[2] = {0, 0};
+  size_t vox_n[2] = {0, 0};
+  bool vox_valid[2] = {false, false};
 };
 
 namespace loamx {
@@ -1342,6 +1351,10 @@ void index_free(loamx_target_index* idx) {
     if (idx->sorted2[k]) (void)hipFree(idx->sorted2[k]);
     if (idx->rel2[k]) (void)hipFree(idx->rel2[k]);
   }
+  for (int k = 0; k < 2; k++) {
+    if (idx->vox[k].keys) (void)hipFree(idx->vox[k].keys);
+    if (idx->vox[k].owner) (void)hipFree(idx->vox[k].owner);
+  }
   if (idx->counts) (void)hipFree(idx->counts);
   if (idx->scratch) (void)hipFree(idx->scratch);
   delete idx;
@@ -1450,27 +1463,29 @@ bool index_can_merge(const loamx_target_index* idx, int k, size_t add) {
          (n_new > 200000) == (idx->cells_cap[k] != 0u);
 }
 
-int index_append(loamx_ctx* ctx, loamx_target_index* idx, const double* edge, size_t n_e, const double* planar, size_t n_p) {
-  const double* host[2] = {edge, planar};
-  const size_t add[2] = {n_e, n_p};
+// First half of an insert: the new points go to a staging buffer (stage[k]: device pointers) and are looked at there
+// (loamx.h: "Non-finite input"): a refused insert must leave the index as it was, and making room (index_reserve) already
+// re-allocates its arrays.
+int index_stage(loamx_ctx* ctx, const loamx_target_index* idx, const double* const host[2], const size_t add[2], double* stage[2]) {
   for (int k = 0; k < 2; k++) {
     if (idx->n[k] + add[k] > 0x0FFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "feature set too large");
     if (add[k] && !host[k]) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null point array");
   }
   hipStream_t s = ctx->stream;
-  // The new points go to a staging buffer first and are looked at there (loamx.h: "Non-finite input"): a refused insert must
-  // leave the index as it was, and making room (index_reserve) already re-allocates its arrays.
   ENSURE(ctx, WS_FIT_IN, (add[0] + add[1] ? add[0] + add[1] : 1) * 24);
-  double* stage[2] = {wsp<double>(ctx, WS_FIT_IN), wsp<double>(ctx, WS_FIT_IN) + add[0] * 3};
-  {
-    for (int k = 0; k < 2; k++)
-      if (add[k]) HIP_TRY(ctx, hipMemcpyAsync(stage[k], host[k], add[k] * 24, hipMemcpyHostToDevice, s));
-    int rc = finite_begin(ctx);
-    if (rc != LOAMX_OK) return rc;
-    for (int k = 0; k < 2; k++) finite_add(ctx, stage[k], false, nullptr, 1, add[k], 1);
-    rc = finite_end(ctx);
-    if (rc != LOAMX_OK) return rc;
-  }
+  stage[0] = wsp<double>(ctx, WS_FIT_IN), stage[1] = wsp<double>(ctx, WS_FIT_IN) + add[0] * 3;
+  for (int k = 0; k < 2; k++)
+    if (add[k]) HIP_TRY(ctx, hipMemcpyAsync(stage[k], host[k], add[k] * 24, hipMemcpyHostToDevice, s));
+  int rc = finite_begin(ctx);
+  if (rc != LOAMX_OK) return rc;
+  for (int k = 0; k < 2; k++) finite_add(ctx, stage[k], false, nullptr, 1, add[k], 1);
+  return finite_end(ctx);
+}
+
+// Second half: appends add[k] staged DEVICE points (finite, at most 0x0FFFFFFF with the set) to each kind — the uploaded
+// points of the plain insert, or what the voxel filter kept of them.
+int index_append_staged(loamx_ctx* ctx, loamx_target_index* idx, const double* const stage[2], const size_t add[2]) {
+  hipStream_t s = ctx->stream;
   for (int k = 0; k < 2; k++) {  // all the room first: a failed allocation leaves the index as it was
     int rc = index_reserve(ctx, idx, k, add[k]);
     if (rc != LOAMX_OK) return rc;
@@ -1549,6 +1564,97 @@ int index_append(loamx_ctx* ctx, loamx_target_index* idx, const double* edge, si
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return LOAMX_OK;
 }
+
+int index_append(loamx_ctx* ctx, loamx_target_index* idx, const double* edge, size_t n_e, const double* planar, size_t n_p) {
+  const double* const host[2] = {edge, planar};
+  const size_t add[2] = {n_e, n_p};
+  double* stage[2];
+  int rc = index_stage(ctx, idx, host, add, stage);
+  if (rc != LOAMX_OK) return rc;
+  return index_append_staged(ctx, idx, stage, add);
+}
+
+/* ---- map upkeep (loamx.h): voxel-filtered insert, crop, read-back ----------------------------------------------------- */
+const char* const kVoxelRangeMsg = "a point's voxel coordinate floor(p / leaf) is outside (-2^20, 2^20)";
+
+bool pose_finite(const double* pose) { return !pose || host_all_finite(pose, false, 7); }
+// the pose the launchers take: nullptr for the identity (given as NULL or exactly {0,0,0,1,0,0,0}), so that nothing is computed
+const double* pose_or_null(const double* pose) { return pose && !pose_is_identity(pose) ? pose : nullptr; }
+
+// the flag words + the two kept counts of one call: [0, kMapFlagWords) flags, then one count per kind
+int map_words_begin(loamx_ctx* ctx, uint32_t** words) {
+  ENSURE(ctx, WS_MAP_WORDS, (kMapFlagWords + 2) * sizeof(uint32_t));
+  *words = wsp<uint32_t>(ctx, WS_MAP_WORDS);
+  untimed(ctx);
+  HIP_TRY(ctx, hipMemsetAsync(*words, 0, (kMapFlagWords + 2) * sizeof(uint32_t), ctx->stream));
+  return LOAMX_OK;
+}
+// the one read-back of a call (synchronises); returns the host copy in the pinned area
+int map_words_end(loamx_ctx* ctx, const uint32_t* words, const uint32_t** host) {
+  uint32_t* h = &ctx->h_pinned[40];
+  HIP_TRY(ctx, hipMemcpyAsync(h, words, (kMapFlagWords + 2) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *host = h;
+  return LOAMX_OK;
+}
+
+// scratch of one filter / crop pass over n points, carved out of one buffer
+struct MapTmp {
+  double* moved;    // [n][3] transformed points
+  uint32_t* slot;   // [n]
+  uint32_t* tiles;  // map_compact_ws_bytes(n)
+  uint8_t* keep;    // [n]
+};
+size_t map_tmp_bytes(size_t n) { return n * 24 + ((n * 4 + 7) & ~(size_t)7) + ((map_compact_ws_bytes(n) + 7) & ~(size_t)7) + n; }
+MapTmp map_tmp_carve(void* base, size_t n) {
+  unsigned char* p = static_cast<unsigned char*>(base);
+  MapTmp t;
+  t.moved = reinterpret_cast<double*>(p), p += n * 24;
+  t.slot = reinterpret_cast<uint32_t*>(p), p += (n * 4 + 7) & ~(size_t)7;
+  t.tiles = reinterpret_cast<uint32_t*>(p), p += (map_compact_ws_bytes(n) + 7) & ~(size_t)7;
+  t.keep = p;
+  return t;
+}
+uint32_t voxel_table_log2(size_t slots_min) {
+  uint32_t l = 4;
+  while (((size_t)1 << l) < slots_min) l++;
+  return l;
+}
+
+// Brings kind k's occupancy table to "describes pts[k][0, n[k]) at `leaf`, with room for n_add more points below half
+// load". (Re)built from the map's own points when there is none, after a crop or a failed call (vox_valid), when the leaf
+// differs from the last call's or when the points would pass half of the slots; otherwise caught up with the points plain
+// inserts have added since. A map point without a voxel at this leaf raises kMapFlagBadMapPoint.
+int index_voxel_table(loamx_ctx* ctx, loamx_target_index* idx, int k, double leaf, size_t n_add, uint32_t* d_flags) {
+  hipStream_t s = ctx->stream;
+  VoxelTable& t = idx->vox[k];
+  const size_t points = idx->n[k] + n_add;
+  const bool fits = t.keys && (((size_t)1 << t.log2_cap) >= 2 * points);
+  if (!fits || !idx->vox_valid[k] || idx->vox_leaf[k] != leaf || idx->vox_n[k] > idx->n[k]) {
+    if (!fits) {  // 3 x the points, rounded up to a power of two: the map grows by half before the next rebuild at the earliest
+      HIP_TRY(ctx, hipStreamSynchronize(s));
+      if (t.keys) (void)hipFree(t.keys);
+      if (t.owner) (void)hipFree(t.owner);
+      t.keys = nullptr, t.owner = nullptr, idx->vox_valid[k] = false;
+      t.log2_cap = voxel_table_log2(3 * points);
+      if (hipMalloc(reinterpret_cast<void**>(&t.keys), sizeof(unsigned long long) << t.log2_cap) != hipSuccess ||
+          hipMalloc(reinterpret_cast<void**>(&t.owner), sizeof(uint32_t) << t.log2_cap) != hipSuccess) {
+        if (t.keys) (void)hipFree(t.keys);
+        t.keys = nullptr, t.owner = nullptr;
+        return fail(ctx, LOAMX_ERR_HIP, "hipMalloc failed for the occupancy table");
+      }
+    }
+    HIP_TRY(ctx, hipMemsetAsync(t.keys, 0xFF, sizeof(unsigned long long) << t.log2_cap, s));
+    HIP_TRY(ctx, hipMemsetAsync(t.owner, 0xFF, sizeof(uint32_t) << t.log2_cap, s));
+    idx->vox_leaf[k] = leaf, idx->vox_n[k] = 0, idx->vox_valid[k] = true;
+  }
+  if (idx->vox_n[k] < idx->n[k]) {
+    launch_voxel_claim(idx->pts[k] + idx->vox_n[k] * 3, (uint32_t)(idx->n[k] - idx->vox_n[k]), nullptr, leaf, t, (uint32_t)idx->vox_n[k], nullptr,
+                       nullptr, d_flags, kMapFlagBadMapPoint, s);
+    idx->vox_n[k] = idx->n[k];
+  }
+  return LOAMX_OK;
+}
 }  // namespace
 
 void loamx_target_index_destroy(loamx_ctx* ctx, loamx_target_index* index) {
@@ -1604,6 +1710,178 @@ int loamx_target_index_size(const loamx_target_index* index, size_t* n_edge, siz
   if (n_edge) *n_edge = index->n[0];
   if (n_planar) *n_planar = index->n[1];
   return LOAMX_OK;
+}
+
+/* ---- map upkeep ------------------------------------------------------------------------------------------------------ */
+int loamx_target_index_points(loamx_ctx* ctx, const loamx_target_index* index, int which_set, size_t first, size_t count, double* xyz_out) {
+  if (!ctx || !index) return LOAMX_ERR_BAD_PARAM;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (which_set != 0 && which_set != 1) return fail(ctx, LOAMX_ERR_BAD_PARAM, "which_set: 0 = edge points, 1 = planar points");
+  const size_t n = index->n[which_set];
+  if (first > n || count > n - first) return fail(ctx, LOAMX_ERR_BAD_PARAM, "first + count lies beyond the set");
+  if (count == 0) return LOAMX_OK;
+  if (!xyz_out) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  untimed(ctx);
+  HIP_TRY(ctx, hipMemcpyAsync(xyz_out, index->pts[which_set] + first * 3, count * 24, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return LOAMX_OK;
+}
+
+int loamx_voxel_filter_dev(loamx_ctx* ctx, const double* d_xyz, size_t n, const double pose[7], double leaf, double* d_xyz_out,
+                           uint32_t* d_src_idx, uint32_t* d_n_out) {
+  if (!ctx) return LOAMX_ERR_BAD_PARAM;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!d_n_out || (n && (!d_xyz || !d_xyz_out))) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  if (n && d_xyz_out == d_xyz) return fail(ctx, LOAMX_ERR_BAD_PARAM, "the voxel filter does not work in place");
+  if (leaf != leaf) return fail(ctx, LOAMX_ERR_BAD_PARAM, "leaf is NaN");
+  if (!pose_finite(pose)) return fail(ctx, LOAMX_ERR_BAD_PARAM, "non-finite pose");
+  if (n > 0x0FFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "too many points in one call");
+  hipStream_t s = ctx->stream;
+  const double* P = pose_or_null(pose);
+  untimed(ctx);
+  if (leaf <= 0.0 || n == 0) {  // the transform alone (n == 0: the zero count)
+    launch_map_transform(d_xyz, (uint32_t)n, P, d_xyz_out, d_src_idx, d_n_out, nullptr, s);
+    CHECK_LAUNCH(ctx, "map_transform_kernel");
+    return LOAMX_OK;
+  }
+  // call-local table (at most half full: 2 n slots or more) and scratch in the workspace. Dropped points (non-finite, or
+  // out of range) only raise words nobody waits for here: the call does not synchronise.
+  uint32_t* words = nullptr;
+  int rc = map_words_begin(ctx, &words);
+  if (rc != LOAMX_OK) return rc;
+  VoxelTable t{nullptr, nullptr, voxel_table_log2(2 * n)};
+  const size_t slots = (size_t)1 << t.log2_cap;
+  ENSURE(ctx, WS_VOX_TABLE, slots * 12);
+  ENSURE(ctx, ctx->wsk[WSK_MAP_TMP][0], map_tmp_bytes(n));
+  t.keys = wsp<unsigned long long>(ctx, WS_VOX_TABLE), t.owner = reinterpret_cast<uint32_t*>(t.keys + slots);
+  const MapTmp tmp = map_tmp_carve(ctx->wsk[WSK_MAP_TMP][0].p, n);
+  HIP_TRY(ctx, hipMemsetAsync(t.keys, 0xFF, slots * 12, s));
+  launch_voxel_claim(d_xyz, (uint32_t)n, P, leaf, t, 0u, tmp.moved, tmp.slot, words, kMapFlagBadPoint, s);
+  launch_voxel_keep(t, tmp.slot, (uint32_t)n, 0u, tmp.keep, s);
+  launch_map_compact(tmp.moved, tmp.keep, (uint32_t)n, tmp.tiles, d_xyz_out, d_src_idx, d_n_out, nullptr, nullptr, 0u, s);
+  CHECK_LAUNCH(ctx, "voxel filter kernels");
+  return LOAMX_OK;
+}
+
+int loamx_target_index_insert_filtered(loamx_ctx* ctx, loamx_target_index* index, const double* edge, size_t n_edge, const double* planar,
+                                       size_t n_planar, const double world_T_scan[7], double edge_leaf, double planar_leaf, size_t* n_edge_added,
+                                       size_t* n_planar_added) {
+  if (!ctx || !index) return LOAMX_ERR_BAD_PARAM;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (n_edge_added) *n_edge_added = 0;
+  if (n_planar_added) *n_planar_added = 0;
+  if (edge_leaf != edge_leaf || planar_leaf != planar_leaf) return fail(ctx, LOAMX_ERR_BAD_PARAM, "leaf is NaN");
+  if (!pose_finite(world_T_scan)) return fail(ctx, LOAMX_ERR_BAD_PARAM, kNonFiniteMsg);
+  if (n_edge == 0 && n_planar == 0) return LOAMX_OK;
+  loamx_target_index* idx = index;
+  const double* const host[2] = {edge, planar};
+  const size_t add[2] = {n_edge, n_planar};
+  const double leaf[2] = {edge_leaf, planar_leaf};
+  double* stage[2];
+  int rc = index_stage(ctx, idx, host, add, stage);
+  if (rc != LOAMX_OK) return rc;
+  hipStream_t s = ctx->stream;
+  const double* P = pose_or_null(world_T_scan);
+  uint32_t* words = nullptr;
+  rc = map_words_begin(ctx, &words);
+  if (rc != LOAMX_OK) return rc;
+  // both kinds are filtered into the workspace before anything is read back: the index itself is not touched until the
+  // one read-back below has shown that the call goes through
+  double* out[2] = {nullptr, nullptr};
+  for (int k = 0; k < 2; k++) {  // (all the room first: nothing below leaves early with claims in a table)
+    if (!add[k]) continue;
+    ENSURE(ctx, ctx->wsk[WSK_MAP_OUT][k], add[k] * 24);
+    if (leaf[k] > 0.0) ENSURE(ctx, ctx->wsk[WSK_MAP_TMP][k], map_tmp_bytes(add[k]));
+  }
+  for (int k = 0; k < 2; k++) {
+    if (!add[k]) continue;
+    out[k] = wskp<double>(ctx, WSK_MAP_OUT, k);
+    if (leaf[k] <= 0.0) {  // transformed, unfiltered
+      launch_map_transform(stage[k], (uint32_t)add[k], P, out[k], nullptr, words + kMapFlagWords + k, words, s);
+      continue;
+    }
+    const MapTmp tmp = map_tmp_carve(ctx->wsk[WSK_MAP_TMP][k].p, add[k]);
+    rc = index_voxel_table(ctx, idx, k, leaf[k], add[k], words);
+    if (rc != LOAMX_OK) {
+      idx->vox_valid[0] = idx->vox_valid[1] = false;
+      return rc;
+    }
+    const uint32_t base = (uint32_t)idx->n[k];
+    launch_voxel_claim(stage[k], (uint32_t)add[k], P, leaf[k], idx->vox[k], base, tmp.moved, tmp.slot, words, kMapFlagBadPoint, s);
+    launch_voxel_keep(idx->vox[k], tmp.slot, (uint32_t)add[k], base, tmp.keep, s);
+    launch_map_compact(tmp.moved, tmp.keep, (uint32_t)add[k], tmp.tiles, out[k], nullptr, words + kMapFlagWords + k, &idx->vox[k], tmp.slot, base, s);
+  }
+  rc = check_launch(ctx, "voxel filter kernels");
+  const uint32_t* h = nullptr;
+  if (rc == LOAMX_OK) rc = map_words_end(ctx, words, &h);
+  if (rc == LOAMX_OK && h[kMapFlagGaveUp]) rc = fail(ctx, LOAMX_ERR_HIP, "the occupancy table's probe sequence gave up (table full)");
+  if (rc == LOAMX_OK && (h[kMapFlagBadPoint] || h[kMapFlagBadMapPoint])) rc = fail(ctx, LOAMX_ERR_UNSUPPORTED, kVoxelRangeMsg);
+  if (rc != LOAMX_OK) {  // the tables hold claims of points that were not inserted: built again by the next call
+    idx->vox_valid[0] = idx->vox_valid[1] = false;
+    return rc;
+  }
+  const size_t kept[2] = {add[0] ? h[kMapFlagWords + 0] : 0u, add[1] ? h[kMapFlagWords + 1] : 0u};
+  if (n_edge_added) *n_edge_added = kept[0];
+  if (n_planar_added) *n_planar_added = kept[1];
+  if (kept[0] == 0 && kept[1] == 0) return LOAMX_OK;  // (no voxel was claimed either: the tables describe the map as before)
+  const bool tabled[2] = {kept[0] && leaf[0] > 0.0, kept[1] && leaf[1] > 0.0};
+  for (int k = 0; k < 2; k++)
+    if (tabled[k]) idx->vox_valid[k] = false;  // ... until the points are really in the map
+  rc = index_append_staged(ctx, idx, out, kept);
+  if (rc != LOAMX_OK) return rc;
+  for (int k = 0; k < 2; k++)
+    if (tabled[k]) idx->vox_valid[k] = true, idx->vox_n[k] = idx->n[k];
+  return LOAMX_OK;
+}
+
+int loamx_target_index_crop(loamx_ctx* ctx, loamx_target_index* index, const double lo[3], const double hi[3], size_t* n_edge_removed,
+                            size_t* n_planar_removed) {
+  if (!ctx || !index) return LOAMX_ERR_BAD_PARAM;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (n_edge_removed) *n_edge_removed = 0;
+  if (n_planar_removed) *n_planar_removed = 0;
+  if (!lo || !hi) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  for (int c = 0; c < 3; c++)
+    if (!(lo[c] <= hi[c])) return fail(ctx, LOAMX_ERR_BAD_PARAM, "crop box: lo <= hi on every axis (and no NaN)");
+  loamx_target_index* idx = index;
+  if (idx->n[0] == 0 && idx->n[1] == 0) return LOAMX_OK;
+  hipStream_t s = ctx->stream;
+  uint32_t* words = nullptr;
+  int rc = map_words_begin(ctx, &words);
+  if (rc != LOAMX_OK) return rc;
+  double* out[2] = {nullptr, nullptr};
+  for (int k = 0; k < 2; k++) {
+    const size_t n = idx->n[k];
+    if (!n) continue;
+    ENSURE(ctx, ctx->wsk[WSK_MAP_OUT][k], n * 24);
+    ENSURE(ctx, ctx->wsk[WSK_MAP_TMP][k], map_tmp_bytes(n));
+    out[k] = wskp<double>(ctx, WSK_MAP_OUT, k);
+    const MapTmp tmp = map_tmp_carve(ctx->wsk[WSK_MAP_TMP][k].p, n);
+    launch_crop_keep(idx->pts[k], (uint32_t)n, lo, hi, tmp.keep, s);
+    launch_map_compact(idx->pts[k], tmp.keep, (uint32_t)n, tmp.tiles, out[k], nullptr, words + kMapFlagWords + k, nullptr, nullptr, 0u, s);
+  }
+  CHECK_LAUNCH(ctx, "crop kernels");
+  const uint32_t* h = nullptr;
+  rc = map_words_end(ctx, words, &h);
+  if (rc != LOAMX_OK) return rc;
+  unsigned rebuild = 0u;
+  size_t removed[2] = {0, 0};
+  for (int k = 0; k < 2; k++) {
+    if (!idx->n[k]) continue;
+    const size_t kept = h[kMapFlagWords + k];
+    removed[k] = idx->n[k] - kept;
+    if (!removed[k]) continue;  // (a kind that loses nothing is not touched)
+    if (kept) HIP_TRY(ctx, hipMemcpyAsync(idx->pts[k], out[k], kept * 24, hipMemcpyDeviceToDevice, s));
+    idx->n[k] = kept, idx->grid_valid[k] = false, rebuild |= 1u << k;
+    idx->vox_valid[k] = false;  // (the indices have shifted)
+  }
+  if (n_edge_removed) *n_edge_removed = removed[0];
+  if (n_planar_removed) *n_planar_removed = removed[1];
+  return rebuild ? index_build(ctx, idx, rebuild) : LOAMX_OK;
 }
 
 /* ---- device-resident batch entry points ----------------------------------------------------------- */

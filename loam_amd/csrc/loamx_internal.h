@@ -321,6 +321,28 @@ void launch_deskew(const void* d_xyz, void* d_out, bool f32, size_t n_scans, uin
                    hipStream_t s);
 void launch_trajectory(const loamx_reg_result* d_results, size_t n_pairs, const double origin[7], double* d_world_T_scan, hipStream_t s);
 
+/* ---- map upkeep (map_kernels.hip): voxel filter against an occupancy table, crop, the stable compaction they share --- */
+constexpr uint32_t kMapTile = 256;             // points per tile of the compaction (one workgroup)
+constexpr uint32_t kMapNoSlot = 0xFFFFFFFFu;   // slot of a point that has no voxel (or whose probe gave up)
+// words of the flag array the claim kernel raises (zeroed by the caller, read back by the host entry points)
+enum { kMapFlagGaveUp = 0, kMapFlagBadPoint = 1, kMapFlagBadMapPoint = 2, kMapFlagWords = 4 };
+// Open-addressed occupancy table: 2^log2_cap slots, keys[slot] = voxel key (map_math.h) or all ones (empty), owner[slot] =
+// lowest index of a point in that voxel (all ones before the first claim). Both arrays start as 0xFF bytes.
+struct VoxelTable {
+  unsigned long long* keys;
+  uint32_t* owner;
+  uint32_t log2_cap;
+};
+void launch_voxel_claim(const double* d_pts, uint32_t n, const double* pose, double leaf, const VoxelTable& t, uint32_t base, double* d_moved,
+                        uint32_t* d_slot, uint32_t* d_flags, uint32_t bad_word, hipStream_t s);
+void launch_voxel_keep(const VoxelTable& t, const uint32_t* d_slot, uint32_t n, uint32_t base, uint8_t* d_keep, hipStream_t s);
+void launch_crop_keep(const double* d_pts, uint32_t n, const double lo[3], const double hi[3], uint8_t* d_keep, hipStream_t s);
+void launch_map_transform(const double* d_pts, uint32_t n, const double* pose, double* d_out, uint32_t* d_src_idx, uint32_t* d_n_out,
+                          uint32_t* d_flags, hipStream_t s);
+size_t map_compact_ws_bytes(size_t n);
+void launch_map_compact(const double* d_in, const uint8_t* d_keep, uint32_t n, uint32_t* d_tiles, double* d_out, uint32_t* d_src_idx,
+                        uint32_t* d_total, const VoxelTable* fix, const uint32_t* d_slot, uint32_t owner_base, hipStream_t s);
+
 /* ---- synthetic generator (synth_kernels.hip) --------------------------------------------------- */
 void launch_synth_pairs(uint64_t seed, uint64_t first_pair, size_t n_pairs, uint32_t H, uint32_t W, double sigma,
                         double* d_xyz, hipStream_t s);

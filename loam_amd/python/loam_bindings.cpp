@@ -2,8 +2,9 @@
 // reference's python/loam_bindings.cpp:24-144: LidarParams, Pose3d, Quaterniond,
 // FeatureExtractionParams, LoamFeatures, extractFeatures, computeCurvature, computeValidPoints,
 // RegistrationParams, RegistrationIterationInfo, RegistrationTerminationType, RegistrationDetail,
-// registerFeatures — with the same keyword arguments; plus two extensions the reference does not have, registerScanSequence
-// and deskewScan (include/loamx.h: "scan sequences"). Point clouds are contiguous (N,3) float64
+// registerFeatures — with the same keyword arguments; plus extensions the reference does not have: registerScanSequence
+// and deskewScan (include/loamx.h: "scan sequences"), and the class TargetIndex with a registerFeatures overload that
+// takes it (scan-to-map: "persistent target index" and "map upkeep"). Point clouds are contiguous (N,3) float64
 // arrays handed to the C ABI without per-point objects (a list of 3-vectors is converted once).
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -205,6 +206,29 @@ A deskew_scan(const A& scan, const loam::LidarParams& lp, const loam::Pose3d& mo
   return out;
 }
 
+// (N,3) arrays as feature sets of row views, without copying the coordinates twice
+struct Row {
+  const double* p;
+  double operator()(int i) const { return p[i]; }
+};
+std::vector<Row> to_rows(const Arr& a, const char* what) {
+  const size_t n = check_points(a, what);
+  std::vector<Row> r(n);
+  for (size_t i = 0; i < n; i++) r[i] = Row{a.data() + 3 * i};
+  return r;
+}
+loam::LoamFeatures<Row> to_features(const PyFeatures& f, const char* edge_name, const char* planar_name) {
+  loam::LoamFeatures<Row> out;
+  out.edge_points = to_rows(f.edge_points, edge_name);
+  out.planar_points = to_rows(f.planar_points, planar_name);
+  return out;
+}
+Arr rows_to_array(const std::vector<double>& xyz) {
+  Arr out(std::vector<py::ssize_t>{(py::ssize_t)(xyz.size() / 3), 3});
+  if (!xyz.empty()) std::memcpy(out.mutable_data(), xyz.data(), xyz.size() * sizeof(double));
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(loam_python, m) {
@@ -314,22 +338,8 @@ PYBIND11_MODULE(loam_python, m) {
       "registerFeatures",
       [](const PyFeatures& source, const PyFeatures& target, const loam::Pose3d& init,
          const loam::RegistrationParams& params, std::shared_ptr<loam::RegistrationDetail> detail) {
-        // wrap the (N,3) arrays as feature sets of row views without copying the coordinates twice
-        struct Row {
-          const double* p;
-          double operator()(int i) const { return p[i]; }
-        };
-        auto rows = [](const Arr& a, const char* what) {
-          const size_t n = check_points(a, what);
-          std::vector<Row> r(n);
-          for (size_t i = 0; i < n; i++) r[i] = Row{a.data() + 3 * i};
-          return r;
-        };
-        loam::LoamFeatures<Row> s, t;
-        s.edge_points = rows(source.edge_points, "source.edge_points");
-        s.planar_points = rows(source.planar_points, "source.planar_points");
-        t.edge_points = rows(target.edge_points, "target.edge_points");
-        t.planar_points = rows(target.planar_points, "target.planar_points");
+        const loam::LoamFeatures<Row> s = to_features(source, "source.edge_points", "source.planar_points");
+        const loam::LoamFeatures<Row> t = to_features(target, "target.edge_points", "target.planar_points");
         py::gil_scoped_release release;
         return loam::registerFeatures<loam::ParenAccessor>(s, t, init, params, detail);
       },
@@ -337,6 +347,47 @@ PYBIND11_MODULE(loam_python, m) {
       py::arg("params") = loam::RegistrationParams(), py::arg("detail") = std::shared_ptr<loam::RegistrationDetail>());
 
   // ---- extensions (no counterpart in the reference's module) ----
+  // scan-to-map: a target (local map) whose index stays on the device and is kept up there
+  py::class_<loam::TargetIndex>(m, "TargetIndex")
+      .def(py::init([](const PyFeatures& features, const loam::RegistrationParams& params) {
+             const loam::LoamFeatures<Row> f = to_features(features, "features.edge_points", "features.planar_points");
+             py::gil_scoped_release release;
+             return loam::TargetIndex::build<loam::ParenAccessor>(f, params);
+           }),
+           py::arg("features"), py::arg("params") = loam::RegistrationParams())
+      .def(
+          "insert",
+          [](loam::TargetIndex& t, const PyFeatures& features) {
+            const loam::LoamFeatures<Row> f = to_features(features, "features.edge_points", "features.planar_points");
+            py::gil_scoped_release release;
+            t.insert<loam::ParenAccessor>(f);
+          },
+          py::arg("features"))
+      .def(
+          "insertFiltered",
+          [](loam::TargetIndex& t, const PyFeatures& features, const loam::Pose3d& world_T_scan, double edge_leaf, double planar_leaf) {
+            const loam::LoamFeatures<Row> f = to_features(features, "features.edge_points", "features.planar_points");
+            py::gil_scoped_release release;
+            return t.insertFiltered<loam::ParenAccessor>(f, world_T_scan, edge_leaf, planar_leaf);
+          },
+          py::arg("features"), py::arg("world_T_scan") = loam::Pose3d::Identity(), py::arg("edge_leaf") = 0.2, py::arg("planar_leaf") = 0.4)
+      .def(
+          "crop", [](loam::TargetIndex& t, const Arr& lo, const Arr& hi) { return t.crop(vec_from(lo), vec_from(hi)); }, py::arg("lo"),
+          py::arg("hi"))
+      .def("edgePoints", [](const loam::TargetIndex& t) { return rows_to_array(t.edgePointRows()); })
+      .def("planarPoints", [](const loam::TargetIndex& t) { return rows_to_array(t.planarPointRows()); })
+      .def("numEdgePoints", &loam::TargetIndex::numEdgePoints)
+      .def("numPlanarPoints", &loam::TargetIndex::numPlanarPoints);
+  m.def(
+      "registerFeatures",
+      [](const PyFeatures& source, const loam::TargetIndex& target, const loam::Pose3d& init, const loam::RegistrationParams& params,
+         std::shared_ptr<loam::RegistrationDetail> detail) {
+        const loam::LoamFeatures<Row> s = to_features(source, "source.edge_points", "source.planar_points");
+        py::gil_scoped_release release;
+        return loam::registerFeatures<loam::ParenAccessor>(s, target, init, params, detail);
+      },
+      py::arg("source"), py::arg("target_index"), py::arg("target_T_source_init"), py::arg("params") = loam::RegistrationParams(),
+      py::arg("detail") = std::shared_ptr<loam::RegistrationDetail>());
   m.def("registerScanSequence", &register_scan_sequence<ArrF>, py::arg("scans"), py::arg("lidar_params"),
         py::arg("fe_params") = loam::FeatureExtractionParams(), py::arg("reg_params") = loam::RegistrationParams(),
         py::arg("inits") = py::none());
