@@ -436,11 +436,24 @@ int loamx_compose_trajectory_dev(loamx_ctx* ctx, const loamx_reg_result* d_resul
  * All arithmetic is FP64; the f32 form widens on load and rounds once on store. An identity motion returns the input bit for
  * bit. A point whose three coordinates are all exactly zero (a beam without a return) stays zero and a point with a
  * non-finite coordinate is copied unchanged, so the output is a scan like the input. d_xyz_out may equal d_xyz (in place);
- * any other overlap is undefined. Asynchronous on the context's stream; lidar->min_range / max_range are not used. */
+ * any other overlap is undefined. Asynchronous on the context's stream; lidar->min_range / max_range are not used.
+ * The motion quaternion must have a norm within [1e-150, 1e150] (it need not be a unit quaternion). Outside that range the
+ * squares of its components underflow or overflow; a zero quaternion, or one whose squares underflow to 0, has no direction
+ * and every finite, non-zero point of that scan becomes NaN. This is not checked. */
 int loamx_deskew_scans_dev(loamx_ctx* ctx, const double* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
                            const double* d_motion, double ref_fraction, double* d_xyz_out);
 int loamx_deskew_scans_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
                                const double* d_motion, double ref_fraction, float* d_xyz_out);
+/* Debug / measurement (no reference counterpart, host arithmetic only, no context): the shape of the launch that
+ * loamx_deskew_scans_dev[_f32] makes for n_scans scans of scan_lines x points_per_line points, from the function the launcher
+ * itself calls. Each thread owns one column of one scan and walks a share of the scan lines.
+ *   out[0] column blocks per scan (256 columns each; the last may be narrower)
+ *   out[1] shares the lines of a scan are split into
+ *   out[2] lines per share (the last share holds scan_lines - (out[1] - 1) * out[2] of them)
+ *   out[3] lines a thread keeps in flight (the unroll of its loop; a share that is no multiple of it ends in a remainder)
+ * An empty call (any of the three sizes 0) launches nothing: out[0..2] = 0. LOAMX_ERR_UNSUPPORTED for the sizes the de-skew
+ * entry points refuse, LOAMX_ERR_BAD_PARAM for a null `out`. A test of "the remainder at shape X" asserts its shape from here. */
+int loamx_deskew_launch_geometry(size_t n_scans, uint64_t scan_lines, uint64_t points_per_line, uint32_t out[4]);
 
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are

@@ -3,6 +3,7 @@
 This is host plumbing only: every compute call goes to the HIP kernels through the C ABI. If the
 library is missing it raises; there is no Python or CPU fallback.
 """
+import collections
 import ctypes as C
 import os
 
@@ -97,6 +98,7 @@ EXPORTS = [
     "loamx_fit_lines", "loamx_fit_planes", "loamx_knn_search", "loamx_associate", "loamx_target_index_stats",
     "loamx_register_scan_sequence_dev", "loamx_register_scan_sequence_dev_f32", "loamx_register_scan_sequence",
     "loamx_register_scan_sequence_f32", "loamx_compose_trajectory_dev", "loamx_deskew_scans_dev", "loamx_deskew_scans_dev_f32",
+    "loamx_deskew_launch_geometry",
     "loamx_target_index_points", "loamx_voxel_filter_dev", "loamx_target_index_insert_filtered", "loamx_target_index_crop",
 ]
 
@@ -204,6 +206,7 @@ def load(build_if_missing=True):
     lib.loamx_compose_trajectory_dev.argtypes = [vp, vp, C.c_size_t, dp, vp]
     lib.loamx_deskew_scans_dev.argtypes = [vp, vp, C.c_size_t, C.POINTER(LidarParams), vp, C.c_double, vp]
     lib.loamx_deskew_scans_dev_f32.argtypes = lib.loamx_deskew_scans_dev.argtypes
+    lib.loamx_deskew_launch_geometry.argtypes = [C.c_size_t, C.c_uint64, C.c_uint64, u32p]
     lib.loamx_ctx_enable_kernel_timing.argtypes = [vp, C.c_int]
     lib.loamx_ctx_reset_kernel_stats.argtypes = [vp]
     lib.loamx_ctx_get_kernel_stats.argtypes = [vp, C.POINTER(KernelStat)]
@@ -246,6 +249,19 @@ class LoamxError(RuntimeError):
     def __init__(self, status, message):
         super().__init__(message)
         self.status = status
+
+
+DeskewGeometry = collections.namedtuple("DeskewGeometry", "col_blocks shares lines_per_share unroll")
+
+
+def deskew_launch_geometry(n_scans, scan_lines, points_per_line):
+    """The launch loamx_deskew_scans_dev makes for this batch (loamx_deskew_launch_geometry: the launcher's own function):
+    column blocks of 256 per scan, shares of the lines, lines per share, lines in flight per thread."""
+    v = (C.c_uint32 * 4)()
+    rc = load().loamx_deskew_launch_geometry(n_scans, scan_lines, points_per_line, v)
+    if rc != OK:
+        raise LoamxError(rc, "loamx_deskew_launch_geometry: " + load().loamx_status_string(rc).decode())
+    return DeskewGeometry(*(int(x) for x in v))
 
 
 def _dp(a):

@@ -2169,6 +2169,14 @@ int loamx_deskew_scans_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_scan
                                double ref_fraction, float* d_xyz_out) {
   return deskew_scans_dev(ctx, d_xyz, true, n_scans, lidar, d_motion, ref_fraction, d_xyz_out);
 }
+int loamx_deskew_launch_geometry(size_t n_scans, uint64_t scan_lines, uint64_t points_per_line, uint32_t out[4]) {
+  if (!out) return LOAMX_ERR_BAD_PARAM;
+  if (scan_lines > 0xFFFFFFFFull || points_per_line > 0xFFFFFFFFull || n_scans * ((points_per_line + 255) / 256) > 0x7FFFFFFFull)
+    return LOAMX_ERR_UNSUPPORTED;  // (what deskew_scans_dev refuses)
+  const DeskewGeometry g = deskew_launch_geometry(n_scans, (uint32_t)scan_lines, (uint32_t)points_per_line);
+  out[0] = g.col_blocks, out[1] = g.groups, out[2] = g.lines_per_block, out[3] = g.unroll;
+  return LOAMX_OK;
+}
 
 /* ---- kernel timing ------------------------------------------------------------------------------------ */
 int loamx_ctx_enable_kernel_timing(loamx_ctx* ctx, int enable) {

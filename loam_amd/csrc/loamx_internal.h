@@ -317,6 +317,12 @@ void launch_check_finite(const void* d_pts, bool f32, const uint32_t* d_n, size_
 void launch_check_finite_scalars(const double* d_v, size_t n_scalars, uint32_t* d_flag, hipStream_t s);
 
 /* ---- scan sequences (sequence_kernels.hip): trajectory of the per-pair results, motion correction of scans ------ */
+// column blocks per scan (blockIdx.x = scan * col_blocks + column block), shares of the lines (gridDim.y), lines per share (the
+// last share may hold fewer), lines a thread keeps in flight; all 0 but the last for an empty call
+struct DeskewGeometry {
+  uint32_t col_blocks, groups, lines_per_block, unroll;
+};
+DeskewGeometry deskew_launch_geometry(size_t n_scans, uint32_t H, uint32_t W);
 void launch_deskew(const void* d_xyz, void* d_out, bool f32, size_t n_scans, uint32_t H, uint32_t W, const double* d_motion, double rho,
                    hipStream_t s);
 void launch_trajectory(const loamx_reg_result* d_results, size_t n_pairs, const double origin[7], double* d_world_T_scan, hipStream_t s);

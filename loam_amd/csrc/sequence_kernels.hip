@@ -89,18 +89,28 @@ __global__ __launch_bounds__(64) void trajectory_kernel(const loamx_reg_result* 
 
 }  // namespace
 
+// The shape of the de-skew launch (loamx_deskew_launch_geometry): the one place that decides it.
+// enough workgroups for 256 compute units several times over, also for a single scan: the lines are split as far as
+// that takes (a thread that walks fewer lines amortises its column's sincos over fewer points)
+DeskewGeometry deskew_launch_geometry(size_t n_scans, uint32_t H, uint32_t W) {
+  DeskewGeometry g{0, 0, 0, (uint32_t)kDeskewUnroll};
+  if (n_scans == 0 || H == 0 || W == 0) return g;
+  g.col_blocks = (W + kDeskewThreads - 1) / kDeskewThreads;
+  const size_t wide = (size_t)g.col_blocks * n_scans;
+  uint32_t groups = (uint32_t)((2048 + wide - 1) / wide);
+  groups = groups < 1u ? 1u : (groups > H ? H : groups);
+  g.lines_per_block = (H + groups - 1) / groups;
+  g.groups = (H + g.lines_per_block - 1) / g.lines_per_block;
+  return g;
+}
+
 // d_xyz / d_out: n_scans x H x W x 3 scalars (float when f32); the caller has checked that the grid fits
 void launch_deskew(const void* d_xyz, void* d_out, bool f32, size_t n_scans, uint32_t H, uint32_t W, const double* d_motion, double rho,
                    hipStream_t s) {
   if (n_scans == 0 || H == 0 || W == 0) return;
-  const uint32_t col_blocks = (W + kDeskewThreads - 1) / kDeskewThreads;
-  // enough workgroups for 256 compute units several times over, also for a single scan: the lines are split as far as
-  // that takes (a thread that walks fewer lines amortises its column's sincos over fewer points)
+  const DeskewGeometry g = deskew_launch_geometry(n_scans, H, W);
+  const uint32_t col_blocks = g.col_blocks, groups = g.groups, lines_per_block = g.lines_per_block;
   const size_t wide = (size_t)col_blocks * n_scans;
-  uint32_t groups = (uint32_t)((2048 + wide - 1) / wide);
-  groups = groups < 1u ? 1u : (groups > H ? H : groups);
-  const uint32_t lines_per_block = (H + groups - 1) / groups;
-  groups = (H + lines_per_block - 1) / lines_per_block;
   const dim3 grid((unsigned)wide, groups);
   if (f32)
     launch_kernel(deskew_kernel<float>, grid, dim3(kDeskewThreads), 0, s, static_cast<const float*>(d_xyz), static_cast<float*>(d_out), d_motion, H, W,

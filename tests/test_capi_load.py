@@ -45,6 +45,28 @@ def test_capacities():
     assert lib.loamx_planar_capacity(lidar, fe) == 64 * 6 * 51
 
 
+def test_deskew_launch_geometry_partitions_every_scan():
+    """loamx_deskew_launch_geometry (host arithmetic, the launcher's own function): the column blocks cover the columns and the
+    shares the lines, no block or share is empty, and the sizes the de-skew refuses are refused here"""
+    import ctypes as C
+    rng = np.random.default_rng(8)
+    shapes = [(1, 64, 1024), (3, 64, 1024), (257, 64, 1024), (1, 1, 1), (4000, 5, 255), (1, 100000, 256), (7, 3, 257)]
+    shapes += [tuple(int(v) for v in (rng.integers(1, 3000), rng.integers(1, 5000), rng.integers(1, 3000))) for _ in range(2000)]
+    for n, h, w in shapes:
+        g = capi.deskew_launch_geometry(n, h, w)
+        assert g.unroll == 4 and min(g) >= 1, (n, h, w, g)
+        assert (g.col_blocks - 1) * 256 < w <= g.col_blocks * 256, (n, h, w, g)
+        assert (g.shares - 1) * g.lines_per_share < h <= g.shares * g.lines_per_share, (n, h, w, g)
+    assert tuple(capi.deskew_launch_geometry(1, 64, 1024)) == (4, 64, 1, 4)  # (DESIGN 4.8: one scan, 4 column blocks x 64 shares)
+    for empty in ((0, 64, 1024), (2, 0, 1024), (2, 64, 0)):
+        assert tuple(capi.deskew_launch_geometry(*empty)) == (0, 0, 0, 4)
+    for bad in ((1, 1 << 32, 16), (1, 16, 1 << 32), (1 << 31, 1, 1)):
+        with pytest.raises(capi.LoamxError) as e:
+            capi.deskew_launch_geometry(*bad)
+        assert e.value.status == capi.ERR_UNSUPPORTED
+    assert capi.load().loamx_deskew_launch_geometry(1, 64, 1024, C.POINTER(C.c_uint32)()) == capi.ERR_BAD_PARAM
+
+
 def test_host_generator_matches_hostcheck():
     import hostcheck_lib as Hc
     a = capi.synth_scan_host(5, 3, 1, 8, 64, 0.01)

@@ -220,3 +220,7 @@ def test_trajectory(oracle):
         check_trajectory(oracle, c, rec, o)
     check_trajectory(oracle, c, rec[:0], origin)  # no pairs: the origin alone
     check_trajectory(oracle, c, rec[:65], None)   # one record into the second tile of 64
+    # both sides of every edge of the first two tiles of 64 records, and the shortest chains
+    for k in (1, 2, 63, 64, 127, 128, 129):
+        for o in (None, origin):
+            check_trajectory(oracle, c, rec[:k], o)
