@@ -156,6 +156,7 @@ constexpr uint32_t kRegFlagNoSmallSets = 8192u;     // edge-sized sets through g
 constexpr uint32_t kRegFlagCheckFinite = 4096u;     // the "_dev" entry points look for non-finite input coordinates first (host side only)
 constexpr uint32_t kRegFlagNoExtractBoxes = 2048u;  // the index builds take their bounding boxes themselves even when the extraction left them
 constexpr uint32_t kRegFlagNoMixedAssoc = 128u;  // edge and plane first kernels as separate launches on two streams (launch_associate)
+constexpr uint32_t kRegFlagForceLate = 16384u;    // plane fit of the mixed launch: every selection it has to verify is refused (all of them take the late list: associate_fit_late_kernel)
 
 // One target feature set's spatial index (device pointers into the workspace)
 struct GridSet {

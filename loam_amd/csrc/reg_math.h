@@ -1122,7 +1122,7 @@ LOAMX_HD int knn_f32_round1_body(const GridDesc& g, const GridPoint* __restrict_
 #else
 #define LOAMX_LEAN_REASON(r) ((void)0)
 #endif
-constexpr int kLeanRowWords = 18;
+constexpr int kLeanRowWords = 19, kLeanGuardWord = 18;  // (word 18: knn_lean_round1's search-over threshold, see knn_guard2_f32)
 #ifndef LOAMX_LEAN_TMAX
 #define LOAMX_LEAN_TMAX 64
 #endif
@@ -1139,14 +1139,16 @@ LOAMX_HD int knn_popcount64(uint64_t v) {
 // What follows the walk of the 3x3x3 block, shared by the lean forms: is the search over (rigorous bound against the
 // distance to the block's faces), then the exact verification of the k selected candidates. The visited list (begin |
 // first batch << 16 per visited range) starts at word `vis_off` of the per-thread list.
-template <int KM, int W = 1>
+// (GUARD = false: the caller has made the search-over test itself — knn_lean_round1 with the test's right-hand side taken in
+// front of the walk, knn_guard2_f32)
+template <int KM, int W = 1, bool GUARD = true>
 LOAMX_HD int knn_lean_finish(const GridDesc& g, const GridPoint* __restrict__ sp, Vec3 q, int k, double max_dist, double pass_max,
                              double a, int32_t cx, int32_t cy, int32_t cz, const KnnKeys32<KM>& c, uint64_t started,
                              const uint32_t* row_scratch, int row_stride, int vis_off, uint32_t pos[KM]) {
   constexpr uint32_t imask = 0xFFu;
   constexpr int NR = (2 * W + 1) * (2 * W + 1);  // rows of the block (W = 1: the 3x3x3 block, W = 2: 5x5x5)
   // ---- is the search over after the block of half-width W? (same test as knn_done, with the rigorous bound)
-  {
+  if (GUARD) {
     double guard = kDblMax;
     const double m = 1e-9 * g.h;
     const int32_t c3[3] = {cx, cy, cz}, n3[3] = {g.nx, g.ny, g.nz};
@@ -1222,6 +1224,115 @@ LOAMX_HD int knn_lean_finish(const GridDesc& g, const GridPoint* __restrict__ sp
   return undecided ? -3 : kept;  // (-3: the keys cannot decide — ties; -1 above: the block does not reach far enough)
 }
 
+/* ------------------------------------------------------------------------------------------------
+ * knn_lean_finish in three pieces (round 7), for the scan-pair path, where the kernel that fits the neighbours gathers the very
+ * FP64 points the verification looks at one kernel later:
+ *   knn_guard2_f32     : the right-hand side of the search-over test, taken in FRONT of the walk from the query point the set-up
+ *                        holds anyway, as one float (a word of the per-thread list) — nothing of the point is needed behind the walk;
+ *   knn_lean_select    : behind the walk, what the keys alone decide: a real key that is not finite (-3), the positions, and a
+ *                        count word for the hand-off: kNnUnverified | number of real keys | the upper 24 bits of the best
+ *                        rejected key (or kNnNoRejected);
+ *   knn_handoff_verify : on the k points as the fit has gathered them, the checks of knn_lean_finish word for word: exact d2
+ *                        strictly ascending and finite, best rejected key beyond d5 by the FP32 error, kept against pass_max.
+ * A count word is 0xFFFFFFFF (queued), has kNnUnverified set, or is a verified count (<= KM < 128).
+ * ---------------------------------------------------------------------------------------------- */
+constexpr uint32_t kNnQueued = 0xFFFFFFFFu, kNnUnverified = 0x80u, kNnNoRejected = 0x40u, kNnCountMask = 0x3Fu;
+
+// Squared distance to the faces of the block of half-width W around the query's cell, rounded DOWN to a float: a query
+// the rounding fails is queued and gets the exact answer there. +inf where the test of knn_lean_finish holds whatever the
+// keys (no face inside the grid, or the faces beyond the radius): bound < +inf also when the bound is DBL_MAX.
+template <int W = 1>
+LOAMX_HD float knn_guard2_f32(const GridDesc& g, Vec3 q, int32_t cx, int32_t cy, int32_t cz, double max_dist) {
+  double guard = kDblMax;
+  const double m = 1e-9 * g.h;
+  const int32_t c3[3] = {cx, cy, cz}, n3[3] = {g.nx, g.ny, g.nz};
+  const double q3[3] = {q.x, q.y, q.z}, o3[3] = {g.ox, g.oy, g.oz};
+#pragma unroll
+  for (int ax = 0; ax < 3; ax++) {  // (as knn_lean_finish)
+    if (c3[ax] - W > 0) {
+      const double d = (q3[ax] - (o3[ax] + (double)(c3[ax] - W) * g.h)) * (1.0 - 1e-9) - m;
+      guard = d < guard ? d : guard;
+    }
+    if (c3[ax] + W < n3[ax] - 1) {
+      const double d = ((o3[ax] + (double)(c3[ax] + W + 1) * g.h) - q3[ax]) * (1.0 - 1e-9) - m;
+      guard = d < guard ? d : guard;
+    }
+  }
+  if (guard < 0.0) guard = 0.0;
+  if (guard == kDblMax || (max_dist > 0.0 && guard >= max_dist)) return knn_bits_f32(0x7F800000u);
+  const double g2 = guard * guard;
+  // two roundings of at most 2^-24 each against the factor's 1e-6; below the normal floats (a guard of 1e-19 m) simply 0
+  const float f = (float)(g2 < 3.0e38 ? g2 : 3.0e38) * 0.999999f;
+  return f < 1.0e-30f ? 0.0f : f;
+}
+
+// Returns 0 and the count word, or -3 (a real key that is not finite: the queue's business, as in knn_lean_finish).
+template <int KM, int W = 1>
+LOAMX_HD int knn_lean_select(int k, const KnnKeys32<KM>& c, uint64_t started, const uint32_t* row_scratch, int row_stride, int vis_off,
+                             uint32_t pos[KM], uint32_t* word) {
+  constexpr uint32_t imask = 0xFFu;
+  constexpr int NR = (2 * W + 1) * (2 * W + 1);
+  uint32_t vrow[KM];
+#pragma unroll
+  for (int i = 0; i < KM; i++) {
+    const uint32_t tb = (c.key[i] & imask) >> 2;
+    const int ord = knn_popcount64(started & ((2ull << tb) - 1ull)) - 1;  // the visited row this batch belongs to
+    vrow[i] = row_scratch[(vis_off + (ord < 0 ? 0 : (ord > NR - 1 ? NR - 1 : ord))) * row_stride];
+  }
+  uint32_t count = 0;
+  bool undecided = false;
+#pragma unroll
+  for (int i = 0; i < KM; i++) {
+    const uint32_t key = c.key[i];
+    const bool real = i >= KM - k && key != 0xFFFFFFFFu;
+    const uint32_t tb = (key & imask) >> 2, ii = key & 3u;
+    pos[i] = real ? (vrow[i] & 0xFFFFu) + (tb - (vrow[i] >> 16)) * 4u + ii : 0u;
+    if (real && key >= 0x7F800000u) undecided = true;
+    count += real ? 1u : 0u;
+  }
+  const uint32_t k6 = c.key[KM];
+  *word = (k6 & ~imask) | kNnUnverified | (k6 == 0xFFFFFFFFu ? kNnNoRejected : 0u) | count;
+  if (undecided) LOAMX_LEAN_REASON(2);
+  return undecided ? -3 : 0;
+}
+
+// nb[j] = neighbour j as gathered from the positions knn_lean_select left (j < the word's count are real), q the query point
+// the keys were taken for, a = knn_f32_err_unit of the target's grid. Returns kept >= 0 or -3 (the keys cannot decide).
+template <int KM>
+LOAMX_HD int knn_handoff_verify(uint32_t word, Vec3 q, const GridPoint nb[KM], int k, double pass_max, double a) {
+  constexpr uint32_t imask = 0xFFu;
+  if (k > KM) k = KM;
+  const int count = (int)(word & kNnCountMask);
+  int kept = 0;
+  bool undecided = false, open = true;
+  double prev = -1.0, d5 = 0.0;
+#pragma unroll
+  for (int j = 0; j < KM; j++) {
+    if (j < count) {
+      const double dx = q.x - nb[j].x, dy = q.y - nb[j].y, dz = q.z - nb[j].z;
+      const double d2 = dx * dx + dy * dy + dz * dz;  // as knn_scan_batch
+      if (!(d2 > prev)) undecided = true;             // a tie or an inversion: the exact order is not this one
+      if (!(d2 <= kDblMax)) undecided = true;
+      prev = d2, d5 = d2;
+      if (open) {
+        if (d2 <= pass_max) kept++;
+        else open = false;
+      }
+    }
+  }
+  if (count == k && !(word & kNnNoRejected)) {
+    const double t6 = (double)knn_bits_f32(word & ~imask);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double sd5 = (double)(__fsqrt_rn((float)d5) * 1.000001f) + 1e-18;
+#else
+    const double sd5 = (double)(sqrtf((float)d5) * 1.000001f) + 1e-18;
+#endif
+    const double err = 2.0 * (3.4641016151377544 * a * sd5 + 3.0 * a * a + 2.384185791015625e-7 * d5);  // x2 safety
+    if (!(t6 > d5 + err)) undecided = true;
+  }
+  return undecided ? -3 : kept;
+}
+
 // one batch of four candidates in registers (n = 0: none)
 struct LeanBatch {
   KnnF4 x, y, z;
@@ -1270,10 +1381,17 @@ LOAMX_HD bool knn_lean_half_trip(KnnKeys32<KM>& c, LeanBatch& cur, LeanBatch& nx
 struct KnnSameQuery {
   LOAMX_HD Vec3 operator()(const Vec3& q) const { return q; }
 };
-template <int KM, typename Requery = KnnSameQuery>
+// HANDOFF (round 7, the scan-pair kernels): bit 0 = the search-over test's right-hand side is taken here in front of the walk
+// and kept in word kLeanGuardWord of the per-thread list (knn_guard2_f32); bit 1 = no verification behind the walk: the
+// count word for the kernel that fits the neighbours goes to *word (knn_lean_select; 0 = the return value is a verified
+// count), and `requery` is not called.
+template <int KM, typename Requery = KnnSameQuery, int HANDOFF = 0>
 LOAMX_HD int knn_lean_round1(const GridDesc& g, const uint32_t* __restrict__ cell_start, const GridPoint* __restrict__ sp,
                              const float* __restrict__ rel, uint32_t plane, Vec3 q, int k, double max_dist, double pass_max,
-                             uint32_t pos[KM], uint32_t* row_scratch, int row_stride, Requery requery = Requery()) {
+                             uint32_t pos[KM], uint32_t* row_scratch, int row_stride, Requery requery = Requery(),
+                             uint32_t* word = nullptr) {
+  static_assert(!(HANDOFF & 2) || (HANDOFF & 1), "the unverified form does not hold the query point behind the walk");
+  if (HANDOFF & 2) *word = 0u;
 #pragma unroll
   for (int j = 0; j < KM; j++) pos[j] = 0;
   if (g.n_points == 0 || k <= 0) return 0;
@@ -1295,6 +1413,7 @@ LOAMX_HD int knn_lean_round1(const GridDesc& g, const uint32_t* __restrict__ cel
   const float fz2[3] = {(float)(sz2m * sz2m) * kDown, 0.0f, (float)(sz2p * sz2p) * kDown};
   const float fr2 = r2 < 1e37 ? (float)r2 * kUp : 3.0e38f;
   const float fa2 = (float)(3003.0 * a * a) * kUp;
+  if (HANDOFF & 1) row_scratch[kLeanGuardWord * row_stride] = knn_f32_bits(knn_guard2_f32<1>(g, q, cx, cy, cz, max_dist));
   int nrow = 0;
   {  // the non-empty rows of the nine within the radius, centre first, then faces, then corners
     const int32_t xa = cx - 1 < 0 ? 0 : cx - 1, xb = cx + 1 > g.nx - 1 ? g.nx - 1 : cx + 1;
@@ -1416,7 +1535,13 @@ LOAMX_HD int knn_lean_round1(const GridDesc& g, const uint32_t* __restrict__ cel
 #if defined(LOAMX_LEAN_UNPIPELINED)
   if (p < e || ri < nrow) return -2;  // the trip budget is used up with rows still to look at: the queue's business
 #endif
-  {
+  if (HANDOFF & 1) {
+    const float guard2 = knn_bits_f32(row_scratch[kLeanGuardWord * row_stride]);
+    if (!(knn_bound32(c, a, imask) < (double)guard2)) { LOAMX_LEAN_REASON(1); return -1; }
+    if (HANDOFF & 2) return knn_lean_select<KM>(k, c, started, row_scratch, row_stride, 0, pos, word);
+    const Vec3 q2 = requery(q);
+    return knn_lean_finish<KM, 1, false>(g, sp, q2, k, max_dist, pass_max, a, 0, 0, 0, c, started, row_scratch, row_stride, 0, pos);
+  } else {
     const Vec3 q2 = requery(q);
     const int32_t cx2 = grid_cell_coord(q2.x, g.ox, g.inv_h), cy2 = grid_cell_coord(q2.y, g.oy, g.inv_h), cz2 = grid_cell_coord(q2.z, g.oz, g.inv_h);
     return knn_lean_finish<KM>(g, sp, q2, k, max_dist, pass_max, a, cx2, cy2, cz2, c, started, row_scratch, row_stride, 0, pos);
@@ -1553,14 +1678,16 @@ LOAMX_HD int knn_lean_round2(const GridDesc& g, const uint32_t* __restrict__ cel
 
 // WIDE = false: 8-bit running numbers (the fast kernel; a query with more than 63 batches is queued);
 // WIDE = true: 10 or 12 bits (the queue kernel tries this before the FP64 search: dense local maps).
-template <int KM, bool WIDE = false, typename Requery = KnnSameQuery>
+template <int KM, bool WIDE = false, typename Requery = KnnSameQuery, int HANDOFF = 0>
 LOAMX_HD int knn_search_f32_round1(const GridDesc& g, const uint32_t* __restrict__ cell_start,
                                    const GridPoint* __restrict__ sp, const float* __restrict__ rel, uint32_t plane, Vec3 q,
                                    int k, double max_dist, double pass_max, uint32_t pos[KM], uint32_t* row_scratch,
-                                   int row_stride, Requery requery = Requery()) {
+                                   int row_stride, Requery requery = Requery(), uint32_t* word = nullptr) {
+  if (HANDOFF & 2) *word = 0u;  // (every path but the lean one hands back a verified count)
 #if !defined(LOAMX_NO_LEAN_KNN)
   if (!WIDE && g.n_points <= kLeanMaxPoints)  // (wave-uniform: a property of the target set)
-    return knn_lean_round1<KM>(g, cell_start, sp, rel, plane, q, k, max_dist, pass_max, pos, row_scratch, row_stride, requery);
+    return knn_lean_round1<KM, Requery, HANDOFF>(g, cell_start, sp, rel, plane, q, k, max_dist, pass_max, pos, row_scratch, row_stride,
+                                                 requery, word);
 #endif
 #pragma unroll
   for (int j = 0; j < KM; j++) pos[j] = 0;

@@ -715,7 +715,7 @@ __global__ void state_init_kernel(RegBatch B, RegConfig C) {
   S.use_moments = 0;
   S.mom_ref_on = 0;
   S.lm.active = 0;
-  for (int c = 0; c < 6; c++) B.n_assoc[8 * pair + c] = 0;
+  for (int c = 0; c < 8; c++) B.n_assoc[8 * pair + c] = 0;
   if (B.max_counts) {  // the host sizes the association grids by the largest set instead of by the capacity
     const RegKind &E = B.kind[kEdge], &P = B.kind[kPlane];
     const uint32_t ne = E.n_src[pair * B.in_pitch], np = P.n_src[pair * B.in_pitch];
@@ -737,6 +737,14 @@ constexpr int kAssocThreads = 256;
 #ifndef LOAMX_KNN_REQUERY
 #define LOAMX_KNN_REQUERY 1
 #endif
+// (round 7) the hand-off between the plane round-1 kernel and the plane fit of one launch pair (associate_knn_mixed_kernel /
+// associate_fit_mixed_kernel), by bits: 1 = the search-over test's threshold taken in front of the walk, 2 = the selection is
+// verified by the fit, on the points it gathers anyway (failures: the late list, associate_fit_late_kernel). 0 = the kernels
+// of round 6. (Measured and left out: the moved query point handed over in record fields 0-2, tools/experiments/r07_*.patch.)
+#ifndef LOAMX_HANDOFF
+#define LOAMX_HANDOFF 3
+#endif
+static_assert(!(LOAMX_HANDOFF & 2) || (LOAMX_HANDOFF & 1), "verification in the fit needs the threshold in front of the walk");
 #ifndef LOAMX_ASSOC_WAVES5
 #define LOAMX_ASSOC_WAVES5 (LOAMX_KNN_REQUERY ? 6 : 4)  // the round-1 kernels of k <= 5 (knn_round1_body: 80 registers with the requery)
 #endif
@@ -936,7 +944,7 @@ constexpr uint32_t kQueueIndex = 0x3FFFFFFFu, kQueueWide = 0x80000000u, kQueueTi
 //                          (in the cell-sorted target array) of the k nearest, ascending.
 //   associate_fit_kernel : pure FP64 arithmetic — gathers the neighbours, fitLine / fitPlane, guards,
 //                          writes the association record.
-template <bool PLANE, int KM>
+template <bool PLANE, int KM, int HANDOFF = 0>
 __device__ __forceinline__ void knn_round1_body(const RegBatch& B, const RegConfig& C, uint32_t blocks_per_pair, uint32_t block,
                                                 uint32_t* s_rows) {
   size_t pair;
@@ -963,6 +971,8 @@ __device__ __forceinline__ void knn_round1_body(const RegBatch& B, const RegConf
   const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
   uint32_t pos[KM];  // (s_rows: per-thread row lists of knn_lean_round1, [word][thread], conflict free)
   const float* __restrict__ rel = gs.rel + pair * 3 * gs.stride;
+  const size_t field = B.n_pairs * stride;
+  uint32_t word = 0;
 #if LOAMX_KNN_REQUERY
   // (round 5) the verification behind the walk takes the query point from a second load + transform instead of from nine
   // registers held through the candidate loop: 89 -> 80 registers, a sixth wavefront per SIMD without scratch (the recomputation
@@ -974,15 +984,17 @@ __device__ __forceinline__ void knn_round1_body(const RegBatch& B, const RegConf
     const GridPoint s2 = src_pts[ii];
     return pose_act(S.est, v3(s2.x, s2.y, s2.z));
   };
-  const int kept = knn_search_f32_round1<KM, false, decltype(requery)>(g, cs, sp, rel, (uint32_t)gs.stride, p, CK.k,
-                                             CK.r, CK.pass, pos, s_rows + threadIdx.x, kAssocThreads, requery);
+  const int kept = knn_search_f32_round1<KM, false, decltype(requery), (HANDOFF & 3)>(g, cs, sp, rel, (uint32_t)gs.stride, p, CK.k,
+                                             CK.r, CK.pass, pos, s_rows + threadIdx.x, kAssocThreads, requery, &word);
 #else
   const int kept = knn_search_f32_round1<KM>(g, cs, sp, rel, (uint32_t)gs.stride, p, CK.k, CK.r, CK.pass, pos,
                                              s_rows + threadIdx.x, kAssocThreads);
 #endif
-  const size_t field = B.n_pairs * stride, slot = pair * stride + i;
+  uint32_t ia = i;
+  asm volatile("" : "+v"(ia));  // (opaque: the slot's 64-bit address is built here, not carried through the candidate loop)
+  const size_t slot = pair * stride + ia;
   uint32_t* __restrict__ nn = K.nn;  // [1 + KM][n_pairs * stride]
-  nn[slot] = kept < 0 ? 0xFFFFFFFFu : (uint32_t)kept;
+  nn[slot] = kept < 0 ? kNnQueued : (word ? word : (uint32_t)kept);  // (word: selected, to be verified by fit_one)
   if (kept < 0) {  // not finished by round 1: queued for associate_knn_rest_kernel
     const uint32_t at = atomicAdd(&B.n_assoc[8 * pair + (PLANE ? 3 : 2)], 1u);
     // (bit 31: the query only ran out of 8-bit running numbers — a dense block: the queue kernel retries the FP32
@@ -1008,7 +1020,7 @@ __global__ __launch_bounds__(kAssocThreads, (KME <= 5 && KMP <= 5) ? LOAMX_ASSOC
   constexpr size_t kRowBytes = sizeof(uint32_t) * kLeanRowWords * kAssocThreads, kTileBytes = kBruteLdsBytes;
   __shared__ __attribute__((aligned(16))) unsigned char s_raw[kRowBytes > kTileBytes ? kRowBytes : kTileBytes];
   if (blockIdx.x < edge_blocks) knn_brute_body<false, KME>(B, C, blocks_edge, blockIdx.x, reinterpret_cast<GridPoint*>(s_raw));
-  else knn_round1_body<true, KMP>(B, C, blocks_plane, blockIdx.x - edge_blocks, reinterpret_cast<uint32_t*>(s_raw));
+  else knn_round1_body<true, KMP, LOAMX_HANDOFF>(B, C, blocks_plane, blockIdx.x - edge_blocks, reinterpret_cast<uint32_t*>(s_raw));
 }
 
 // The queue chain. Round 1 queues 1-7 % of the plane queries, nearly all of them because their 3x3x3 block does not hold
@@ -1421,18 +1433,22 @@ __device__ __forceinline__ void knn_exact_one(const RegBatch& B, const RegConfig
 
 // fitLine / fitPlane on the neighbours of query i of `pair` and its association record; the neighbour
 // count and positions are read at index nidx of the (1 + KM)-field array nnsrc. Returns "valid".
-template <bool PLANE, int KM, bool QUEUED = false>
+// HANDOFF (the round-1 kernel's, see LOAMX_HANDOFF): bit 1 = a count word may be an unverified selection: verified here on
+// the gathered points (knn_handoff_verify), the verified count written back over it; a query that fails is appended to the
+// pair's late list (the tail of K.exact, filled from its end; counted in n_assoc[8 * pair + 6 + PLANE]) and left to
+// associate_fit_late_kernel.
+template <bool PLANE, int KM, bool QUEUED = false, int HANDOFF = 0>
 __device__ __forceinline__ bool fit_one(const RegBatch& B, const RegConfig& C, const PairState& S, size_t pair, uint32_t i,
-                                        const uint32_t* __restrict__ nnsrc, size_t nidx) {
+                                        const uint32_t* nnsrc, size_t nidx) {
   const RegKind& K = B.kind[PLANE];
   const RegKindConfig& CK = C.kind[PLANE];
   const size_t stride = K.stride;
   const GridSet &gs = K.grid, &src_gs = K.src_grid;
+  const size_t field = B.n_pairs * stride, slot = pair * stride + i;
   const GridPoint sq = src_gs.sorted[pair * src_gs.stride + i];
   const Vec3 p = pose_act(S.est, v3(sq.x, sq.y, sq.z));
   const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
-  const size_t field = B.n_pairs * stride, slot = pair * stride + i;
-  const int kept = (int)nnsrc[nidx];
+  int kept = (int)nnsrc[nidx];
   const int kq = CK.k;
   const int shift = KM - (kq < KM ? kq : KM);  // neighbour j is slot shift + j (knn_search_positions)
   double prim[6] = {0, 0, 0, 0, 0, 0};
@@ -1448,6 +1464,15 @@ __device__ __forceinline__ bool fit_one(const RegBatch& B, const RegConfig& C, c
   GridPoint tp[KM];
 #pragma unroll
   for (int j = 0; j < KM; j++) tp[j] = sp[at[j] < (uint32_t)gs.stride ? at[j] : 0u];
+  if ((HANDOFF & 2) && ((uint32_t)kept & kNnUnverified)) {  // (queued words have left above; verified counts are below 128)
+    kept = knn_handoff_verify<KM>((uint32_t)kept, p, tp, kq, CK.pass, knn_f32_err_unit(gs.desc[pair]));
+    if (kept < 0 || (C.flags & kRegFlagForceLate)) {
+      const uint32_t at = atomicAdd(&B.n_assoc[8 * pair + 6 + (PLANE ? 1 : 0)], 1u);
+      K.exact[pair * stride + (stride - 1 - at)] = i;
+      return false;
+    }
+    K.nn[nidx] = (uint32_t)kept;
+  }
   if (kept >= CK.min_pts) {  // registration.cpp:39 / :80
     Vec3 nb[KM];
 #pragma unroll
@@ -1481,7 +1506,7 @@ __device__ __forceinline__ bool fit_one(const RegBatch& B, const RegConfig& C, c
 #ifndef LOAMX_FIT_WAVES
 #define LOAMX_FIT_WAVES 4
 #endif
-template <bool PLANE, int KM>
+template <bool PLANE, int KM, int HANDOFF = 0>
 __device__ __forceinline__ void fit_body(const RegBatch& B, const RegConfig& C, uint32_t blocks_per_pair, uint32_t block) {
   size_t pair;
   uint32_t chunk;
@@ -1492,9 +1517,9 @@ __device__ __forceinline__ void fit_body(const RegBatch& B, const RegConfig& C, 
   const RegKind& K = B.kind[PLANE];
   const size_t stride = K.stride;
   const uint32_t n_src = K.n_src[pair * B.in_pitch];
-  const uint32_t* __restrict__ nn = K.nn;
+  const uint32_t* nn = K.nn;  // (HANDOFF: fit_one writes the verified count back)
   bool valid = false;
-  if (i < n_src && i < stride) valid = fit_one<PLANE, KM>(B, C, S, pair, i, nn, pair * stride + i);  // (queued queries: skipped inside)
+  if (i < n_src && i < stride) valid = fit_one<PLANE, KM, false, HANDOFF>(B, C, S, pair, i, nn, pair * stride + i);  // (queued queries: skipped inside)
   // (one atomic per wavefront, no barrier: a wavefront that is done leaves)
   const unsigned long long m = __ballot(valid);
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(&B.n_assoc[8 * pair + (PLANE ? 1 : 0)], (uint32_t)__popcll(m));
@@ -1508,7 +1533,7 @@ template <int KME, int KMP>  // (edge and plane fits in one launch, as associate
 __global__ __launch_bounds__(kAssocThreads, LOAMX_FIT_WAVES) void associate_fit_mixed_kernel(RegBatch B, RegConfig C, uint32_t blocks_edge,
                                                                                               uint32_t blocks_plane, uint32_t edge_blocks) {
   if (blockIdx.x < edge_blocks) fit_body<false, KME>(B, C, blocks_edge, blockIdx.x);
-  else fit_body<true, KMP>(B, C, blocks_plane, blockIdx.x - edge_blocks);
+  else fit_body<true, KMP, LOAMX_HANDOFF>(B, C, blocks_plane, blockIdx.x - edge_blocks);
 }
 
 // The queued queries, after associate_knn_rest_kernel: what its keys left undecided is searched exactly first, then the
@@ -1539,6 +1564,34 @@ __global__ __launch_bounds__(kRestThreads, 3) void associate_fit_queued_kernel(R
   if ((threadIdx.x & 63) == 0 && count) atomicAdd(&B.n_assoc[8 * pair + (PLANE ? 1 : 0)], count);
 }
 
+// The late list of associate_fit_mixed_kernel (selections the fit's verification refused: tied or inverted exact
+// distances, a rejected key too close to the k-th — fractions of a percent of a scan's queries): the exact collector, then
+// the fit, with the results in the query's own slot of nn. On the main stream behind the queue chain's join.
+template <bool PLANE, int KM>
+__global__ __launch_bounds__(kRestThreads, 3) void associate_fit_late_kernel(RegBatch B, RegConfig C, uint32_t blocks_per_pair) {  // (3: as associate_fit_queued_kernel)
+  size_t pair;
+  uint32_t chunk0;
+  if (!xcd_pair_map(blockIdx.x, blocks_per_pair, B.n_pairs, pair, chunk0)) return;
+  const uint32_t late = B.n_assoc[8 * pair + 6 + (PLANE ? 1 : 0)];
+  if (late == 0u) return;                                             // uniform per workgroup
+  const PairState& S = B.state[pair];
+  if (!S.active) return;                                              // uniform per workgroup
+  __shared__ uint32_t s_rows[18 * kRestThreads];
+  const RegKind& K = B.kind[PLANE];
+  const size_t stride = K.stride;
+  uint32_t* nn = K.nn;  // (written and read back here: no __restrict__)
+  const uint32_t* __restrict__ list = K.exact + pair * stride;
+  uint32_t count = 0;
+  for (uint32_t t = chunk0 * kRestThreads + threadIdx.x; t < late && t < stride; t += blocks_per_pair * kRestThreads) {
+    const uint32_t i = list[stride - 1 - t];
+    knn_exact_one<PLANE, KM>(B, C, S, pair, i, pair * stride + i, nn, s_rows + threadIdx.x, kRestThreads);
+    count += fit_one<PLANE, KM, true>(B, C, S, pair, i, nn, pair * stride + i) ? 1u : 0u;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) count += __shfl_xor(count, off);
+  if ((threadIdx.x & 63) == 0 && count) atomicAdd(&B.n_assoc[8 * pair + (PLANE ? 1 : 0)], count);
+}
+
 // (the ICF iteration number of an active pair is S.iterations, the iterations it has completed: no kernel argument
 // changes from one iteration to the next, so that the iteration can be replayed as a hipGraph)
 __global__ __launch_bounds__(64) void lm_begin_kernel(RegBatch B, RegConfig C) {
@@ -1549,7 +1602,7 @@ __global__ __launch_bounds__(64) void lm_begin_kernel(RegBatch B, RegConfig C) {
   if (!S.active) return;
   const uint32_t iteration = S.iterations;
   const uint32_t ne = B.n_assoc[8 * pair], np = B.n_assoc[8 * pair + 1];
-  for (int c = 0; c < 6; c++) B.n_assoc[8 * pair + c] = 0;
+  for (int c = 0; c < 8; c++) B.n_assoc[8 * pair + c] = 0;
   if ((uint64_t)ne + np < C.min_associations) {  // registration-inl.h:45-48
     S.termination = LOAMX_INSUFFICIENT_ASSOCIATIONS;
     S.active = 0;
@@ -2599,6 +2652,10 @@ void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipS
     launch_kernel((associate_fit_mixed_kernel<5, 5>), grid, dim3(kAssocThreads), 0, s, B, C, be, bp, edge_blocks);
     LOAMX_ASSOC_B(true, 5, bp, (fork2 ? sb : s));
     if (fork2 && hipEventRecord(aux2 ? ev_join2 : ev_join, sb) == hipSuccess) (void)hipStreamWaitEvent(s, aux2 ? ev_join2 : ev_join, 0);
+    if (LOAMX_HANDOFF & 2) {  // the selections the fit refused (its workgroups leave at once where a pair has none)
+      const uint32_t lblk = rest_blocks(B.n_pairs, bp);
+      launch_kernel((associate_fit_late_kernel<true, 5>), dim3((unsigned)(pair_groups * 8 * lblk)), dim3(kRestThreads), 0, s, B, C, lblk);
+    }
     return;
   }
   // (edges alone: on the caller's stream, nothing to run them next to)
