@@ -5,6 +5,7 @@
  */
 #pragma once
 #include <memory>
+#include <stdexcept>
 #include <utility>
 #include <vector>
 
@@ -216,6 +217,87 @@ Pose3d registerFeatures(const LoamFeatures<PointType, Alloc>& source, const Targ
                                                   source.planar_points.size(), init, &rp, &result, capture.arg()));
   capture.finish(result);
   return Pose3d::fromArray(result.pose);
+}
+
+/** @brief Extension (not in the reference): the 6x6 Gauss-Newton information matrix H = sum J^T J of the registration residuals of a
+ * pair at a pose, with its eigen-decomposition (loamx.h: loamx_reg_information). Basis: the left perturbation
+ * target_T_source <- Exp([omega, t]) o target_T_source — omega a rotation vector in radians about the target frame's axes
+ * (entries 0-2), t in metres (entries 3-5), rotation first. What a pose graph or a filter needs next to the pose, and what
+ * LOAM's mapping thread thresholds to detect corridors, tunnels and open fields. */
+struct RegistrationInformation {
+  double information[36];   ///< H, row-major, symmetric
+  double eigenvalues[6];    ///< ascending
+  double eigenvectors[36];  ///< row i: unit eigenvector of eigenvalues[i]
+  double gradient[6];       ///< sum J^T r: near zero where the pose sits at a minimum
+  double weighted_sq_error; ///< sum of the (Huber-scaled) squared residuals
+  size_t n_edge, n_plane;   ///< rows that entered the sums
+  size_t n_huber;           ///< of those, rows beyond the Huber threshold
+  size_t n_dropped;         ///< valid associations left out (non-finite row)
+
+  /// sigma^2 * sum v_i v_i^T / lambda_i over lambda_i > rel_threshold * lambda_5 with sigma^2 = weighted_sq_error / (rows - 6):
+  /// the covariance of the pose in the observable directions, row-major 6x6. Throws where there are not more than 6 rows.
+  std::vector<double> covariance(double rel_threshold = 1e-12) const {
+    const size_t rows = n_edge + n_plane;
+    if (rows <= 6) throw std::runtime_error("RegistrationInformation::covariance: not more than 6 residual rows");
+    const double sigma2 = weighted_sq_error / static_cast<double>(rows - 6);
+    std::vector<double> cov(36, 0.0);
+    for (int i = 0; i < 6; i++) {
+      if (!(eigenvalues[i] > rel_threshold * eigenvalues[5])) continue;
+      for (int a = 0; a < 6; a++)
+        for (int b = 0; b < 6; b++) cov[6 * a + b] += eigenvectors[6 * i + a] * eigenvectors[6 * i + b] / eigenvalues[i];
+    }
+    for (double& c : cov) c *= sigma2;
+    return cov;
+  }
+  /// The eigenvectors (6 entries each) whose eigenvalue lies below min_eigenvalue: the directions the geometry leaves open.
+  std::vector<std::vector<double>> degenerateDirections(double min_eigenvalue) const {
+    std::vector<std::vector<double>> out;
+    for (int i = 0; i < 6; i++)
+      if (eigenvalues[i] < min_eigenvalue) out.emplace_back(eigenvectors + 6 * i, eigenvectors + 6 * i + 6);
+    return out;
+  }
+};
+
+namespace gpu {
+inline RegistrationInformation fromC(const loamx_reg_information& c) {
+  RegistrationInformation r{};
+  for (int i = 0; i < 36; i++) r.information[i] = c.information[i], r.eigenvectors[i] = c.eigenvectors[i];
+  for (int i = 0; i < 6; i++) r.eigenvalues[i] = c.eigenvalues[i], r.gradient[i] = c.gradient[i];
+  r.weighted_sq_error = c.weighted_sq_error;
+  r.n_edge = c.n_edge, r.n_plane = c.n_plane, r.n_huber = c.n_huber, r.n_dropped = c.n_dropped;
+  return r;
+}
+}  // namespace gpu
+
+/// The information matrix of the residuals of (source, target) at target_T_source: one association pass, no solve.
+template <template <typename> class Accessor = FieldAccessor, typename PointType, template <typename> class Alloc>
+RegistrationInformation registrationInformation(const LoamFeatures<PointType, Alloc>& source, const LoamFeatures<PointType, Alloc>& target,
+                                                const Pose3d& target_T_source, const RegistrationParams& params = RegistrationParams()) {
+  loamx_ctx* ctx = gpu::defaultContext();
+  const std::vector<double> se = gpu::pack<Accessor>(source.edge_points), sp = gpu::pack<Accessor>(source.planar_points);
+  const std::vector<double> te = gpu::pack<Accessor>(target.edge_points), tp = gpu::pack<Accessor>(target.planar_points);
+  const loamx_reg_params rp = gpu::toC(params);
+  double pose[7];
+  target_T_source.toArray(pose);
+  loamx_reg_information info{};
+  gpu::check(ctx, loamx_registration_information(ctx, se.data(), source.edge_points.size(), sp.data(), source.planar_points.size(), te.data(),
+                                                 target.edge_points.size(), tp.data(), target.planar_points.size(), pose, &rp, &info));
+  return gpu::fromC(info);
+}
+
+/// ... against a prebuilt TargetIndex (scan-to-map: where degeneracy matters most)
+template <template <typename> class Accessor = FieldAccessor, typename PointType, template <typename> class Alloc>
+RegistrationInformation registrationInformation(const LoamFeatures<PointType, Alloc>& source, const TargetIndex& target,
+                                                const Pose3d& target_T_source, const RegistrationParams& params = RegistrationParams()) {
+  loamx_ctx* ctx = gpu::defaultContext();
+  const std::vector<double> se = gpu::pack<Accessor>(source.edge_points), sp = gpu::pack<Accessor>(source.planar_points);
+  const loamx_reg_params rp = gpu::toC(params);
+  double pose[7];
+  target_T_source.toArray(pose);
+  loamx_reg_information info{};
+  gpu::check(ctx, loamx_registration_information_indexed(ctx, target.handle(), se.data(), source.edge_points.size(), sp.data(),
+                                                         source.planar_points.size(), pose, &rp, &info));
+  return gpu::fromC(info);
 }
 
 }  // namespace loam

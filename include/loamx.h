@@ -336,6 +336,43 @@ int loamx_associate(loamx_ctx* ctx, const double* src_edge, size_t n_src_edge, c
                     const double* tgt_edge, size_t n_tgt_edge, const double* tgt_planar, size_t n_tgt_planar,
                     const double pose[7], const loamx_reg_params* reg, loamx_assoc_dump* out);
 
+/* ---- registration information matrix (no reference counterpart: the reference returns a pose and nothing else) ----------
+ * The 6x6 Gauss-Newton information matrix H = sum J^T J of the registration residuals of a pair at a pose T = target_T_source,
+ * with its eigen-decomposition: what a pose graph or a filter needs next to the pose (a covariance), and what LOAM's mapping
+ * thread, LeGO-LOAM and LIO-SAM threshold to detect corridors, tunnels and open fields (the small eigenvalues and their
+ * directions). The pair is associated ONCE at T, exactly as loamx_associate does (same kernels, same parameters of
+ * loamx_reg_params; max_iterations, the convergence thresholds and min_associations play no part, max_iterations == 0 is
+ * fine). Every valid association with moved point v = T.act(p) contributes one row:
+ *   plane  s = n.v - d,             r = |s|,           g = copysign(1, s) n
+ *   edge   c = (v - a) x (v - b),   r = |c| / |a - b|, g = ((a - b) x c) / (|c| |a - b|)
+ *   row    J = [ v x g , g ]  (1 x 6): the derivative of r for the LEFT perturbation T <- Exp([omega, t]) o T, omega a rotation
+ *          vector in radians about the TARGET frame's axes, t in metres, rotation first (columns 0-2 omega, 3-5 t)
+ *   Huber(1.0) as the solver applies it: for r^2 > 1, J and r are scaled by sqrt(1 / r)
+ *   a row with a non-finite entry is left out and counted in n_dropped (an edge point exactly on its line has |c| = 0)
+ * A pair without a single row gives a zero matrix, zero eigenvalues and identity eigenvectors. Deterministic: the same bytes
+ * on every run, and the same bytes for a pair whether it is computed alone or inside any batch (fixed chunks of a pair's
+ * association slots, partial sums added in chunk order). Records are per rank: the multi-GPU gather does not carry them. */
+typedef struct {
+  double information[36];   /* H = sum J^T J, row-major, bitwise symmetric */
+  double eigenvalues[6];    /* ascending */
+  double eigenvectors[36];  /* row i: unit eigenvector of eigenvalues[i]; its largest-magnitude component (lowest index on ties) is positive */
+  double gradient[6];       /* sum J^T r  (scaled rows and residuals) */
+  double weighted_sq_error; /* sum of scaled r^2 */
+  uint32_t n_edge, n_plane; /* rows that entered the sums */
+  uint32_t n_huber;         /* of those, rows with r^2 > 1 */
+  uint32_t n_dropped;       /* valid associations left out (non-finite row) */
+} loamx_reg_information;    /* 696 bytes */
+/* host, one pair (H2D, kernels, D2H, synchronous). Null pointers, non-finite points or pose: LOAMX_ERR_BAD_PARAM;
+ * num_*_neighbors > 16: LOAMX_ERR_UNSUPPORTED — as loamx_register_features. */
+int loamx_registration_information(loamx_ctx* ctx, const double* src_edge, size_t n_src_edge, const double* src_planar,
+                                   size_t n_src_planar, const double* tgt_edge, size_t n_tgt_edge, const double* tgt_planar,
+                                   size_t n_tgt_planar, const double pose[7], const loamx_reg_params* reg,
+                                   loamx_reg_information* info);
+/* the same against a persistent target index (scan-to-map: where degeneracy matters most) */
+int loamx_registration_information_indexed(loamx_ctx* ctx, const loamx_target_index* index, const double* src_edge,
+                                           size_t n_src_edge, const double* src_planar, size_t n_src_planar, const double pose[7],
+                                           const loamx_reg_params* reg, loamx_reg_information* info);
+
 /* ---- device-resident batch entry points (asynchronous on the context stream) ------------------ */
 
 /* Feature buffers of scan s live at base + s * stride with
@@ -367,6 +404,17 @@ int loamx_register_features_batch_dev(loamx_ctx* ctx, size_t n_pairs, const doub
                                       const uint32_t* d_n_tgt_planar, size_t edge_stride, size_t planar_stride,
                                       const double* d_init, const loamx_reg_params* reg,
                                       loamx_reg_result* d_results);
+
+/* loamx_registration_information over n_pairs independent pairs: the argument list of loamx_register_features_batch_dev with
+ * the poses d_pose (n_pairs x 7 doubles, NULL = identity) in place of d_init and one information record per pair in place of
+ * the results. */
+int loamx_registration_information_batch_dev(loamx_ctx* ctx, size_t n_pairs, const double* d_src_edge,
+                                             const uint32_t* d_n_src_edge, const double* d_src_planar,
+                                             const uint32_t* d_n_src_planar, const double* d_tgt_edge,
+                                             const uint32_t* d_n_tgt_edge, const double* d_tgt_planar,
+                                             const uint32_t* d_n_tgt_planar, size_t edge_stride, size_t planar_stride,
+                                             const double* d_pose, const loamx_reg_params* reg,
+                                             loamx_reg_information* d_info);
 
 /* The north-star unit: one scan-pair registration = extractFeatures(target scan), extractFeatures(
  * source scan), registerFeatures(source, target, identity). d_xyz holds n_pairs x 2 scans, target
@@ -419,6 +467,22 @@ int loamx_register_scan_sequence(loamx_ctx* ctx, const double* xyz, size_t n_sca
 int loamx_register_scan_sequence_f32(loamx_ctx* ctx, const float* xyz, size_t n_scans, const loamx_lidar_params* lidar,
                                      const loamx_fe_params* fe, const loamx_reg_params* reg, const double* init,
                                      loamx_reg_result* results);
+/* The "_dev" pair and sequence entry points with the information matrix behind the registration: d_results as the plain
+ * forms write them (bit-identical), plus d_info[p] = the information record of pair p taken at d_results[p].pose — one more
+ * association pass at the final poses against the target indexes the registration built, then the two information kernels.
+ * The records are those of loamx_registration_information_batch_dev at these poses on the pairs' extracted features. */
+int loamx_register_scan_pairs_info_dev(loamx_ctx* ctx, const double* d_xyz, size_t n_pairs, const loamx_lidar_params* lidar,
+                                       const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results,
+                                       loamx_reg_information* d_info);
+int loamx_register_scan_pairs_info_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_pairs, const loamx_lidar_params* lidar,
+                                           const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results,
+                                           loamx_reg_information* d_info);
+int loamx_register_scan_sequence_info_dev(loamx_ctx* ctx, const double* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                                          const loamx_fe_params* fe, const loamx_reg_params* reg, const double* d_init,
+                                          loamx_reg_result* d_results, loamx_reg_information* d_info);
+int loamx_register_scan_sequence_info_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                                              const loamx_fe_params* fe, const loamx_reg_params* reg, const double* d_init,
+                                              loamx_reg_result* d_results, loamx_reg_information* d_info);
 /* The chained trajectory of n_pairs consecutive results (device records): d_world_T_scan holds (n_pairs + 1) x 7 doubles,
  * world_T_scan[0] = origin (HOST pointer to a pose; NULL = identity), world_T_scan[i + 1] = world_T_scan[i] (+) results[i].pose
  * with the arithmetic of Pose3d::compose (geometry.h:32), in the order of the loop a host would write — a pair that ended
@@ -512,7 +576,8 @@ enum {
   LOAMX_K_EXTRACT_FUSED = 9, /* curvature + validity + selection + compaction in one pass over the scan: 24 B/point read
                                 (12 with float input) + (4 + 24) B per feature written. LOAMX_K_CURVATURE / _SELECT count
                                 the separate kernels, which run when the parameters rule the fused one out */
-  LOAMX_K_COUNT = 10
+  LOAMX_K_INFORMATION = 10, /* information_kernel + information_finish_kernel: 72 B per edge + 56 B per plane slot streamed */
+  LOAMX_K_COUNT = 11
 };
 typedef struct {
   uint64_t launches;

@@ -13,7 +13,7 @@ from . import build as _build
 
 OK, ERR_SCAN_SIZE, ERR_BAD_PARAM, ERR_HIP, ERR_CAPACITY, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_COMM = range(8)
 CONVERGED, MAX_ITER, INSUFFICIENT_ASSOCIATIONS = 0, 1, 2
-K_CURVATURE, K_SELECT, K_COMPACT, K_GRID, K_ASSOC, K_SWEEP, K_LM, K_MOMENT, K_KNN_PLANE, K_EXTRACT_FUSED, K_COUNT = range(11)
+K_CURVATURE, K_SELECT, K_COMPACT, K_GRID, K_ASSOC, K_SWEEP, K_LM, K_MOMENT, K_KNN_PLANE, K_EXTRACT_FUSED, K_INFORMATION, K_COUNT = range(12)
 
 
 class LidarParams(C.Structure):
@@ -71,6 +71,66 @@ class KernelStat(C.Structure):
 
 
 RESULT_DTYPE = np.dtype([("pose", np.float64, 7), ("termination", np.uint32), ("iterations", np.uint32)])
+# loamx_reg_information as a numpy record (696 bytes): arrays of device records come back as this dtype
+INFORMATION_DTYPE = np.dtype([("information", np.float64, (6, 6)), ("eigenvalues", np.float64, 6), ("eigenvectors", np.float64, (6, 6)),
+                              ("gradient", np.float64, 6), ("weighted_sq_error", np.float64), ("n_edge", np.uint32),
+                              ("n_plane", np.uint32), ("n_huber", np.uint32), ("n_dropped", np.uint32)])
+
+
+def information_covariance(eigenvalues, eigenvectors, weighted_sq_error, n_rows, rel_threshold=1e-12):
+    """sigma^2 * sum v_i v_i^T / lambda_i over lambda_i > rel_threshold * lambda_5, sigma^2 = weighted_sq_error / (n_rows - 6):
+    the covariance of the pose in the basis of the information matrix, restricted to the directions the geometry observes."""
+    if n_rows <= 6:
+        raise ValueError(f"covariance: {n_rows} residual rows do not determine 6 degrees of freedom and a variance")
+    lam, vec = np.asarray(eigenvalues, dtype=np.float64), np.asarray(eigenvectors, dtype=np.float64).reshape(6, 6)
+    sigma2 = float(weighted_sq_error) / (n_rows - 6)
+    cov = np.zeros((6, 6))
+    for i in range(6):
+        if lam[i] > rel_threshold * lam[5]:
+            cov += np.outer(vec[i], vec[i]) / lam[i]
+    return sigma2 * cov
+
+
+class RegInformation(C.Structure):
+    """loamx_reg_information (include/loamx.h): the Gauss-Newton information matrix of a pair's residuals at a pose, in the
+    left-perturbation basis [omega (rad, target axes), t (m)], with its eigenpairs."""
+    _fields_ = [("_information", C.c_double * 36), ("_eigenvalues", C.c_double * 6), ("_eigenvectors", C.c_double * 36),
+                ("_gradient", C.c_double * 6), ("weighted_sq_error", C.c_double), ("n_edge", C.c_uint32), ("n_plane", C.c_uint32),
+                ("n_huber", C.c_uint32), ("n_dropped", C.c_uint32)]
+
+    @classmethod
+    def from_record(cls, rec):
+        """from one INFORMATION_DTYPE record (or 696 bytes)"""
+        return cls.from_buffer_copy(np.ascontiguousarray(rec).tobytes())
+
+    def _view(self, name, shape):
+        return np.ctypeslib.as_array(getattr(self, name)).reshape(shape)
+
+    @property
+    def information(self):
+        """H = sum J^T J, (6, 6), a view of the record"""
+        return self._view("_information", (6, 6))
+
+    @property
+    def eigenvalues(self):
+        return self._view("_eigenvalues", (6,))
+
+    @property
+    def eigenvectors(self):
+        """(6, 6): row i is the unit eigenvector of eigenvalues[i]"""
+        return self._view("_eigenvectors", (6, 6))
+
+    @property
+    def gradient(self):
+        return self._view("_gradient", (6,))
+
+    def covariance(self, rel_threshold=1e-12):
+        return information_covariance(self.eigenvalues, self.eigenvectors, self.weighted_sq_error, int(self.n_edge) + int(self.n_plane),
+                                      rel_threshold)
+
+    def degenerate_directions(self, min_eigenvalue):
+        """the eigenvectors (rows) whose eigenvalue lies below min_eigenvalue: the directions the geometry does not constrain"""
+        return self.eigenvectors[self.eigenvalues < min_eigenvalue].copy()
 
 class AssocDump(C.Structure):
     """loamx_assoc_dump (include/loamx.h)"""
@@ -100,6 +160,9 @@ EXPORTS = [
     "loamx_register_scan_sequence_f32", "loamx_compose_trajectory_dev", "loamx_deskew_scans_dev", "loamx_deskew_scans_dev_f32",
     "loamx_deskew_launch_geometry",
     "loamx_target_index_points", "loamx_voxel_filter_dev", "loamx_target_index_insert_filtered", "loamx_target_index_crop",
+    "loamx_registration_information", "loamx_registration_information_indexed", "loamx_registration_information_batch_dev",
+    "loamx_register_scan_pairs_info_dev", "loamx_register_scan_pairs_info_dev_f32", "loamx_register_scan_sequence_info_dev",
+    "loamx_register_scan_sequence_info_dev_f32",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -241,6 +304,15 @@ def load(build_if_missing=True):
     lib.loamx_ctx_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     lib.loamx_ctx_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int)]
     lib.loamx_ctx_last_extract_route.argtypes = [vp, C.POINTER(C.c_uint32)]
+    lib.loamx_registration_information.argtypes = [vp, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp,
+                                                   C.POINTER(RegistrationParams), C.POINTER(RegInformation)]
+    lib.loamx_registration_information_indexed.argtypes = [vp, vp, dp, C.c_size_t, dp, C.c_size_t, dp, C.POINTER(RegistrationParams),
+                                                           C.POINTER(RegInformation)]
+    lib.loamx_registration_information_batch_dev.argtypes = lib.loamx_register_features_batch_dev.argtypes
+    lib.loamx_register_scan_pairs_info_dev.argtypes = lib.loamx_register_scan_pairs_dev.argtypes + [vp]
+    lib.loamx_register_scan_pairs_info_dev_f32.argtypes = lib.loamx_register_scan_pairs_info_dev.argtypes
+    lib.loamx_register_scan_sequence_info_dev.argtypes = lib.loamx_register_scan_sequence_dev.argtypes + [vp]
+    lib.loamx_register_scan_sequence_info_dev_f32.argtypes = lib.loamx_register_scan_sequence_info_dev.argtypes
     _lib = lib
     return lib
 
@@ -644,6 +716,39 @@ class Context:
                                                              C.byref(reg), C.byref(res), None))
         return np.array(list(res.pose)), res.termination, res.iterations
 
+    # ---- registration information matrix (include/loamx.h: loamx_reg_information) -----------------------
+    def registration_information(self, src_edge, src_planar, tgt_edge, tgt_planar, pose=None, reg=None):
+        """The information matrix of the pair's residuals at `pose` (target_T_source; None = identity), as a RegInformation."""
+        reg = reg or RegistrationParams()
+        arrs = [_pts(a) for a in (src_edge, src_planar, tgt_edge, tgt_planar)]
+        pose = np.ascontiguousarray([0, 0, 0, 1, 0, 0, 0] if pose is None else pose, dtype=np.float64)
+        if pose.size != 7:
+            raise ValueError("a pose has 7 values: qx, qy, qz, qw, tx, ty, tz")
+        info = RegInformation()
+        self._check(self.lib.loamx_registration_information(self.h, _dp(arrs[0]), len(arrs[0]), _dp(arrs[1]), len(arrs[1]), _dp(arrs[2]),
+                                                            len(arrs[2]), _dp(arrs[3]), len(arrs[3]), _dp(pose), C.byref(reg), C.byref(info)))
+        return info
+
+    def registration_information_indexed(self, index, src_edge, src_planar, pose=None, reg=None):
+        """the same against a persistent target index (scan-to-map)"""
+        reg = reg or RegistrationParams()
+        se, sp = _pts(src_edge), _pts(src_planar)
+        pose = np.ascontiguousarray([0, 0, 0, 1, 0, 0, 0] if pose is None else pose, dtype=np.float64)
+        if pose.size != 7:
+            raise ValueError("a pose has 7 values: qx, qy, qz, qw, tx, ty, tz")
+        info = RegInformation()
+        self._check(self.lib.loamx_registration_information_indexed(self.h, index, _dp(se), len(se), _dp(sp), len(sp), _dp(pose),
+                                                                    C.byref(reg), C.byref(info)))
+        return info
+
+    def registration_information_batch_dev(self, n_pairs, d_src_edge, d_n_src_edge, d_src_planar, d_n_src_planar, d_tgt_edge,
+                                           d_n_tgt_edge, d_tgt_planar, d_n_tgt_planar, edge_stride, planar_stride, d_pose, reg, d_info):
+        """n_pairs device-resident pairs (layout of register_features_batch_dev) at the poses d_pose (n_pairs x 7 device doubles,
+        0 = identity) -> n_pairs device records (INFORMATION_DTYPE). Asynchronous on the context's stream."""
+        self._check(self.lib.loamx_registration_information_batch_dev(
+            self.h, n_pairs, d_src_edge, d_n_src_edge, d_src_planar, d_n_src_planar, d_tgt_edge, d_n_tgt_edge, d_tgt_planar,
+            d_n_tgt_planar, edge_stride, planar_stride, d_pose or None, C.byref(reg), d_info))
+
     # ---- device-resident batch entry points (raw device pointers as ints) -----------------------------
     def edge_capacity(self, lidar, fe):
         return self.lib.loamx_edge_capacity(C.byref(lidar), C.byref(fe))
@@ -664,7 +769,12 @@ class Context:
             self.h, n_pairs, d_src_edge, d_n_src_edge, d_src_planar, d_n_src_planar, d_tgt_edge, d_n_tgt_edge,
             d_tgt_planar, d_n_tgt_planar, edge_stride, planar_stride, d_init, C.byref(reg), d_results))
 
-    def register_scan_pairs_dev(self, d_xyz, n_pairs, lidar, fe, reg, d_results, f32=False):
+    def register_scan_pairs_dev(self, d_xyz, n_pairs, lidar, fe, reg, d_results, f32=False, d_info=None):
+        """d_info: device room for n_pairs information records (INFORMATION_DTYPE), taken at the result poses (the "_info" form)"""
+        if d_info:
+            fn = self.lib.loamx_register_scan_pairs_info_dev_f32 if f32 else self.lib.loamx_register_scan_pairs_info_dev
+            self._check(fn(self.h, d_xyz, n_pairs, C.byref(lidar), C.byref(fe), C.byref(reg), d_results, d_info))
+            return
         fn = self.lib.loamx_register_scan_pairs_dev_f32 if f32 else self.lib.loamx_register_scan_pairs_dev
         self._check(fn(self.h, d_xyz, n_pairs, C.byref(lidar), C.byref(fe), C.byref(reg), d_results))
 
@@ -700,9 +810,14 @@ class Context:
         return res
 
     # ---- scan sequences: scan i is the source of pair i - 1 and the target of pair i ------------------------
-    def register_scan_sequence_dev(self, d_xyz, n_scans, lidar, fe, reg, d_results, d_init=0, f32=False):
+    def register_scan_sequence_dev(self, d_xyz, n_scans, lidar, fe, reg, d_results, d_init=0, f32=False, d_info=None):
         """n_scans device-resident scans back to back -> n_scans - 1 device records (pair p: scan p target, scan p + 1
-        source); d_init: (n_scans - 1) x 7 device doubles or 0 (identity). Asynchronous on the context's stream."""
+        source); d_init: (n_scans - 1) x 7 device doubles or 0 (identity). Asynchronous on the context's stream.
+        d_info: device room for n_scans - 1 information records, taken at the result poses (the "_info" form)."""
+        if d_info:
+            fn = self.lib.loamx_register_scan_sequence_info_dev_f32 if f32 else self.lib.loamx_register_scan_sequence_info_dev
+            self._check(fn(self.h, d_xyz, n_scans, C.byref(lidar), C.byref(fe), C.byref(reg), d_init or None, d_results, d_info))
+            return
         fn = self.lib.loamx_register_scan_sequence_dev_f32 if f32 else self.lib.loamx_register_scan_sequence_dev
         self._check(fn(self.h, d_xyz, n_scans, C.byref(lidar), C.byref(fe), C.byref(reg), d_init or None, d_results))
 

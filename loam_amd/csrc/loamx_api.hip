@@ -28,7 +28,7 @@ enum WsId {
   WS_SORT_SCRATCH, WS_SORT_SCRATCH_SRC, WS_NASSOC, WS_STATE, WS_PARTIALS, WS_MOM_PARTIALS, WS_MOMENTS, WS_FLAGGED_LIST, WS_FLAGGED_COUNT,
   WS_LINE_TOT, WS_EXTRACT_EVENTS, WS_BOX, WS_FINITE_FLAG, WS_COUNTERS, WS_ITERINFO, WS_STREAM_IN0, WS_STREAM_IN1, WS_STREAM_RES,
   WS_FIT_IN, WS_FIT_OUT, WS_FCOUNTS, WS_RESULTS, WS_INIT, WS_STREAM_INIT,
-  WS_VOX_TABLE, WS_MAP_WORDS,
+  WS_VOX_TABLE, WS_MAP_WORDS, WS_INFO_PARTIALS, WS_INFO,
   WS_COUNT
 };
 // the buffers that exist once per feature kind: loamx_ctx::wsk[id][kEdge | kPlane]
@@ -128,7 +128,7 @@ namespace {
 const char* kKernelNames[LOAMX_K_COUNT] = {"curvature_valid_kernel", "select_kernel", "compact_kernel",
                                            "grid_build_kernel",      "associate_kernel", "sweep_kernel",
                                            "lm_kernels",             "moment_kernel",    "knn_plane_kernel",
-                                           "extract_fused_kernel"};
+                                           "extract_fused_kernel",   "information_kernel"};
 
 struct OptionName {
   const char* name;
@@ -511,6 +511,16 @@ struct RegInputs {
   uint32_t src_box_offset;  // RegBatch::src_box_offset: scans from a pair's target box to its source box; 0: target boxes only
 };
 
+// The information matrix (loamx.h: loamx_reg_information) of every pair, written to d_info.
+//   only  = true:  the poses arrive in place of the initial estimates (RegInputs::init); index builds, ONE association pass at
+//                  them, the two information kernels — no solve, d_results untouched (the dump path without its one-pair limit)
+//   only  = false: behind the registration, once every pair has stopped: the loop's target indexes are reused and the pass
+//                  associates at each pair's final estimate
+struct InfoRequest {
+  loamx_reg_information* d_info;
+  bool only;
+};
+
 // host-side hook called after the association kernels of iteration `it` (detail capture)
 typedef int (*AfterAssocHook)(loamx_ctx*, const RegBatch&, uint32_t it, void* user);
 
@@ -607,13 +617,13 @@ int enqueue_icf_iteration(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C,
 // host arrays of *dump (one pair); no solve, d_results untouched
 int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loamx_reg_result* d_results, bool want_iter_info,
                  AfterAssocHook hook, void* hook_user, const loamx_target_index* prebuilt = nullptr, const loamx_assoc_dump* dump = nullptr,
-                 const size_t* dump_n_src = nullptr) {
+                 const size_t* dump_n_src = nullptr, const InfoRequest* info = nullptr) {
   if (in.n_pairs == 0) return LOAMX_OK;
   RegConfig C = C_in;
   // The reference's associateEdges / associatePlanes (registration.cpp:23-103) do not know max_iterations; here a pair with
   // max_iterations == 0 is never active (state_init_kernel), so its association kernels would return at once and the dump
   // would read workspace nobody wrote. One association pass needs one iteration's worth of "active".
-  if (dump && C.max_iterations == 0) C.max_iterations = 1;
+  if ((dump || (info && info->only)) && C.max_iterations == 0) C.max_iterations = 1;
   untimed(ctx);
   if (in.n_pairs > 0x7FFFFFFFull / 128) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "too many pairs in one call");
   const size_t np = in.n_pairs, es = in.kind[kEdge].stride ? in.kind[kEdge].stride : 1, ps = in.kind[kPlane].stride ? in.kind[kPlane].stride : 1;
@@ -674,6 +684,8 @@ int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loa
   SCRATCH(ctx->ws[WS_MOMENTS], np * (size_t)(kMomSize + 2) * sizeof(double), B.moments);
   SCRATCH(ctx->ws[WS_FLAGGED_LIST], np * (size_t)B.mom_blocks_per_pair * kSweepChunk * sizeof(uint32_t), B.flagged_list);
   SCRATCH(ctx->ws[WS_FLAGGED_COUNT], np * (size_t)B.mom_blocks_per_pair * 4 * sizeof(uint32_t), B.flagged_count);
+  InfoPartial* info_partials = nullptr;
+  if (info) SCRATCH(ctx->ws[WS_INFO_PARTIALS], np * info_blocks_per_pair(es, ps) * sizeof(InfoPartial), info_partials);
 #undef SCRATCH_K
 #undef SCRATCH
   {
@@ -770,6 +782,23 @@ int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loa
     HIP_TRY(ctx, hipStreamSynchronize(s));
     return LOAMX_OK;
   }
+  // One association pass at the pairs' current estimates, then the information kernels. Behind a registration every pair has
+  // stopped and the association kernels would leave at once: info_activate_kernel marks the pairs active for this one pass
+  // (nothing reads `active` afterwards: the next call starts from state_init_kernel; the queue lengths in n_assoc are zero,
+  // lm_begin_kernel cleared them when the pair's last iteration began).
+  auto information_pass = [&](bool activate) -> int {
+    untimed(ctx);
+    if (activate) launch_info_activate(B, s);
+    const int rc_a = enqueue_association(ctx, B, C);
+    if (rc_a != LOAMX_OK) return rc_a;
+    {
+      TimedScope t(ctx, LOAMX_K_INFORMATION, 0.0, true);
+      launch_information(B, info_partials, info->d_info, s);
+    }
+    CHECK_LAUNCH(ctx, "information_kernel");
+    return LOAMX_OK;
+  };
+  if (info && info->only) return information_pass(false);
   // (Replaying an ICF iteration as a hipGraph was measured in round 2 — captured once, cached, ~110 kernel nodes over
   // three streams: 13.6 vs 13.1 ms per 1 024-pair step and 1.06 vs 1.07 ms for one pair. The GPU-side turnaround of
   // dependent kernels bounds both, not the host's launch rate, and the graph loses the stream priorities; removed.)
@@ -795,7 +824,7 @@ int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loa
       HIP_TRY(ctx, hipStreamSynchronize(s));
       if (ctx->h_pinned[0] == 0) {
         ctx->max_counts_clean = true;
-        return LOAMX_OK;
+        return info ? information_pass(true) : LOAMX_OK;
       }
     }
   }
@@ -803,7 +832,7 @@ int register_dev(loamx_ctx* ctx, const RegInputs& in, const RegConfig& C_in, loa
   launch_write_results(B, d_results, s);
   CHECK_LAUNCH(ctx, "write_results_kernel");
   ctx->max_counts_clean = true;
-  return LOAMX_OK;
+  return info ? information_pass(true) : LOAMX_OK;
 }
 
 int resolve_events(loamx_ctx* ctx) {
@@ -1173,11 +1202,13 @@ struct HostSets {  // one scan's feature sets in host memory, [edge, plane]
 };
 static int register_features_impl(loamx_ctx* ctx, const loamx_target_index* index, const HostSets& src, HostSets tgt, const double init_pose[7],
                                   const loamx_reg_params* reg, loamx_reg_result* result, loamx_reg_detail* detail,
-                                  const loamx_assoc_dump* dump = nullptr) {
+                                  const loamx_assoc_dump* dump = nullptr, loamx_reg_information* info_out = nullptr) {
   if (!ctx) return LOAMX_ERR_BAD_PARAM;
   std::lock_guard<std::mutex> lock(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if ((!result && !dump) || !init_pose) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  if ((!result && !dump && !info_out) || !init_pose) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  for (int k = 0; k < 2; k++)
+    if ((src.n[k] && !src.pts[k]) || (!index && tgt.n[k] && !tgt.pts[k])) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
   RegConfig C;
   int rc = make_reg_config(ctx, reg, C);
   if (rc != LOAMX_OK) return rc;
@@ -1204,6 +1235,7 @@ static int register_features_impl(loamx_ctx* ctx, const loamx_target_index* inde
   ENSURE(ctx, WS_FCOUNTS, 4 * sizeof(uint32_t));
   ENSURE(ctx, WS_RESULTS, sizeof(loamx_reg_result));
   ENSURE(ctx, WS_INIT, 7 * sizeof(double));
+  if (info_out) ENSURE(ctx, WS_INFO, sizeof(loamx_reg_information));
   for (int k = 0; k < 2; k++) {
     if (src.n[k]) HIP_TRY(ctx, hipMemcpyAsync(ctx->wsk[WSK_SRC][k].p, src.pts[k], src.n[k] * 24, hipMemcpyHostToDevice, s));
     if (tgt.n[k]) HIP_TRY(ctx, hipMemcpyAsync(ctx->wsk[WSK_TGT][k].p, tgt.pts[k], tgt.n[k] * 24, hipMemcpyHostToDevice, s));
@@ -1228,9 +1260,15 @@ static int register_features_impl(loamx_ctx* ctx, const loamx_target_index* inde
   in.init = wsp<double>(ctx, WS_INIT);
   DetailHook hook{detail, {src.n[kEdge], src.n[kPlane]}};
   if (detail) detail->n_iter_info = 0;
+  const InfoRequest info_req{wsp<loamx_reg_information>(ctx, WS_INFO), true};
   rc = register_dev(ctx, in, C, wsp<loamx_reg_result>(ctx, WS_RESULTS), detail && detail->iter_info,
-                    detail ? detail_hook : nullptr, &hook, index, dump, src.n);
+                    detail ? detail_hook : nullptr, &hook, index, dump, src.n, info_out ? &info_req : nullptr);
   if (rc != LOAMX_OK || dump) return rc;
+  if (info_out) {
+    HIP_TRY(ctx, hipMemcpyAsync(info_out, ctx->ws[WS_INFO].p, sizeof(loamx_reg_information), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return LOAMX_OK;
+  }
   HIP_TRY(ctx, hipMemcpyAsync(result, ctx->ws[WS_RESULTS].p, sizeof(loamx_reg_result), hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   if (detail && detail->iter_info && result->iterations) {
@@ -1255,6 +1293,23 @@ int loamx_register_features_indexed(loamx_ctx* ctx, const loamx_target_index* in
   if (!index) return LOAMX_ERR_BAD_PARAM;
   return register_features_impl(ctx, index, {{src_edge, src_planar}, {n_se, n_sp}}, {{nullptr, nullptr}, {0, 0}}, init_pose, reg, result,
                                 detail);
+}
+
+/* ---- registration information matrix, one pair from host memory ---------------------------------------------- */
+int loamx_registration_information(loamx_ctx* ctx, const double* src_edge, size_t n_se, const double* src_planar, size_t n_sp,
+                                   const double* tgt_edge, size_t n_te, const double* tgt_planar, size_t n_tp, const double pose[7],
+                                   const loamx_reg_params* reg, loamx_reg_information* info) {
+  if (!info) return LOAMX_ERR_BAD_PARAM;
+  return register_features_impl(ctx, nullptr, {{src_edge, src_planar}, {n_se, n_sp}}, {{tgt_edge, tgt_planar}, {n_te, n_tp}}, pose, reg, nullptr,
+                                nullptr, nullptr, info);
+}
+
+int loamx_registration_information_indexed(loamx_ctx* ctx, const loamx_target_index* index, const double* src_edge, size_t n_se,
+                                           const double* src_planar, size_t n_sp, const double pose[7], const loamx_reg_params* reg,
+                                           loamx_reg_information* info) {
+  if (!index || !info) return LOAMX_ERR_BAD_PARAM;
+  return register_features_impl(ctx, index, {{src_edge, src_planar}, {n_se, n_sp}}, {{nullptr, nullptr}, {0, 0}}, pose, reg, nullptr, nullptr,
+                                nullptr, info);
 }
 
 /* ---- rows a16-a19 one by one ------------------------------------------------------------------------------ */
@@ -1913,12 +1968,12 @@ int loamx_extract_features_batch_dev_f32(loamx_ctx* ctx, const float* d_xyz, siz
   return extract_batch_dev(ctx, d_xyz, true, n_scans, lidar, fe, d_edge_idx, d_n_edge, d_edge_xyz, d_planar_idx, d_n_planar, d_planar_xyz);
 }
 
-int loamx_register_features_batch_dev(loamx_ctx* ctx, size_t n_pairs, const double* d_src_edge,
-                                      const uint32_t* d_n_src_edge, const double* d_src_planar,
-                                      const uint32_t* d_n_src_planar, const double* d_tgt_edge,
-                                      const uint32_t* d_n_tgt_edge, const double* d_tgt_planar,
-                                      const uint32_t* d_n_tgt_planar, size_t edge_stride, size_t planar_stride,
-                                      const double* d_init, const loamx_reg_params* reg, loamx_reg_result* d_results) {
+// (d_info != nullptr: loamx_registration_information_batch_dev — d_init holds the poses, d_results is not used)
+static int register_features_batch(loamx_ctx* ctx, size_t n_pairs, const double* d_src_edge, const uint32_t* d_n_src_edge,
+                                   const double* d_src_planar, const uint32_t* d_n_src_planar, const double* d_tgt_edge,
+                                   const uint32_t* d_n_tgt_edge, const double* d_tgt_planar, const uint32_t* d_n_tgt_planar,
+                                   size_t edge_stride, size_t planar_stride, const double* d_init, const loamx_reg_params* reg,
+                                   loamx_reg_result* d_results, loamx_reg_information* d_info) {
   if (!ctx) return LOAMX_ERR_BAD_PARAM;
   std::lock_guard<std::mutex> lock(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1943,7 +1998,34 @@ int loamx_register_features_batch_dev(loamx_ctx* ctx, size_t n_pairs, const doub
       if (rc != LOAMX_OK) return rc;
     }
   }
-  return register_dev(ctx, in, C, d_results, false, nullptr, nullptr);
+  const InfoRequest info_req{d_info, true};
+  return register_dev(ctx, in, C, d_results, false, nullptr, nullptr, nullptr, nullptr, nullptr, d_info ? &info_req : nullptr);
+}
+
+int loamx_register_features_batch_dev(loamx_ctx* ctx, size_t n_pairs, const double* d_src_edge,
+                                      const uint32_t* d_n_src_edge, const double* d_src_planar,
+                                      const uint32_t* d_n_src_planar, const double* d_tgt_edge,
+                                      const uint32_t* d_n_tgt_edge, const double* d_tgt_planar,
+                                      const uint32_t* d_n_tgt_planar, size_t edge_stride, size_t planar_stride,
+                                      const double* d_init, const loamx_reg_params* reg, loamx_reg_result* d_results) {
+  return register_features_batch(ctx, n_pairs, d_src_edge, d_n_src_edge, d_src_planar, d_n_src_planar, d_tgt_edge, d_n_tgt_edge, d_tgt_planar,
+                                 d_n_tgt_planar, edge_stride, planar_stride, d_init, reg, d_results, nullptr);
+}
+
+int loamx_registration_information_batch_dev(loamx_ctx* ctx, size_t n_pairs, const double* d_src_edge,
+                                             const uint32_t* d_n_src_edge, const double* d_src_planar,
+                                             const uint32_t* d_n_src_planar, const double* d_tgt_edge,
+                                             const uint32_t* d_n_tgt_edge, const double* d_tgt_planar,
+                                             const uint32_t* d_n_tgt_planar, size_t edge_stride, size_t planar_stride,
+                                             const double* d_pose, const loamx_reg_params* reg, loamx_reg_information* d_info) {
+  if (!ctx) return LOAMX_ERR_BAD_PARAM;
+  if (n_pairs != 0 && (!d_info || !d_n_src_edge || !d_n_src_planar || !d_n_tgt_edge || !d_n_tgt_planar || !d_src_edge || !d_src_planar ||
+                       !d_tgt_edge || !d_tgt_planar)) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  }
+  return register_features_batch(ctx, n_pairs, d_src_edge, d_n_src_edge, d_src_planar, d_n_src_planar, d_tgt_edge, d_n_tgt_edge, d_tgt_planar,
+                                 d_n_tgt_planar, edge_stride, planar_stride, d_pose, reg, nullptr, d_info);
 }
 
 // How the scans of a call lie in memory. Interleaved pairs: n_pairs x 2 scans, pair p = (scan 2p target, scan 2p + 1 source).
@@ -1953,7 +2035,8 @@ enum class ScanLayout { kPairs, kSequence };
 // d_init: n_pairs x 7 doubles or nullptr = identity)
 static int register_scan_pairs_locked(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_pairs, const loamx_lidar_params* lidar,
                                       const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results, bool look = false,
-                                      ScanLayout layout = ScanLayout::kPairs, const double* d_init = nullptr) {
+                                      ScanLayout layout = ScanLayout::kPairs, const double* d_init = nullptr,
+                                      loamx_reg_information* d_info = nullptr) {
   ExtractParams P;
   int rc = make_extract_params(ctx, lidar, fe, P);
   if (rc != LOAMX_OK) return rc;
@@ -1991,15 +2074,16 @@ static int register_scan_pairs_locked(loamx_ctx* ctx, const void* d_xyz, bool f3
     in.kind[k] = RegInputs::Kind{cap[k], xyz + cap[k] * 3, xyz, count + 1, count};
   }
   in.init = d_init;
-  return register_dev(ctx, in, C, d_results, false, nullptr, nullptr);
+  const InfoRequest info_req{d_info, false};
+  return register_dev(ctx, in, C, d_results, false, nullptr, nullptr, nullptr, nullptr, nullptr, d_info ? &info_req : nullptr);
 }
 static int register_scan_pairs(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_pairs, const loamx_lidar_params* lidar,
                                const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results,
-                               ScanLayout layout = ScanLayout::kPairs, const double* d_init = nullptr) {
+                               ScanLayout layout = ScanLayout::kPairs, const double* d_init = nullptr, loamx_reg_information* d_info = nullptr) {
   if (!ctx) return LOAMX_ERR_BAD_PARAM;
   std::lock_guard<std::mutex> lock(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  return register_scan_pairs_locked(ctx, d_xyz, f32, n_pairs, lidar, fe, reg, d_results, false, layout, d_init);
+  return register_scan_pairs_locked(ctx, d_xyz, f32, n_pairs, lidar, fe, reg, d_results, false, layout, d_init, d_info);
 }
 
 // Host memory in, host memory out (loamx.h: loamx_register_scan_pairs): chunk k + 1 is uploaded on the copy stream into the
@@ -2104,6 +2188,38 @@ int loamx_register_scan_pairs_dev(loamx_ctx* ctx, const double* d_xyz, size_t n_
 int loamx_register_scan_pairs_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_pairs, const loamx_lidar_params* lidar,
                                       const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results) {
   return register_scan_pairs(ctx, d_xyz, true, n_pairs, lidar, fe, reg, d_results);
+}
+
+// (the "_info" forms: the same static helpers with a place for the information records)
+static int register_scan_pairs_info(loamx_ctx* ctx, const void* d_xyz, bool f32, size_t n_pairs, const loamx_lidar_params* lidar,
+                                    const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results, ScanLayout layout,
+                                    const double* d_init, loamx_reg_information* d_info) {
+  if (!ctx) return LOAMX_ERR_BAD_PARAM;
+  if (n_pairs != 0 && (!d_info || !d_results || !d_xyz)) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  }
+  return register_scan_pairs(ctx, d_xyz, f32, n_pairs, lidar, fe, reg, d_results, layout, d_init, d_info);
+}
+int loamx_register_scan_pairs_info_dev(loamx_ctx* ctx, const double* d_xyz, size_t n_pairs, const loamx_lidar_params* lidar,
+                                       const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results,
+                                       loamx_reg_information* d_info) {
+  return register_scan_pairs_info(ctx, d_xyz, false, n_pairs, lidar, fe, reg, d_results, ScanLayout::kPairs, nullptr, d_info);
+}
+int loamx_register_scan_pairs_info_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_pairs, const loamx_lidar_params* lidar,
+                                           const loamx_fe_params* fe, const loamx_reg_params* reg, loamx_reg_result* d_results,
+                                           loamx_reg_information* d_info) {
+  return register_scan_pairs_info(ctx, d_xyz, true, n_pairs, lidar, fe, reg, d_results, ScanLayout::kPairs, nullptr, d_info);
+}
+int loamx_register_scan_sequence_info_dev(loamx_ctx* ctx, const double* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                                          const loamx_fe_params* fe, const loamx_reg_params* reg, const double* d_init,
+                                          loamx_reg_result* d_results, loamx_reg_information* d_info) {
+  return register_scan_pairs_info(ctx, d_xyz, false, n_scans < 2 ? 0 : n_scans - 1, lidar, fe, reg, d_results, ScanLayout::kSequence, d_init, d_info);
+}
+int loamx_register_scan_sequence_info_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_scans, const loamx_lidar_params* lidar,
+                                              const loamx_fe_params* fe, const loamx_reg_params* reg, const double* d_init,
+                                              loamx_reg_result* d_results, loamx_reg_information* d_info) {
+  return register_scan_pairs_info(ctx, d_xyz, true, n_scans < 2 ? 0 : n_scans - 1, lidar, fe, reg, d_results, ScanLayout::kSequence, d_init, d_info);
 }
 
 /* ---- scan sequences: scan i is the source of pair i - 1 and the target of pair i ----------------------------- */

@@ -311,6 +311,20 @@ void launch_knn_queries(const GridSet& gs, const double* d_q, size_t n_q, int k,
                         hipStream_t s);
 void launch_assoc_dump(const RegBatch& B, const RegConfig& C, const AssocDumpSet (&out)[2], hipStream_t s);
 
+/* ---- registration information matrix (info_kernels.hip; arithmetic: info_math.h) -------------------------------- */
+// what information_kernel leaves per (pair, chunk of the pair's association slots): the 21 + 6 + 1 sums of info_math.h
+// (InfoAcc::s) and the counters n_edge, n_plane, n_huber, n_dropped
+struct InfoPartial {
+  double s[28];
+  uint32_t c[4];
+};
+uint32_t info_blocks_per_pair(size_t edge_stride, size_t plane_stride);  // partials per pair at these capacities
+// marks every pair active for ONE more association pass (the association kernels leave at once for a pair that has stopped);
+// est, termination and iterations are not touched
+void launch_info_activate(const RegBatch& B, hipStream_t s);
+// behind launch_associate: partials[n_pairs][info_blocks_per_pair], one record per pair
+void launch_information(const RegBatch& B, InfoPartial* partials, loamx_reg_information* d_info, hipStream_t s);
+
 /* ---- non-finite input check of the "_dev" entry points (context option CHECK_FINITE; synth_kernels.hip) --------- */
 // sets of `stride` points, `pitch` sets apart; d_n: points held by set i at d_n[i * pitch], or nullptr = all `stride`
 void launch_check_finite(const void* d_pts, bool f32, const uint32_t* d_n, size_t n_sets, size_t stride, uint32_t pitch, uint32_t* d_flag,

@@ -5,3 +5,4 @@ from .loam_python import (FeatureExtractionParams, LidarParams, LoamFeatures, Po
                           RegistrationTerminationType, computeCurvature, computeValidPoints, extractFeatures,
                           registerFeatures)
 from .loam_python import deskewScan, registerScanSequence  # noqa: F401  (extensions: scan sequences)
+from .loam_python import RegistrationInformation, registrationInformation  # noqa: F401  (extension: information matrix)

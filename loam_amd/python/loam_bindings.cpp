@@ -228,6 +228,12 @@ Arr rows_to_array(const std::vector<double>& xyz) {
   if (!xyz.empty()) std::memcpy(out.mutable_data(), xyz.data(), xyz.size() * sizeof(double));
   return out;
 }
+// rows x cols doubles as a new array (cols == 1: a vector of `rows` entries)
+Arr matrix_to_array(const double* v, size_t rows, size_t cols) {
+  Arr out(cols == 1 ? std::vector<py::ssize_t>{(py::ssize_t)rows} : std::vector<py::ssize_t>{(py::ssize_t)rows, (py::ssize_t)cols});
+  if (rows * cols) std::memcpy(out.mutable_data(), v, rows * cols * sizeof(double));
+  return out;
+}
 
 }  // namespace
 
@@ -388,6 +394,49 @@ PYBIND11_MODULE(loam_python, m) {
       },
       py::arg("source"), py::arg("target_index"), py::arg("target_T_source_init"), py::arg("params") = loam::RegistrationParams(),
       py::arg("detail") = std::shared_ptr<loam::RegistrationDetail>());
+  // the information matrix of a pair's residuals at a pose (include/loamx.h: loamx_reg_information)
+  py::class_<loam::RegistrationInformation>(m, "RegistrationInformation")
+      .def_property_readonly("information", [](const loam::RegistrationInformation& r) { return matrix_to_array(r.information, 6, 6); })
+      .def_property_readonly("eigenvalues", [](const loam::RegistrationInformation& r) { return matrix_to_array(r.eigenvalues, 6, 1); })
+      .def_property_readonly("eigenvectors", [](const loam::RegistrationInformation& r) { return matrix_to_array(r.eigenvectors, 6, 6); })
+      .def_property_readonly("gradient", [](const loam::RegistrationInformation& r) { return matrix_to_array(r.gradient, 6, 1); })
+      .def_readonly("weighted_sq_error", &loam::RegistrationInformation::weighted_sq_error)
+      .def_readonly("n_edge", &loam::RegistrationInformation::n_edge)
+      .def_readonly("n_plane", &loam::RegistrationInformation::n_plane)
+      .def_readonly("n_huber", &loam::RegistrationInformation::n_huber)
+      .def_readonly("n_dropped", &loam::RegistrationInformation::n_dropped)
+      .def(
+          "covariance",
+          [](const loam::RegistrationInformation& r, double rel_threshold) {
+            if (r.n_edge + r.n_plane <= 6) throw py::value_error("covariance: not more than 6 residual rows");
+            return matrix_to_array(r.covariance(rel_threshold).data(), 6, 6);
+          },
+          py::arg("rel_threshold") = 1e-12)
+      .def(
+          "degenerateDirections",
+          [](const loam::RegistrationInformation& r, double min_eigenvalue) {
+            std::vector<double> flat;
+            for (const std::vector<double>& v : r.degenerateDirections(min_eigenvalue)) flat.insert(flat.end(), v.begin(), v.end());
+            return matrix_to_array(flat.data(), flat.size() / 6, 6);
+          },
+          py::arg("min_eigenvalue"));
+  m.def(
+      "registrationInformation",
+      [](const PyFeatures& source, const PyFeatures& target, const loam::Pose3d& pose, const loam::RegistrationParams& params) {
+        const loam::LoamFeatures<Row> s = to_features(source, "source.edge_points", "source.planar_points");
+        const loam::LoamFeatures<Row> t = to_features(target, "target.edge_points", "target.planar_points");
+        py::gil_scoped_release release;
+        return loam::registrationInformation<loam::ParenAccessor>(s, t, pose, params);
+      },
+      py::arg("source"), py::arg("target"), py::arg("target_T_source"), py::arg("params") = loam::RegistrationParams());
+  m.def(
+      "registrationInformation",
+      [](const PyFeatures& source, const loam::TargetIndex& target, const loam::Pose3d& pose, const loam::RegistrationParams& params) {
+        const loam::LoamFeatures<Row> s = to_features(source, "source.edge_points", "source.planar_points");
+        py::gil_scoped_release release;
+        return loam::registrationInformation<loam::ParenAccessor>(s, target, pose, params);
+      },
+      py::arg("source"), py::arg("target_index"), py::arg("target_T_source"), py::arg("params") = loam::RegistrationParams());
   m.def("registerScanSequence", &register_scan_sequence<ArrF>, py::arg("scans"), py::arg("lidar_params"),
         py::arg("fe_params") = loam::FeatureExtractionParams(), py::arg("reg_params") = loam::RegistrationParams(),
         py::arg("inits") = py::none());
