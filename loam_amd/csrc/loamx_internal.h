@@ -11,7 +11,7 @@
 
 namespace loamx {
 
-/* ---- kernel launches with timing attached (loamx_api.hip: TimedScope) ------------------------------------
+/* ---- kernel launches with timing attached (api_host.h: TimedScope) ---------------------------------------
  * While a timing scope of the calling thread is in "attach" mode, the first kernel launched records the scope's
  * start event with its own begin and every kernel re-records the stop event with its end (the last one
  * stands): hipExtLaunchKernelGGL takes the timestamps from the dispatch itself, so no marker packets sit between
