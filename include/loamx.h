@@ -158,6 +158,38 @@ enum {
   LOAMX_ROUTE_ROWS_CH_SHIFT = 24        /* 6 bits: points of a sector per lane of the row kernels (RowSelGeom::ch) */
 };
 int loamx_ctx_last_extract_route(loamx_ctx* ctx, uint32_t* bits);
+/* Debug / measurement (no reference counterpart): what the solve kernels of the LAST registration enqueued on this context
+ * worked on for one of its pairs — which of their record walks a test of "form F at shape X" really ran. Nothing is recorded
+ * by the kernels for it: the call synchronises the stream and copies from the workspace the registration wrote anyway, which
+ * holds the state of the pair's last completed ICF iteration (a test reads iteration i by running with max_iterations =
+ * i + 1 and asking for iterations == i + 1). The source counts are read through the count pointers the call was given: the
+ * context's own copies for the host entry points; for the "_dev" entry points the CALLER's arrays, which must still be
+ * allocated. Valid from a registration until the next registration, association dump or information call on the context
+ * (they size the workspace anew). LOAMX_ERR_BAD_PARAM before any registration and when `pair` is out of range. Never part of
+ * a result. */
+enum {
+  LOAMX_WALK_NONE = 0,           /* no moment pass in that iteration (NO_MOMENTS, or the pair never started a solve): no lists */
+  LOAMX_WALK_FLAT = 1,           /* the listed plane records as one flat list in LDS */
+  LOAMX_WALK_TILED_BY_COUNT = 2, /* tile by tile: more than flat_cache listed records */
+  LOAMX_WALK_TILED_BY_TILES = 3  /* tile by tile: the call's plane capacity makes more than list_cache tiles */
+};
+typedef struct {
+  uint32_t iterations, termination; /* PairState: as in the pair's result record */
+  uint32_t use_moments;             /* PairState: the pair's next solve would take the moment pass (0 under NO_MOMENTS) */
+  uint32_t mom_ref_on;              /* PairState: the moments were taken at the first candidate (first ICF iteration) ... */
+  double mom_ref[7];                /* ... this one */
+  uint32_t tiles;                   /* moment tiles per pair of the call: 4 per sweep_chunk slots of plane capacity */
+  uint32_t live_tiles;              /* tiles t with (t / 4) * sweep_chunk < n_sp: the ones the kernels look at */
+  uint64_t edge_stride, planar_stride; /* slot capacities of the call */
+  uint32_t n_se, n_sp;              /* the pair's source counts, clamped to the capacities */
+  uint32_t walk;                    /* LOAMX_WALK_*: what the constants below imply for listed_total and tiles */
+  uint32_t listed_total;            /* listed plane records (|s| > 0.5 at the reference point) over the live tiles */
+  double s0max, v2max;              /* the two maxima behind the moments' validity bound (0 under LOAMX_WALK_NONE) */
+  uint32_t sweep_chunk, edge_cache, list_cache, flat_cache; /* the kernels' constants */
+  uint32_t* tile_counts;            /* in: room for tile_counts_cap words or NULL; out: listed records of the first */
+  size_t tile_counts_cap;           /*     min(live_tiles, tile_counts_cap) live tiles */
+} loamx_solve_census;
+int loamx_ctx_last_solve_census(loamx_ctx* ctx, size_t pair, loamx_solve_census* out);
 /* Debug / measurement switches of ONE context (no reference counterpart). loamx_ctx_create reads the environment
  * variables LOAMX_<NAME> once as the defaults (set = 1); no entry point looks at the environment afterwards, and a
  * switch only ever affects the context it was set on. None changes a result beyond the order in which a pair's residual

@@ -154,7 +154,7 @@ EXPORTS = [
     "loamx_target_index_insert", "loamx_target_index_size",
     "loamx_shard_range", "loamx_comm_get_unique_id", "loamx_comm_create", "loamx_comm_wrap", "loamx_comm_destroy",
     "loamx_comm_info", "loamx_gather_results_dev", "loamx_comm_barrier", "loamx_comm_stats", "loamx_ctx_extract_counters",
-    "loamx_ctx_set_option", "loamx_ctx_get_option", "loamx_ctx_last_extract_route",
+    "loamx_ctx_set_option", "loamx_ctx_get_option", "loamx_ctx_last_extract_route", "loamx_ctx_last_solve_census",
     "loamx_fit_lines", "loamx_fit_planes", "loamx_knn_search", "loamx_associate", "loamx_target_index_stats",
     "loamx_register_scan_sequence_dev", "loamx_register_scan_sequence_dev_f32", "loamx_register_scan_sequence",
     "loamx_register_scan_sequence_f32", "loamx_compose_trajectory_dev", "loamx_deskew_scans_dev", "loamx_deskew_scans_dev_f32",
@@ -188,6 +188,23 @@ class ExtractRoute:
     def __repr__(self):
         return "ExtractRoute(%s%s)" % ("|".join(n for n in ROUTE_BITS if n in self.names),
                                        ", R=%d ch=%d" % (self.rows_R, self.rows_ch) if "ROWS" in self.names else "")
+
+
+class SolveCensusStruct(C.Structure):
+    """loamx_solve_census (include/loamx.h)"""
+    _fields_ = [("iterations", C.c_uint32), ("termination", C.c_uint32), ("use_moments", C.c_uint32), ("mom_ref_on", C.c_uint32),
+                ("mom_ref", C.c_double * 7), ("tiles", C.c_uint32), ("live_tiles", C.c_uint32),
+                ("edge_stride", C.c_uint64), ("planar_stride", C.c_uint64), ("n_se", C.c_uint32), ("n_sp", C.c_uint32),
+                ("walk", C.c_uint32), ("listed_total", C.c_uint32), ("s0max", C.c_double), ("v2max", C.c_double),
+                ("sweep_chunk", C.c_uint32), ("edge_cache", C.c_uint32), ("list_cache", C.c_uint32), ("flat_cache", C.c_uint32),
+                ("tile_counts", C.POINTER(C.c_uint32)), ("tile_counts_cap", C.c_size_t)]
+
+
+WALK_NONE, WALK_FLAT, WALK_TILED_BY_COUNT, WALK_TILED_BY_TILES = 0, 1, 2, 3
+WALK_NAMES = ("none", "flat", "tiled-by-count", "tiled-by-tiles")
+SolveCensus = collections.namedtuple(
+    "SolveCensus", "iterations termination use_moments mom_ref_on mom_ref tiles live_tiles edge_stride planar_stride n_se n_sp walk "
+                   "listed_total s0max v2max sweep_chunk edge_cache list_cache flat_cache tile_counts")
 
 
 _lib = None
@@ -304,6 +321,7 @@ def load(build_if_missing=True):
     lib.loamx_ctx_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     lib.loamx_ctx_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int)]
     lib.loamx_ctx_last_extract_route.argtypes = [vp, C.POINTER(C.c_uint32)]
+    lib.loamx_ctx_last_solve_census.argtypes = [vp, C.c_size_t, C.POINTER(SolveCensusStruct)]
     lib.loamx_registration_information.argtypes = [vp, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp,
                                                    C.POINTER(RegistrationParams), C.POINTER(RegInformation)]
     lib.loamx_registration_information_indexed.argtypes = [vp, vp, dp, C.c_size_t, dp, C.c_size_t, dp, C.POINTER(RegistrationParams),
@@ -504,6 +522,18 @@ class Context:
         v = C.c_uint32(0)
         self._check(self.lib.loamx_ctx_last_extract_route(self.h, C.byref(v)))
         return ExtractRoute(v.value)
+
+    def last_solve_census(self, pair=0):
+        """what the solve kernels of the last registration on this context worked on for `pair` (include/loamx.h:
+        loamx_ctx_last_solve_census), as a SolveCensus; tile_counts = the listed plane records of every live moment tile"""
+        v = SolveCensusStruct()
+        self._check(self.lib.loamx_ctx_last_solve_census(self.h, pair, C.byref(v)))  # (no array: the number of live tiles)
+        counts = np.zeros(max(1, v.live_tiles), dtype=np.uint32)
+        v.tile_counts, v.tile_counts_cap = counts.ctypes.data_as(C.POINTER(C.c_uint32)), v.live_tiles
+        self._check(self.lib.loamx_ctx_last_solve_census(self.h, pair, C.byref(v)))
+        return SolveCensus(v.iterations, v.termination, v.use_moments, v.mom_ref_on, np.array(list(v.mom_ref)), v.tiles, v.live_tiles,
+                           v.edge_stride, v.planar_stride, v.n_se, v.n_sp, v.walk, v.listed_total, v.s0max, v.v2max, v.sweep_chunk,
+                           v.edge_cache, v.list_cache, v.flat_cache, counts[:v.live_tiles].copy())
 
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)

@@ -76,6 +76,11 @@ struct loamx_ctx {
   hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
 
   uint32_t last_extract_route = 0;  // LOAMX_ROUTE_* of the last extract_dev call (loamx_ctx_last_extract_route)
+  // the last reg_solve's call as loamx_ctx_last_solve_census reads it: device pointers into the workspace (and to the call's
+  // count arrays), good from reg_solve until the next reg_prepare sizes the workspace anew
+  loamx::RegBatch last_solve_batch = {};
+  uint32_t last_solve_flags = 0;  // RegConfig::flags of that call
+  bool last_solve_valid = false;
 
   unsigned long long sweep_slots_base[2] = {0, 0};
   unsigned long long features_base = 0;  // events[2] at the last loamx_ctx_reset_kernel_stats

@@ -101,6 +101,7 @@ namespace loamx {
 
 int reg_prepare(loamx_ctx* ctx, const RegInputs& in, RegConfig& C, const loamx_target_index* prebuilt, const RegPrepareOpts& opts, RegBatch& B) {
   B = RegBatch{};
+  ctx->last_solve_valid = false;  // (the workspace the solve readout points into may move below)
   if (in.n_pairs == 0) return LOAMX_OK;
   if (opts.one_pass && C.max_iterations == 0) C.max_iterations = 1;
   untimed(ctx);
@@ -289,6 +290,7 @@ int reg_information(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, InfoP
 int reg_solve(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, loamx_reg_result* d_results, AfterAssocHook hook, void* hook_user) {
   if (B.n_pairs == 0) return LOAMX_OK;
   hipStream_t s = ctx->stream;
+  ctx->last_solve_batch = B, ctx->last_solve_flags = C.flags, ctx->last_solve_valid = true;  // (loamx_ctx_last_solve_census)
   // (Replaying an ICF iteration as a hipGraph was measured in round 2 — captured once, cached, ~110 kernel nodes over
   // three streams: 13.6 vs 13.1 ms per 1 024-pair step and 1.06 vs 1.07 ms for one pair. The GPU-side turnaround of
   // dependent kernels bounds both, not the host's launch rate, and the graph loses the stream priorities; removed.)
@@ -494,6 +496,53 @@ int loamx_registration_information_indexed(loamx_ctx* ctx, const loamx_target_in
   if (!index || !info) return LOAMX_ERR_BAD_PARAM;
   return register_features_impl(ctx, index, {{src_edge, src_planar}, {n_se, n_sp}}, {{nullptr, nullptr}, {0, 0}}, pose, reg,
                                 HostOutput::to_info(info));
+}
+
+/* ---- solve readout (debug / tests): copies of what the last reg_solve left in the workspace, no kernel involved ---- */
+int loamx_ctx_last_solve_census(loamx_ctx* ctx, size_t pair, loamx_solve_census* out) {
+  if (!out) return LOAMX_ERR_BAD_PARAM;
+  API_ENTER(ctx);
+  if (!ctx->last_solve_valid) return fail(ctx, LOAMX_ERR_BAD_PARAM, "no registration on this context to read (or its workspace has been handed on since)");
+  const RegBatch& B = ctx->last_solve_batch;
+  if (pair >= B.n_pairs) return fail(ctx, LOAMX_ERR_BAD_PARAM, "pair out of range");
+  hipStream_t s = ctx->stream;
+  untimed(ctx);
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  PairState S;
+  uint32_t n_raw[2] = {0, 0};
+  HIP_TRY(ctx, hipMemcpy(&S, B.state + pair, sizeof(S), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 2; k++) HIP_TRY(ctx, hipMemcpy(&n_raw[k], B.kind[k].n_src + pair * B.in_pitch, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  uint32_t* const counts_out = out->tile_counts;
+  const size_t cap = counts_out ? out->tile_counts_cap : 0;
+  *out = loamx_solve_census{};
+  out->tile_counts = counts_out, out->tile_counts_cap = cap;
+  out->iterations = S.iterations, out->termination = S.termination, out->use_moments = S.use_moments, out->mom_ref_on = S.mom_ref_on;
+  for (int i = 0; i < 7; i++) out->mom_ref[i] = S.mom_ref[i];
+  out->tiles = B.mom_blocks_per_pair * 4;
+  out->edge_stride = B.kind[kEdge].stride, out->planar_stride = B.kind[kPlane].stride;
+  out->n_se = n_raw[kEdge] < B.kind[kEdge].stride ? n_raw[kEdge] : (uint32_t)B.kind[kEdge].stride;  // (as the kernels clamp them)
+  out->n_sp = n_raw[kPlane] < B.kind[kPlane].stride ? n_raw[kPlane] : (uint32_t)B.kind[kPlane].stride;
+  out->sweep_chunk = (uint32_t)kSweepChunk, out->edge_cache = kEdgeCache, out->list_cache = kListCache, out->flat_cache = kFlatCache;
+  uint32_t live = 0;
+  while (live < out->tiles && (size_t)(live / 4) * kSweepChunk < out->n_sp) live++;
+  out->live_tiles = live;
+  // Did moment_kernel and lm_pair_loop_kernel run in the pair's last completed iteration? In every iteration but the first
+  // unless NO_MOMENTS; in the first one when the moments were taken at its first candidate. Otherwise nobody wrote the tile
+  // counts and the maxima (or an earlier call did): they are not looked at.
+  const bool lists = !(ctx->last_solve_flags & kRegFlagNoMoments) && (S.iterations >= 2u || S.mom_ref_on != 0u);
+  if (!lists) return LOAMX_OK;  // walk = LOAMX_WALK_NONE
+  double maxima[2];
+  HIP_TRY(ctx, hipMemcpy(maxima, B.moments + pair * (size_t)(kMomSize + 2) + kMomSize, sizeof(maxima), hipMemcpyDeviceToHost));
+  out->s0max = maxima[0], out->v2max = maxima[1];
+  std::vector<uint32_t> cnt(live);
+  if (live) HIP_TRY(ctx, hipMemcpy(cnt.data(), B.flagged_count + pair * (size_t)out->tiles, live * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (uint32_t t = 0; t < live; t++) {
+    out->listed_total += cnt[t];
+    if (t < cap) counts_out[t] = cnt[t];
+  }
+  // lm_pair_loop_kernel: the flat list needs the tile counts in LDS (tiles <= kListCache) and room for the records
+  out->walk = out->tiles > kListCache ? LOAMX_WALK_TILED_BY_TILES : (out->listed_total > kFlatCache ? LOAMX_WALK_TILED_BY_COUNT : LOAMX_WALK_FLAT);
+  return LOAMX_OK;
 }
 
 /* ---- rows a16-a19 one by one ------------------------------------------------------------------------------ */

@@ -217,6 +217,10 @@ constexpr int kSweepThreads = 256;
 #endif
 constexpr int kSweepItems = LOAMX_SWEEP_ITEMS;  // association slots per thread
 constexpr int kSweepChunk = kSweepThreads * kSweepItems;
+// what lm_pair_loop_kernel keeps in LDS for the length of a pair's solve (register_kernels.hip: light_eval)
+constexpr uint32_t kEdgeCache = 320;   // records (9 doubles each: 23 KB); a scan yields ~290 edge features
+constexpr uint32_t kListCache = 64;    // moment tiles of a pair (4 per chunk of kSweepChunk slots)
+constexpr uint32_t kFlatCache = 192;   // records (7 doubles each: 10.5 KB); more than that: the tile-by-tile walk
 
 struct RegBatch {
   size_t n_pairs;

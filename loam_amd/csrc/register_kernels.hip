@@ -1722,13 +1722,11 @@ __device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOM
 // Kept in LDS for the whole solve of a pair (lm_pair_loop_kernel), because every one of its <= 5 evaluations reads them
 // and from global memory they were dependent round trips on the one wavefront's critical path (measured per evaluation
 // of a single pair: 20 counts of listed records, one after the other, 5.2 us; edge records 4.2 us of a 15 us evaluation):
-// the pair's edge records and the numbers of listed plane records of its moment tiles.
-constexpr uint32_t kEdgeCache = 320;   // records (9 doubles each: 23 KB); a scan yields ~290 edge features
-constexpr uint32_t kListCache = 64;    // moment tiles of a pair (4 per chunk of kSweepChunk slots)
-// Round 5: the LISTED plane records of a pair (the ones its moments leave out: 0 - 1 % of the slots) as one flat list in LDS for
-// the whole solve, like the edge records. They were read tile by tile in every evaluation — up to 20 rounds of two dependent
+// the pair's edge records (kEdgeCache) and the numbers of listed plane records of its moment tiles (kListCache).
+// (The three constants: loamx_internal.h, where the host's solve readout sees them too.)
+// Round 5 (kFlatCache): the LISTED plane records of a pair (the ones its moments leave out: 0 - 1 % of the slots) as one flat list in
+// LDS for the whole solve, like the edge records. They were read tile by tile in every evaluation — up to 20 rounds of two dependent
 // global round trips with a handful of lanes each: a third of the kernel (stamped: 22 k of an evaluation's ~60 k cycles).
-constexpr uint32_t kFlatCache = 192;   // records (7 doubles each: 10.5 KB); more than that: the tile-by-tile walk
 __device__ __forceinline__ double light_eval(const RegBatch& B, size_t pair, const double x[7], uint32_t n_se, uint32_t n_sp,
                                              const double* mom, LightLds& L, const double (*s_edge)[kEdgeCache], const uint32_t* s_listed,
                                              const double (*s_frec)[kFlatCache], uint32_t n_flat) {

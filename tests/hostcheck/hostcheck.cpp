@@ -810,6 +810,162 @@ int hostcheck_register(const double* src_edge, uint64_t n_se, const double* src_
   return 0;
 }
 
+/* ---- the solve as the kernels launch it, with a census of its forms ------------------------------------------------
+ * hostcheck_register above streams the whole first ICF iteration; the kernels have not done that since round 4. This one
+ * follows enqueue_icf_iteration (api_register.hip): in the first iteration ONE evaluation of all records at the identity
+ * update and its bookkeeping step, then moments taken at the first candidate (plane_moments_valid_rel), then the loop of
+ * lm_pair_loop_kernel; later iterations as above. flags: 1 = NO_MOMENTS, 2 = NO_REF_MOMENTS. Per ICF iteration it reports
+ * what no result shows: how many plane records the moments left out (listed), how close any record came to the listing
+ * threshold, how many evaluations were made and how many of them streamed the records, and the listed records per moment
+ * tile — tile (q / sweep_chunk) * 4 + (q % sweep_threads) / 64 of slot q, the slots being the pair's source planar points in
+ * the order the ordered source build leaves them (grid_choose_morton over their bounding box, Morton code, then index). */
+struct hostcheck_iter_census {
+  uint32_t listed;          // plane records with |s| > kMomInlier at the reference point
+  uint32_t evals;           // evaluations of the normal equations in this iteration
+  uint32_t evals_streamed;  // ... that went over every record (no moments, or the candidate had left their bound)
+  uint32_t moments;         // 0: no moment pass; 1: moments at the identity update; 2: at the first candidate
+  double min_margin;        // smallest | |s| - kMomInlier | over the valid plane records (1e300: no moment pass, no record)
+  double s0max, v2max;      // what moment_kernel hands the validity bound
+  double mom_ref[7];        // the first candidate (moments == 2)
+};
+
+int hostcheck_register_forms(const double* src_edge, uint64_t n_se, const double* src_planar, uint64_t n_sp, const double* tgt_edge,
+                             uint64_t n_te, const double* tgt_planar, uint64_t n_tp, const double init[7], const loamx_reg_params* prm,
+                             uint32_t flags, uint32_t sweep_chunk, uint32_t sweep_threads, loamx_reg_result* out, loamx_iter_info* info,
+                             hostcheck_iter_census* census, uint32_t* tile_counts, uint64_t tiles_cap) {
+  HostGrid GE, GP;
+  build_grid(tgt_edge, (uint32_t)n_te, prm->max_edge_neighbor_dist, GE);
+  build_grid(tgt_planar, (uint32_t)n_tp, prm->max_plane_neighbor_dist, GP);
+  const bool no_moments = (flags & 1u) != 0, ref_moments = (flags & 3u) == 0;
+  // slot of every source planar point (launch_grid_build<true>)
+  std::vector<uint32_t> slot_of(n_sp);
+  {
+    Vec3 lo = v3(0, 0, 0), hi = v3(0, 0, 0);
+    for (uint64_t i = 0; i < n_sp; i++) {
+      const Vec3 p = v3(src_planar[3 * i], src_planar[3 * i + 1], src_planar[3 * i + 2]);
+      if (i == 0) lo = hi = p;
+      lo = v3(fmin(lo.x, p.x), fmin(lo.y, p.y), fmin(lo.z, p.z)), hi = v3(fmax(hi.x, p.x), fmax(hi.y, p.y), fmax(hi.z, p.z));
+    }
+    GridDesc g;
+    grid_choose_morton(g, lo, hi, (uint32_t)n_sp);
+    std::vector<std::pair<uint32_t, uint32_t>> key(n_sp);
+    for (uint64_t i = 0; i < n_sp; i++)
+      key[i] = {grid_morton_of_point(g, v3(src_planar[3 * i], src_planar[3 * i + 1], src_planar[3 * i + 2])), (uint32_t)i};
+    std::sort(key.begin(), key.end());
+    for (uint64_t r = 0; r < n_sp; r++) slot_of[key[r].second] = (uint32_t)r;
+  }
+  double est[7];
+  memcpy(est, init, sizeof(est));
+  uint32_t term = LOAMX_MAX_ITER, iters = 0;
+  for (uint64_t it = 0; it < prm->max_iterations; it++) {
+    hostcheck_iter_census& Cn = census[it];
+    Cn = hostcheck_iter_census{};
+    Cn.min_margin = 1e300;
+    uint32_t* tc = tile_counts ? tile_counts + it * tiles_cap : nullptr;
+    for (uint64_t t = 0; tc && t < tiles_cap; t++) tc[t] = 0;
+    std::vector<Slot> edges, planes;
+    const uint32_t ne = associate(src_edge, (uint32_t)n_se, tgt_edge, GE, est, false, prm, edges);
+    const uint32_t np = associate(src_planar, (uint32_t)n_sp, tgt_planar, GP, est, true, prm, planes);
+    if ((uint64_t)ne + np < prm->min_associations) {
+      term = LOAMX_INSUFFICIENT_ASSOCIATIONS;
+      break;
+    }
+    LmState st;
+    lm_init(st);
+    double acc[kAccSize];
+    bool first = true, use_moments = it >= 1 && !no_moments, ref_on = false;
+    double ref[7] = {0, 0, 0, 1, 0, 0, 0};
+    if (it == 0 && ref_moments) {  // sweep_kernel + lm_step_kernel, once
+      sweep(edges, planes, st.xeval, acc);
+      Cn.evals++, Cn.evals_streamed++;
+      lm_consume(st, acc, true);
+      first = false;
+      if (st.active) {  // lm_step_pair: the rest of the solve off moments taken at this candidate
+        use_moments = ref_on = true;
+        memcpy(ref, st.xeval, sizeof(ref));
+      }
+    }
+    std::vector<double> M(kMomSize + 2, 0.0);
+    std::vector<Slot> flagged;
+    if (use_moments && st.active) {  // moment_kernel
+      double phi_ref[kMomDim];
+      plane_phi(ref, phi_ref);
+      Cn.moments = ref_on ? 2u : 1u;
+      memcpy(Cn.mom_ref, ref, sizeof(ref));
+      for (uint64_t i = 0; i < n_sp; i++) {
+        const Slot& sl = planes[i];
+        if (!sl.valid) continue;
+        double c[kMomDim];
+        plane_coeffs(sl.p, v3(sl.prim[0], sl.prim[1], sl.prim[2]), sl.prim[3], c);
+        double sref = c[0];
+        if (ref_on) {
+          sref = 0.0;
+          for (int j = 0; j < kMomDim; j++) sref += c[j] * phi_ref[j];
+        }
+        const double a0 = fabs(sref);
+        Cn.min_margin = std::min(Cn.min_margin, fabs(a0 - kMomInlier));
+        if (!(a0 <= kMomInlier)) {
+          flagged.push_back(sl);
+          Cn.listed++;
+          const uint64_t q = slot_of[i], t = (q / sweep_chunk) * 4 + (q % sweep_threads) / 64;
+          if (tc && t < tiles_cap) tc[t]++;
+          continue;
+        }
+        for (int a = 0; a < kMomDim; a++)
+          for (int b = 0; b < kMomDim; b++) M[a * kMomStride + b] += c[a] * c[b];
+        M[kMomSize] = std::max(M[kMomSize], a0);
+        M[kMomSize + 1] = std::max(M[kMomSize + 1], vdot(sl.p, sl.p));
+      }
+      Cn.s0max = M[kMomSize], Cn.v2max = M[kMomSize + 1];
+    }
+    while (st.active) {  // lm_pair_loop_kernel (without moments: five sweep_kernel + lm_step_kernel launches; the same sums)
+      const bool valid = use_moments && (ref_on ? plane_moments_valid_rel(M[kMomSize], M[kMomSize + 1], st.xeval, ref)
+                                                : plane_moments_valid_at(M[kMomSize], M[kMomSize + 1], st.xeval));
+      sweep(edges, valid ? flagged : planes, st.xeval, acc);
+      if (valid) plane_eval_from_moments(M.data(), st.xeval, acc);
+      else Cn.evals_streamed++;
+      Cn.evals++;
+      lm_consume(st, acc, first);
+      first = false;
+    }
+    if (info) {
+      memcpy(info[it].target_T_source_init, est, sizeof(est));
+      memcpy(info[it].estimate_update, st.x_user, sizeof(est));
+      info[it].n_edge_associations = ne, info[it].n_plane_associations = np;
+    }
+    iters = (uint32_t)it + 1;
+    if (outer_update(est, st.x_user, prm->rotation_convergence_thresh, prm->position_convergence_thresh)) {
+      term = LOAMX_CONVERGED;
+      break;
+    }
+  }
+  memcpy(out->pose, est, sizeof(est));
+  out->termination = term, out->iterations = iters;
+  return 0;
+}
+
+// The kernels' own validity bounds (reg_math.h: plane_moments_valid_at, and plane_moments_valid_rel when r != nullptr) on given
+// maxima: out[0] = the verdict (1 / 0), out[1] = the bound's left-hand side as a number. The header functions only say whether
+// s0max + K(v2max, x[, r]) < 0.999; K is found from them by bisection over s0max (the largest s for which they still say yes is
+// 0.999 - K to the last bit or two), so that no second copy of the formula exists that a test could agree with by mistake.
+// +inf when K >= 1000.
+void hostcheck_moments_bound(double s0max, double v2max, const double x[7], const double* r, double out[2]) {
+  auto ok = [&](double s) { return r ? plane_moments_valid_rel(s, v2max, x, r) : plane_moments_valid_at(s, v2max, x); };
+  out[0] = ok(s0max) ? 1.0 : 0.0;
+  double lo = -1000.0, hi = 0.999;  // ok(hi) is false for every K >= 0
+  if (!ok(lo)) {
+    out[1] = HUGE_VAL;
+    return;
+  }
+  for (int i = 0; i < 200; i++) {
+    const double mid = lo + 0.5 * (hi - lo);
+    if (!(mid > lo && mid < hi)) break;
+    if (ok(mid)) lo = mid;
+    else hi = mid;
+  }
+  out[1] = s0max + (0.999 - lo);
+}
+
 void hostcheck_synth_scan(uint64_t seed, uint64_t pair, uint32_t which, uint32_t H, uint32_t W, double sigma, double* xyz) {
   const loamx_synth::Pose7 pose = loamx_synth::pair_pose(seed, pair);
   for (uint32_t l = 0; l < H; l++)

@@ -233,3 +233,44 @@ def moments_rel(v, n, d, x, r):
     out = np.zeros(4)
     lib().hostcheck_moments_rel(_dp(v), _dp(n), _dp(d), C.c_uint64(len(d)), _dp(x), _dp(r), _dp(out))
     return bool(out[0]), float(out[1]), float(out[2]), float(out[3])
+
+
+class IterCensus(C.Structure):
+    """hostcheck_iter_census (tests/hostcheck/hostcheck.cpp)"""
+    _fields_ = [("listed", C.c_uint32), ("evals", C.c_uint32), ("evals_streamed", C.c_uint32), ("moments", C.c_uint32),
+                ("min_margin", C.c_double), ("s0max", C.c_double), ("v2max", C.c_double), ("mom_ref", C.c_double * 7)]
+
+
+def register_forms(src_edge, src_planar, tgt_edge, tgt_planar, init=None, prm=None, no_moments=False, no_ref_moments=False,
+                   sweep_chunk=4096, sweep_threads=256, tiles=0):
+    """The registration with the kernels' own launch sequence (first ICF iteration: one evaluation, then moments at the first
+    candidate). Returns (pose, termination, iterations, [IterInfo], [census dict per started iteration]); a census holds
+    listed, evals, evals_streamed, moments (0 none / 1 at the identity / 2 at the first candidate), min_margin, s0max, v2max,
+    mom_ref and tile_counts (`tiles` words: listed records per moment tile of the pair's plane slots)."""
+    prm = prm or reg_params()
+    arrs = [np.ascontiguousarray(np.asarray(a, float).reshape(-1, 3)) for a in (src_edge, src_planar, tgt_edge, tgt_planar)]
+    init = np.ascontiguousarray([0, 0, 0, 1, 0, 0, 0] if init is None else init, dtype=np.float64)
+    res = RegResult()
+    mi = max(1, prm.max_iterations)
+    info = (IterInfo * mi)()
+    cen = (IterCensus * mi)()
+    tc = np.zeros((mi, max(1, tiles)), dtype=np.uint32)
+    lib().hostcheck_register_forms(_dp(arrs[0]), C.c_uint64(len(arrs[0])), _dp(arrs[1]), C.c_uint64(len(arrs[1])),
+                                   _dp(arrs[2]), C.c_uint64(len(arrs[2])), _dp(arrs[3]), C.c_uint64(len(arrs[3])),
+                                   _dp(init), C.byref(prm), C.c_uint32((1 if no_moments else 0) | (2 if no_ref_moments else 0)),
+                                   C.c_uint32(sweep_chunk), C.c_uint32(sweep_threads), C.byref(res), info, cen,
+                                   tc.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint64(tc.shape[1]))
+    census = [dict(listed=cen[i].listed, evals=cen[i].evals, evals_streamed=cen[i].evals_streamed, moments=cen[i].moments,
+                   min_margin=cen[i].min_margin, s0max=cen[i].s0max, v2max=cen[i].v2max, mom_ref=np.array(list(cen[i].mom_ref)),
+                   tile_counts=tc[i, :tiles].copy()) for i in range(res.iterations)]
+    return np.array(list(res.pose)), res.termination, res.iterations, [info[i] for i in range(res.iterations)], census
+
+
+def moments_bound(s0max, v2max, x, ref=None):
+    """(verdict, left-hand side) of the kernels' validity bound of the plane moments at candidate x: plane_moments_valid_at, or
+    plane_moments_valid_rel against the reference candidate `ref`; the moments stand in for the records while lhs < 0.999"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    r = None if ref is None else np.ascontiguousarray(ref, dtype=np.float64)
+    out = np.zeros(2)
+    lib().hostcheck_moments_bound(C.c_double(s0max), C.c_double(v2max), _dp(x), _dp(r) if r is not None else None, _dp(out))
+    return bool(out[0]), float(out[1])
