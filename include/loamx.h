@@ -275,6 +275,41 @@ int loamx_target_index_insert(loamx_ctx* ctx, loamx_target_index* index, const d
 int loamx_target_index_stats(const loamx_target_index* index, uint64_t* full_builds, uint64_t* merges);
 /* number of edge / planar points in the index (either pointer may be NULL) */
 int loamx_target_index_size(const loamx_target_index* index, size_t* n_edge, size_t* n_planar);
+/* Debug / measurement (no reference counterpart): one feature kind of a persistent index as it lies on the device, and which
+ * form of the index build made it — what a test of "build form F at shape X" asserts instead of assuming. `build`, the unit
+ * behind lds_passes / scan_tiles and the rule behind table_valid are recorded by the launcher at the place where it chooses
+ * the kernel, never derived from a second copy of its predicates (the rule of LOAMX_ROUTE_* above). Nothing is recorded by the
+ * kernels: the call synchronises the stream and copies from the index's own arrays. Never part of a result.
+ * LOAMX_ERR_BAD_PARAM: which_set not 0 / 1, a kind whose grid is not valid (a failed insert), a buffer too small. */
+enum {
+  LOAMX_INDEX_BUILD_NONE = 0,
+  LOAMX_INDEX_BUILD_PACKED = 1, /* grid_build_kernel<false, true>: one workgroup, 16-bit cell counters, cell order in LDS */
+  LOAMX_INDEX_BUILD_SINGLE = 2, /* grid_build_kernel<false, false>: one workgroup, 32-bit counters (NO_PACKED_GRID / NO_BIG_GRID) */
+  LOAMX_INDEX_BUILD_BIG = 3     /* the multi-workgroup gridbig_* kernels */
+};
+enum { LOAMX_INDEX_OP_NONE = 0, LOAMX_INDEX_OP_FULL_BUILD = 1, LOAMX_INDEX_OP_MERGE = 2 };
+typedef struct {
+  uint64_t n, capacity;          /* points of the kind / points its buffers hold without growing (the builds are chosen by it) */
+  double origin[3], h, inv_h;    /* the GridDesc, copied from the device */
+  int32_t nx, ny, nz;
+  uint32_t n_points;
+  uint32_t build;                /* LOAMX_INDEX_BUILD_*: the form of the kind's last FULL build */
+  uint32_t table_valid;          /* 0: that build left the cell table unwritten (single-workgroup forms, sets of at most 512 points) */
+  uint64_t table_entries;        /* capacity of the cell table: 65 536, or the map table's */
+  uint32_t lds_passes;           /* PACKED / SINGLE: ceil(nx ny nz / cells per LDS pass), else 0 */
+  uint32_t scan_tiles;           /* BIG: ceil(nx ny nz / entries per scan tile), else 0 */
+  uint32_t last_op, reserved;    /* LOAMX_INDEX_OP_*: what brought the kind to its present state */
+  uint64_t full_builds, merges;  /* of THIS kind (loamx_target_index_stats counts both kinds together) */
+  /* optional copies, NULL to skip; a capacity below the need is LOAMX_ERR_BAD_PARAM */
+  uint32_t* cell_start;          /* [nx ny nz + 1]; left untouched while table_valid == 0 */
+  size_t cell_start_cap;
+  double* xyz;                   /* [n][3] the cell-sorted points ... */
+  uint32_t* orig;                /* [n]    ... and their indices in insertion order */
+  size_t points_cap;
+  float* rel;                    /* [3][rel_cap]: the first n + 4 entries of each plane (the four pad entries included) */
+  size_t rel_cap;
+} loamx_index_census;
+int loamx_target_index_census(loamx_ctx* ctx, const loamx_target_index* index, int which_set, loamx_index_census* out);
 /* same contract as loamx_register_features, target taken from the index */
 int loamx_register_features_indexed(loamx_ctx* ctx, const loamx_target_index* index, const double* src_edge,
                                     size_t n_src_edge, const double* src_planar, size_t n_src_planar,

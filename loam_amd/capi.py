@@ -151,7 +151,7 @@ EXPORTS = [
     "loamx_copy_to_device", "loamx_copy_to_host",
     "loamx_compute_curvature_f32", "loamx_compute_valid_points_f32", "loamx_extract_features_f32",
     "loamx_extract_features_batch_dev_f32", "loamx_register_scan_pairs_dev_f32",
-    "loamx_target_index_insert", "loamx_target_index_size",
+    "loamx_target_index_insert", "loamx_target_index_size", "loamx_target_index_census",
     "loamx_shard_range", "loamx_comm_get_unique_id", "loamx_comm_create", "loamx_comm_wrap", "loamx_comm_destroy",
     "loamx_comm_info", "loamx_gather_results_dev", "loamx_comm_barrier", "loamx_comm_stats", "loamx_ctx_extract_counters",
     "loamx_ctx_set_option", "loamx_ctx_get_option", "loamx_ctx_last_extract_route", "loamx_ctx_last_solve_census",
@@ -207,6 +207,26 @@ SolveCensus = collections.namedtuple(
                    "listed_total s0max v2max sweep_chunk edge_cache list_cache flat_cache tile_counts")
 
 
+class IndexCensusStruct(C.Structure):
+    """loamx_index_census (include/loamx.h)"""
+    _fields_ = [("n", C.c_uint64), ("capacity", C.c_uint64), ("origin", C.c_double * 3), ("h", C.c_double), ("inv_h", C.c_double),
+                ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("n_points", C.c_uint32),
+                ("build", C.c_uint32), ("table_valid", C.c_uint32), ("table_entries", C.c_uint64),
+                ("lds_passes", C.c_uint32), ("scan_tiles", C.c_uint32), ("last_op", C.c_uint32), ("reserved", C.c_uint32),
+                ("full_builds", C.c_uint64), ("merges", C.c_uint64),
+                ("cell_start", C.POINTER(C.c_uint32)), ("cell_start_cap", C.c_size_t),
+                ("xyz", C.POINTER(C.c_double)), ("orig", C.POINTER(C.c_uint32)), ("points_cap", C.c_size_t),
+                ("rel", C.POINTER(C.c_float)), ("rel_cap", C.c_size_t)]
+
+
+INDEX_BUILD_NONE, INDEX_BUILD_PACKED, INDEX_BUILD_SINGLE, INDEX_BUILD_BIG = 0, 1, 2, 3
+INDEX_BUILD_NAMES = ("none", "packed", "single", "big")
+INDEX_OP_NONE, INDEX_OP_FULL_BUILD, INDEX_OP_MERGE = 0, 1, 2
+IndexCensus = collections.namedtuple(
+    "IndexCensus", "n capacity origin h inv_h dims n_points build table_valid table_entries lds_passes scan_tiles last_op full_builds "
+                   "merges cell_start xyz orig rel")
+
+
 _lib = None
 
 
@@ -254,6 +274,7 @@ def load(build_if_missing=True):
     lib.loamx_target_index_size.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     lib.loamx_target_index_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.loamx_target_index_points.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, dp]
+    lib.loamx_target_index_census.argtypes = [vp, vp, C.c_int, C.POINTER(IndexCensusStruct)]
     lib.loamx_voxel_filter_dev.argtypes = [vp, vp, C.c_size_t, dp, C.c_double, vp, vp, vp]
     lib.loamx_target_index_insert_filtered.argtypes = [vp, vp, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_double, C.c_double,
                                                        C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
@@ -672,6 +693,27 @@ class Context:
         a, b = C.c_uint64(0), C.c_uint64(0)
         self._check(self.lib.loamx_target_index_stats(index, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def target_index_census(self, index, which_set, arrays=True):
+        """One kind of a persistent index as it lies on the device and the build form behind it (include/loamx.h:
+        loamx_target_index_census), as an IndexCensus. arrays: cell_start (nx ny nz + 1; None while table_valid == 0), the
+        cell-sorted points xyz (n, 3) with orig (n,), and rel (3, n + 4) with the pad entries; False: None for all four."""
+        v = IndexCensusStruct()
+        self._check(self.lib.loamx_target_index_census(self.h, index, which_set, C.byref(v)))
+        cs = xyz = orig = rel = None
+        if arrays:
+            n, ncell = int(v.n), int(v.nx) * int(v.ny) * int(v.nz)
+            cs, xyz = np.zeros(ncell + 1, dtype=np.uint32), np.zeros((n, 3))
+            orig, rel = np.zeros(n, dtype=np.uint32), np.zeros((3, n + 4), dtype=np.float32)
+            v.cell_start, v.cell_start_cap = cs.ctypes.data_as(C.POINTER(C.c_uint32)), ncell + 1
+            v.xyz, v.orig, v.points_cap = _dp(xyz), orig.ctypes.data_as(C.POINTER(C.c_uint32)), n
+            v.rel, v.rel_cap = rel.ctypes.data_as(C.POINTER(C.c_float)), n + 4
+            self._check(self.lib.loamx_target_index_census(self.h, index, which_set, C.byref(v)))
+            if not v.table_valid:
+                cs = None
+        return IndexCensus(int(v.n), int(v.capacity), np.array(list(v.origin)), v.h, v.inv_h, (v.nx, v.ny, v.nz), v.n_points, v.build,
+                           v.table_valid, int(v.table_entries), v.lds_passes, v.scan_tiles, v.last_op, int(v.full_builds), int(v.merges),
+                           cs, xyz, orig, rel)
 
     # ---- map upkeep: voxel-filtered insert, crop, read-back (include/loamx.h, "map upkeep") ----------------
     @staticmethod

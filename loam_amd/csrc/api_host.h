@@ -107,6 +107,12 @@ struct loamx_target_index {
   size_t n_at_build[2] = {0, 0};
   bool grid_valid[2] = {false, false};  // the kind's cell-sorted arrays + table describe idx->pts[k][0 .. n[k]) (full build or merges since)
   uint64_t full_builds = 0, merges = 0;  // per kind: a call that rebuilds both kinds counts two
+  // what loamx_target_index_census reports per kind: the launcher's choice at the kind's last full build, whether that build
+  // (or a merge since) left a written cell table, the last operation (LOAMX_INDEX_OP_*) and the kind's own event counts
+  loamx::GridBuildForm build_form[2] = {{0u, 0u, 0u}, {0u, 0u, 0u}};
+  bool table_valid[2] = {false, false};
+  uint32_t last_op[2] = {0u, 0u};
+  uint64_t kind_builds[2] = {0, 0}, kind_merges[2] = {0, 0};
   // occupancy table of the filtered insert, one per kind (loamx_internal.h: VoxelTable; built by the first filtered insert).
   // While vox_valid[k]: owner[slot] = lowest index in pts[k] of any point of that voxel at leaf vox_leaf[k], over the
   // points [0, vox_n[k]) — plain inserts leave vox_n behind n, the next filtered insert catches up.

@@ -107,16 +107,21 @@ int index_build(loamx_ctx* ctx, loamx_target_index* idx, unsigned kinds = 3u) {
   for (int k = 0; k < 2; k++)
     B.kind[k].grid = index_grid_set(idx, k);
   untimed(ctx);
+  GridBuildForm form[2] = {{kGridBuildNone, 0u, 0u}, {kGridBuildNone, 0u, 0u}};
   {
     TimedScope t(ctx, LOAMX_K_GRID, 0.0);
     for (int k = 0; k < 2; k++)
-      if (kinds & (1u << k)) launch_grid_build_target(B, C, k, s);
+      if (kinds & (1u << k)) form[k] = launch_grid_build_target(B, C, k, s);
   }
   int rc = check_launch(ctx, "grid_build_kernel");
   if (rc != LOAMX_OK) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(s));
   for (int k = 0; k < 2; k++)
-    if (kinds & (1u << k)) idx->n_at_build[k] = idx->n[k], idx->grid_valid[k] = true, idx->full_builds++;
+    if (kinds & (1u << k)) {
+      idx->n_at_build[k] = idx->n[k], idx->grid_valid[k] = true, idx->full_builds++;
+      idx->build_form[k] = form[k], idx->table_valid[k] = idx->n[k] >= form[k].table_min_points;
+      idx->last_op[k] = LOAMX_INDEX_OP_FULL_BUILD, idx->kind_builds[k]++;
+    }
   return LOAMX_OK;
 }
 
@@ -225,6 +230,7 @@ int index_append_staged(loamx_ctx* ctx, loamx_target_index* idx, const double* c
     std::swap(idx->rel[k], idx->rel2[k]);
     idx->grid_valid[k] = true;
     idx->merges++;
+    idx->last_op[k] = LOAMX_INDEX_OP_MERGE, idx->kind_merges[k]++;
   }
   if (rebuild) return index_build(ctx, idx, rebuild);
   HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -375,6 +381,57 @@ int loamx_target_index_size(const loamx_target_index* index, size_t* n_edge, siz
   if (!index) return LOAMX_ERR_BAD_PARAM;
   if (n_edge) *n_edge = index->n[0];
   if (n_planar) *n_planar = index->n[1];
+  return LOAMX_OK;
+}
+
+int loamx_target_index_census(loamx_ctx* ctx, const loamx_target_index* index, int which_set, loamx_index_census* out) {
+  if (!ctx || !index) return LOAMX_ERR_BAD_PARAM;
+  API_ENTER(ctx);
+  if (!out) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  if (which_set != 0 && which_set != 1) return fail(ctx, LOAMX_ERR_BAD_PARAM, "which_set: 0 = edge points, 1 = planar points");
+  const int k = which_set;
+  if (!index->grid_valid[k]) return fail(ctx, LOAMX_ERR_BAD_PARAM, "this kind has no grid (its last build or insert failed)");
+  hipStream_t s = ctx->stream;
+  untimed(ctx);
+  GridDesc g;
+  HIP_TRY(ctx, hipMemcpyAsync(&g, index->desc[k], sizeof(GridDesc), hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  const size_t n = index->n[k], stride = index->cap[k] + kGridPad;
+  const GridBuildForm& f = index->build_form[k];
+  const uint64_t ncell = (uint64_t)g.nx * (uint64_t)g.ny * (uint64_t)g.nz;
+  out->n = n, out->capacity = index->cap[k];
+  out->origin[0] = g.ox, out->origin[1] = g.oy, out->origin[2] = g.oz;
+  out->h = g.h, out->inv_h = g.inv_h;
+  out->nx = g.nx, out->ny = g.ny, out->nz = g.nz, out->n_points = g.n_points;
+  out->build = f.form;
+  out->table_entries = index->cells_cap[k] ? index->cells_cap[k] : kGridCellsCap;
+  out->table_valid = index->table_valid[k] ? 1u : 0u;
+  const uint32_t units = f.unit_cells ? (uint32_t)((ncell + f.unit_cells - 1) / f.unit_cells) : 0u;
+  out->lds_passes = f.form == kGridBuildBig ? 0u : units;
+  out->scan_tiles = f.form == kGridBuildBig ? units : 0u;
+  out->last_op = index->last_op[k];
+  out->full_builds = index->kind_builds[k], out->merges = index->kind_merges[k];
+  if (ncell > out->table_entries) return fail(ctx, LOAMX_ERR_HIP, "the grid has more cells than its table has entries");
+  if (out->cell_start && out->table_valid) {
+    if (out->cell_start_cap < ncell + 1) return fail(ctx, LOAMX_ERR_BAD_PARAM, "cell_start_cap: nx * ny * nz + 1 entries are needed");
+    HIP_TRY(ctx, hipMemcpyAsync(out->cell_start, index->cells[k], (ncell + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  }
+  if ((out->xyz || out->orig) && out->points_cap < n) return fail(ctx, LOAMX_ERR_BAD_PARAM, "points_cap: n entries are needed");
+  std::vector<GridPoint> sorted;
+  if ((out->xyz || out->orig) && n) {
+    sorted.resize(n);
+    HIP_TRY(ctx, hipMemcpyAsync(sorted.data(), index->sorted[k], n * sizeof(GridPoint), hipMemcpyDeviceToHost, s));
+  }
+  if (out->rel) {
+    if (out->rel_cap < n + kGridPad) return fail(ctx, LOAMX_ERR_BAD_PARAM, "rel_cap: n + 4 entries per plane are needed");
+    for (int c = 0; c < 3; c++)
+      HIP_TRY(ctx, hipMemcpyAsync(out->rel + c * out->rel_cap, index->rel[k] + c * stride, (n + kGridPad) * sizeof(float), hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  for (size_t p = 0; p < sorted.size(); p++) {
+    if (out->xyz) out->xyz[3 * p] = sorted[p].x, out->xyz[3 * p + 1] = sorted[p].y, out->xyz[3 * p + 2] = sorted[p].z;
+    if (out->orig) out->orig[p] = sorted[p].orig;
+  }
   return LOAMX_OK;
 }
 

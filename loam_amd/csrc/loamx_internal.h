@@ -275,7 +275,15 @@ constexpr uint32_t kGridMapCellsCap = 1u << 18;
 inline bool grid_small(size_t stride, uint32_t reg_flags) { return stride <= kGridSmallCap && !(reg_flags & kRegFlagNoPackedGrid); }
 void launch_grid_build_targets(const RegBatch& B, const RegConfig& C, hipStream_t s);
 void launch_grid_build_sources(const RegBatch& B, const RegConfig& C, hipStream_t s);
-void launch_grid_build_target(const RegBatch& B, const RegConfig& C, int kind, hipStream_t s);  // one feature kind
+// What the launcher chose for a target build, reported where it chooses the kernel (loamx_target_index_census hands it on: a
+// read-out, never a second copy of grid_small / grid_big). form: LOAMX_INDEX_BUILD_* of loamx.h.
+constexpr uint32_t kGridBuildNone = 0u, kGridBuildPacked = 1u, kGridBuildSingle = 2u, kGridBuildBig = 3u;
+struct GridBuildForm {
+  uint32_t form;
+  uint32_t unit_cells;        // cells per LDS pass of the single-workgroup kernels / table entries per scan tile of the gridbig_* kernels
+  uint32_t table_min_points;  // the kernel writes the cell table of a set of at least this many points (0: of every set)
+};
+GridBuildForm launch_grid_build_target(const RegBatch& B, const RegConfig& C, int kind, hipStream_t s);  // one feature kind
 void launch_grid_build_source(const RegBatch& B, const RegConfig& C, int kind, hipStream_t s);
 void launch_state_init(const RegBatch& B, const RegConfig& C, hipStream_t s);
 // aux == nullptr: everything on s; aux2 == nullptr: the plane queue chain follows the edge chain on aux

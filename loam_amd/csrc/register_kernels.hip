@@ -2468,7 +2468,7 @@ static void debug_ptr(const char* what, const void* p, size_t need) {
 // box_min / box_max: the sets' bounding boxes as the extraction left them (keys; entry [pair * in_pitch][axis] of the arrays
 // passed here, i.e. already offset to the scan role and feature kind), valid while *box_bad == 0; nullptr: none
 template <bool ORDERED>
-static void launch_grid_build(size_t n_pairs, const double* pts, const uint32_t* n_pts, size_t stride, uint32_t in_pitch,
+static GridBuildForm launch_grid_build(size_t n_pairs, const double* pts, const uint32_t* n_pts, size_t stride, uint32_t in_pitch,
                               double max_dist, const GridSet& gs, GridPoint* scratch, uint32_t flags, hipStream_t s, unsigned long long* bytes,
                               const unsigned long long* box_min = nullptr, const unsigned long long* box_max = nullptr, const uint32_t* box_bad = nullptr,
                               const uint32_t* small_if = nullptr) {
@@ -2484,28 +2484,32 @@ static void launch_grid_build(size_t n_pairs, const double* pts, const uint32_t*
   }
   if (!ORDERED && grid_big(stride, scratch, flags)) {
     launch_grid_build_big(n_pairs, pts, n_pts, stride, in_pitch, max_dist, gs, scratch, s);
-    return;
+    return GridBuildForm{kGridBuildBig, kScanTile, 0u};  // (every entry of the table is written, whatever the set's size)
   }
-  if (grid_small(stride, flags))
+  // (the single-workgroup kernels leave the table of an unordered set of at most kBruteMax points unwritten)
+  if (grid_small(stride, flags)) {
     launch_kernel((grid_build_kernel<ORDERED, true>), dim3((unsigned)n_pairs), dim3(kBuildThreads), 0, s, pts, n_pts, stride,
                        in_pitch, max_dist, gs, scratch, bytes, box_min, box_max, box_bad, small_if);
-  else
-    launch_kernel((grid_build_kernel<ORDERED, false>), dim3((unsigned)n_pairs), dim3(kBuildThreads), 0, s, pts, n_pts, stride,
-                       in_pitch, max_dist, gs, scratch, bytes, box_min, box_max, box_bad, small_if);
+    return GridBuildForm{kGridBuildPacked, kGridLdsCells, ORDERED ? 0u : kBruteMax + 1u};
+  }
+  launch_kernel((grid_build_kernel<ORDERED, false>), dim3((unsigned)n_pairs), dim3(kBuildThreads), 0, s, pts, n_pts, stride,
+                     in_pitch, max_dist, gs, scratch, bytes, box_min, box_max, box_bad, small_if);
+  return GridBuildForm{kGridBuildSingle, kGridLdsCells, ORDERED ? 0u : kBruteMax + 1u};
 }
 
-void launch_grid_build_target(const RegBatch& B, const RegConfig& C, int kind, hipStream_t s) {
-  if (B.n_pairs == 0) return;
+GridBuildForm launch_grid_build_target(const RegBatch& B, const RegConfig& C, int kind, hipStream_t s) {
+  if (B.n_pairs == 0) return GridBuildForm{kGridBuildNone, 0u, 0u};
   const RegKind& K = B.kind[kind];
   // (boxes: [scan][kind][axis]; the target scan of pair p is scan p * in_pitch of the arrays in B)
   const unsigned long long* bmin = B.box_min ? B.box_min + 3 * kind : nullptr;
   const unsigned long long* bmax = B.box_max ? B.box_max + 3 * kind : nullptr;
   const bool small_edges = kind == kEdge && B.small_edge_sets == 1u;
-  launch_grid_build<false>(B.n_pairs, K.tgt, K.n_tgt, K.stride, B.in_pitch, C.kind[kind].r, K.grid, B.sort_scratch, C.flags, s, B.grid_bytes, bmin, bmax, B.box_bad,
-                           small_edges ? K.n_tgt : nullptr);
+  const GridBuildForm form = launch_grid_build<false>(B.n_pairs, K.tgt, K.n_tgt, K.stride, B.in_pitch, C.kind[kind].r, K.grid, B.sort_scratch, C.flags, s,
+                                                      B.grid_bytes, bmin, bmax, B.box_bad, small_edges ? K.n_tgt : nullptr);
   if (small_edges)  // (both edge sets of the pairs whose target edge set is brute-force sized)
     launch_kernel(small_sets_build_kernel, dim3((unsigned)B.n_pairs), dim3(kSmallThreads), 0, s, K.tgt, K.n_tgt, K.src, K.n_src, K.stride,
                   B.in_pitch, C.kind[kind].r, K.grid, K.src_grid, B.grid_bytes, bmin, bmax, B.box_bad);
+  return form;
 }
 void launch_grid_build_targets(const RegBatch& B, const RegConfig& C, hipStream_t s) {
   for (int kind = 0; kind < 2; kind++) launch_grid_build_target(B, C, kind, s);

@@ -346,7 +346,7 @@ struct HostGrid {
   std::vector<float> rel;  // 3 planes of sp.size() floats: offsets from the grid origin (FP32 pre-selection)
 };
 
-static void build_grid(const double* pts, uint32_t n, double max_dist, HostGrid& G) {
+static void build_grid(const double* pts, uint32_t n, double max_dist, HostGrid& G, uint32_t cells_cap = kGridCellsCap) {
   Vec3 lo = v3(0, 0, 0), hi = v3(0, 0, 0);
   for (uint32_t i = 0; i < n; i++) {
     const Vec3 p = v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
@@ -354,7 +354,7 @@ static void build_grid(const double* pts, uint32_t n, double max_dist, HostGrid&
     lo = v3(std::min(lo.x, p.x), std::min(lo.y, p.y), std::min(lo.z, p.z));
     hi = v3(std::max(hi.x, p.x), std::max(hi.y, p.y), std::max(hi.z, p.z));
   }
-  grid_choose(G.g, lo, hi, n, max_dist, kGridCellsCap);
+  grid_choose(G.g, lo, hi, n, max_dist, cells_cap);
   const uint32_t ncell = (uint32_t)(G.g.nx * G.g.ny * G.g.nz);
   G.cell_start.assign(ncell + 1 + 4, 0);  // (+4 spare entries, as the device tables)
   std::vector<uint32_t> cell(n);
@@ -441,6 +441,40 @@ void hostcheck_grid_choose(const double* pts, uint64_t n, double max_dist, doubl
   HostGrid G;
   build_grid(pts, (uint32_t)n, max_dist, G);
   out[0] = G.g.h, out[1] = G.g.nx, out[2] = G.g.ny, out[3] = G.g.nz;
+}
+
+// ... with the cell cap as an argument (a map-sized persistent index owns a larger table): out = {h, nx, ny, nz} of
+// grid_choose over the exact bounding box of the set
+void hostcheck_grid_choose_cap(const double* pts, uint64_t n, double max_dist, uint32_t cells_cap, double out[4]) {
+  Vec3 lo = v3(0, 0, 0), hi = v3(0, 0, 0);
+  for (uint64_t i = 0; i < n; i++) {
+    const Vec3 p = v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+    if (i == 0) lo = hi = p;
+    lo = v3(std::min(lo.x, p.x), std::min(lo.y, p.y), std::min(lo.z, p.z));
+    hi = v3(std::max(hi.x, p.x), std::max(hi.y, p.y), std::max(hi.z, p.z));
+  }
+  GridDesc g;
+  grid_choose(g, lo, hi, (uint32_t)n, max_dist, cells_cap);
+  out[0] = g.h, out[1] = g.nx, out[2] = g.ny, out[3] = g.nz;
+}
+
+// The whole structure build_grid makes (what every hostcheck search runs on), for tests/index_common.py: desc = {ox, oy, oz, h,
+// inv_h}, dims = {nx, ny, nz}, cell_start[nx ny nz + 1], the cell-sorted points xyz[n][3] + orig[n], rel[3][n + kGridPad].
+// cell_start == nullptr: the descriptor alone (the caller sizes the table from it).
+void hostcheck_build_grid(const double* pts, uint64_t n, double max_dist, uint32_t cells_cap, double desc[5], int32_t dims[3],
+                          uint32_t* cell_start, double* xyz, uint32_t* orig, float* rel) {
+  HostGrid G;
+  build_grid(pts, (uint32_t)n, max_dist, G, cells_cap);
+  desc[0] = G.g.ox, desc[1] = G.g.oy, desc[2] = G.g.oz, desc[3] = G.g.h, desc[4] = G.g.inv_h;
+  dims[0] = G.g.nx, dims[1] = G.g.ny, dims[2] = G.g.nz;
+  if (!cell_start) return;
+  const size_t ncell = (size_t)G.g.nx * G.g.ny * G.g.nz;
+  std::copy(G.cell_start.begin(), G.cell_start.begin() + ncell + 1, cell_start);
+  for (uint64_t p = 0; p < n; p++) {
+    xyz[3 * p] = G.sp[p].x, xyz[3 * p + 1] = G.sp[p].y, xyz[3 * p + 2] = G.sp[p].z;
+    orig[p] = G.sp[p].orig;
+  }
+  std::copy(G.rel.begin(), G.rel.end(), rel);  // (three planes of n + kGridPad floats)
 }
 
 // per-query search statistics of the keyed path (analysis only): candidates and rows visited;

@@ -144,6 +144,31 @@ def grid_choose(pts, max_dist):
     return float(out[0]), (int(out[1]), int(out[2]), int(out[3]))
 
 
+def grid_choose_cap(pts, max_dist, cells_cap=65536):
+    """grid_choose over the exact bounding box of `pts` with the cell cap as an argument -> (h, (nx, ny, nz))"""
+    pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+    out = np.empty(4)
+    lib().hostcheck_grid_choose_cap(_dp(pts), C.c_uint64(len(pts)), C.c_double(max_dist), C.c_uint32(cells_cap), _dp(out))
+    return float(out[0]), (int(out[1]), int(out[2]), int(out[3]))
+
+
+def build_grid(pts, max_dist, cells_cap=65536):
+    """the hostcheck's own index of `pts` (what its searches run on) as a dict with the fields of capi.IndexCensus that
+    tests/index_common.check_index reads: origin, h, inv_h, dims, n, n_points, cell_start, xyz, orig, rel, table_valid"""
+    pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+    n = len(pts)
+    desc, dims = np.empty(5), np.zeros(3, dtype=np.int32)
+    i32p, u32p = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+    args = (_dp(pts), C.c_uint64(n), C.c_double(max_dist), C.c_uint32(cells_cap), _dp(desc), dims.ctypes.data_as(i32p))
+    lib().hostcheck_build_grid(*args, None, None, None, None)
+    ncell = int(dims[0]) * int(dims[1]) * int(dims[2])
+    cs, xyz, orig = np.zeros(ncell + 1, dtype=np.uint32), np.zeros((n, 3)), np.zeros(n, dtype=np.uint32)
+    rel = np.zeros((3, n + 4), dtype=np.float32)
+    lib().hostcheck_build_grid(*args, cs.ctypes.data_as(u32p), _dp(xyz), orig.ctypes.data_as(u32p), rel.ctypes.data_as(C.POINTER(C.c_float)))
+    return dict(n=n, n_points=n, origin=desc[:3].copy(), h=float(desc[3]), inv_h=float(desc[4]), dims=tuple(int(d) for d in dims),
+                cell_start=cs, xyz=xyz, orig=orig, rel=rel, table_valid=1)
+
+
 def fit_plane(pts):
     pts = np.ascontiguousarray(pts, dtype=np.float64)
     out = np.empty(4)
