@@ -201,7 +201,7 @@ int loamx_ctx_last_solve_census(loamx_ctx* ctx, size_t pair, loamx_solve_census*
  *   extraction:    FORCE_TIE_REPLAY, FORCE_SCAN_GIVEUP, CURV_V1, NO_FUSED_COMPACT, NO_MIS_SELECT, NO_ROW_SELECT, FUSED_EXTRACT,
  *                  FUSED_ROWS, NO_SPLIT_CURV, STAGE_ALWAYS
  *   registration:  NO_MOMENTS, NO_REF_MOMENTS, NO_PACKED_GRID, NO_BIG_GRID, NO_GRID_SIDE, NO_EXTRACT_BOXES, NO_SMALL_SETS, DEBUG_POISON,
- *                  QUEUE_TWO_STAGE, QUEUE_ONE_STAGE, NO_COOP_LEFT, NO_MIXED_ASSOC, FORCE_LATE_VERIFY, MAP_CELLS_LOG2 (a number: 0 = default)
+ *                  QUEUE_TWO_STAGE, QUEUE_ONE_STAGE, NO_COOP_LEFT, NO_MIXED_ASSOC, FORCE_LATE_VERIFY, NO_LIVE_DEAL, MAP_CELLS_LOG2 (a number: 0 = default)
  *   host streaming: STREAM_CHUNK_PAIRS (a number: pairs per uploaded chunk of loamx_register_scan_pairs / _scan_sequence; 0 = default, 128)
  *   multi-GPU:     FORCE_RCCL (a one-rank communicator really enqueues the RCCL collectives)
  *   input checks:  CHECK_FINITE (see "Non-finite input" below)

@@ -163,6 +163,11 @@ int reg_prepare(loamx_ctx* ctx, const RegInputs& in, RegConfig& C, const loamx_t
   SCRATCH(ctx->ws[WS_MOMENTS], np * (size_t)(kMomSize + 2) * sizeof(double), B.moments);
   SCRATCH(ctx->ws[WS_FLAGGED_LIST], np * (size_t)B.mom_blocks_per_pair * kSweepChunk * sizeof(uint32_t), B.flagged_list);
   SCRATCH(ctx->ws[WS_FLAGGED_COUNT], np * (size_t)B.mom_blocks_per_pair * 4 * sizeof(uint32_t), B.flagged_count);
+  // the live lists (xcd_map.h) only where the deal exists: at least 8 pairs (below, xcd_pair_map spreads chunks, not pairs)
+  if (np >= 8 && !(C.flags & kRegFlagNoLiveDeal)) {
+    SCRATCH(ctx->ws[WS_LIVE], sizeof(LiveLists) + 2 * np * sizeof(uint32_t), B.live);
+    B.live_pairs = reinterpret_cast<uint32_t*>(B.live + 1);
+  }
   if (opts.want_info_partials) {
     InfoPartial* info_partials = nullptr;  // (bound nowhere in B: the callers hand reg_info_partials(ctx) to reg_information)
     SCRATCH(ctx->ws[WS_INFO_PARTIALS], np * info_blocks_per_pair(es, ps) * sizeof(InfoPartial), info_partials);
@@ -236,7 +241,9 @@ int reg_dump(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, const loamx_
   if (B.n_pairs == 0) return LOAMX_OK;
   hipStream_t s = ctx->stream;
   if (B.n_pairs != 1) return fail(ctx, LOAMX_ERR_BAD_PARAM, "association dump: one pair at a time");
-  int rc_a = enqueue_association(ctx, B, C);
+  RegBatch Bd = B;
+  Bd.want_nn_counts = 1u;  // (assoc_dump_kernel reads the verified counts out of nn: only here does fit_one write them back)
+  int rc_a = enqueue_association(ctx, Bd, C);
   if (rc_a != LOAMX_OK) return rc_a;
   untimed(ctx);
   const size_t n[2] = {n_src[kEdge], n_src[kPlane]}, kq[2] = {(size_t)C.kind[kEdge].k, (size_t)C.kind[kPlane].k}, pw[2] = {6, 4};
@@ -310,7 +317,7 @@ int reg_solve(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, loamx_reg_r
       // all) they are written while the read-back travels, instead of ~26 us of idle GPU later; otherwise they are written
       // again at the end.
       untimed(ctx);
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, B.n_active, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, B.live_count(it), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       launch_write_results(B, d_results, s);
       CHECK_LAUNCH(ctx, "write_results_kernel");
       HIP_TRY(ctx, hipStreamSynchronize(s));

@@ -23,6 +23,7 @@ constexpr int kInfoChunk = kInfoThreads * kInfoItems;
 __global__ void info_activate_kernel(RegBatch B) {
   const size_t pair = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (pair >= B.n_pairs) return;
+  if (pair == 0 && B.live) B.live->stamp[0] = B.live->stamp[1] = 0u;  // every pair again: the solve's last list does not count
   B.state[pair].active = 1u;  // est, termination and iterations — what write_results_kernel reads — stay as they are
 }
 

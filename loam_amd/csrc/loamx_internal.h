@@ -8,6 +8,7 @@
 #include "../../include/loamx.h"
 #include "extract_math.h"
 #include "reg_math.h"
+#include "xcd_map.h"
 
 namespace loamx {
 
@@ -156,6 +157,7 @@ constexpr uint32_t kRegFlagNoSmallSets = 8192u;     // edge-sized sets through g
 constexpr uint32_t kRegFlagCheckFinite = 4096u;     // the "_dev" entry points look for non-finite input coordinates first (host side only)
 constexpr uint32_t kRegFlagNoExtractBoxes = 2048u;  // the index builds take their bounding boxes themselves even when the extraction left them
 constexpr uint32_t kRegFlagNoMixedAssoc = 128u;  // edge and plane first kernels as separate launches on two streams (launch_associate)
+constexpr uint32_t kRegFlagNoLiveDeal = 32768u;   // ICF iterations 3+: every pair keeps its place in the grids (xcd_pair_map), finished or not — no deal of the live pairs (xcd_live_map)
 constexpr uint32_t kRegFlagForceLate = 16384u;    // plane fit of the mixed launch: every selection it has to verify is refused (all of them take the late list: associate_fit_late_kernel)
 
 // One target feature set's spatial index (device pointers into the workspace)
@@ -195,6 +197,21 @@ struct RegKind {
   uint32_t* rest;     // [n_pairs * stride] queue of the queries round 1 of the k-NN did not finish
   uint32_t* exact;    // queue of the queries the keyed collector could not decide (exact collector re-runs them)
 };
+
+// The pairs that go on, listed on the device at the end of an ICF iteration for the kernels of the next one (xcd_map.h:
+// xcd_live_map). Two lists, used alternately: the kernels of iteration i read list i % 2 while its solve fills list (i + 1) % 2.
+// A list counts only while its stamp is the iteration that reads it; everything else — the first two iterations, an association
+// pass outside a solve, the next call — finds no stamp of its own and places by xcd_pair_map.
+// Where the lists exist, a list's entry count IS the count of the pairs that go on (RegBatch::n_active without them): one atomic
+// per pair gives the pair its place in the list, and the host reads n[(it + 1) % 2] behind iteration it (RegBatch::live_count).
+struct LiveLists {
+  uint32_t iter;      // ICF iterations begun in this call: state_init_kernel 0, lm_begin_kernel + 1 (behind the association kernels)
+  uint32_t n[2];      // entries of list 0 / 1 (outer_update_pair)
+  uint32_t stamp[2];  // the iteration list 0 / 1 is for; 0: none (lists are for iterations >= kLiveFirstIter)
+  uint32_t pad[3];
+  // uint32_t pairs[2][n_pairs] behind it (RegBatch::live_pairs)
+};
+constexpr uint32_t kLiveFirstIter = 2u;  // (until then next to every pair goes on: the deal would only shuffle them)
 
 struct PairState {
   double est[7];
@@ -239,7 +256,7 @@ struct RegBatch {
   uint32_t* flagged_list;   // [n_pairs][mom_blocks_per_pair][4 wavefronts][kSweepChunk / 4] plane slots the moments leave out, in slot order
   uint32_t* flagged_count;  // [n_pairs][mom_blocks_per_pair][4]
   uint32_t blocks_per_pair;
-  uint32_t* n_active;    // device counter read back by the host after every outer iteration
+  uint32_t* n_active;    // device counter read back by the host after every outer iteration (with live lists: live_count)
   unsigned long long* sweep_slots;  // [0,1] edge / plane association slots streamed by sweep_kernel (roofline bytes);
                                     // [2,3] assoc_slots; [4] plane slots streamed by the moment pass
   unsigned long long* assoc_slots;  // [2] edge / plane source features processed by associate_kernel
@@ -257,6 +274,11 @@ struct RegBatch {
   const uint32_t* box_bad;
   uint32_t src_box_offset;  // scans from a pair's target box to its source box (1: the source scan lies one scan behind the target
                             // scan, in interleaved pairs and in a sequence alike); 0: the source sets have no boxes
+  LiveLists* live;       // null: no deal of the live pairs (fewer than 8 pairs, NO_LIVE_DEAL)
+  // the device counter of the pairs that go on after ICF iteration `it` of the call, for the host's read-back
+  const uint32_t* live_count(uint32_t it) const { return (live && it + 1u >= kLiveFirstIter) ? &live->n[(it + 1u) & 1u] : n_active; }
+  uint32_t* live_pairs;  // [2][n_pairs]
+  uint32_t want_nn_counts;  // 1: an association dump will read the verified neighbour counts fit_one leaves in RegKind::nn (reg_dump)
   uint32_t small_edge_sets;  // 1: pairs whose TARGET edge set holds at most kBruteMax points get both edge sets from small_sets_build_kernel;
                              // 2: the target is a persistent index whose edge set is that small: every source edge set in its given order
 };

@@ -705,6 +705,7 @@ __global__ __launch_bounds__(kRankThreads) void grid_rank_kernel(const uint32_t*
 __global__ void state_init_kernel(RegBatch B, RegConfig C) {
   const size_t pair = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (pair >= B.n_pairs) return;
+  if (pair == 0 && B.live) *B.live = LiveLists{};  // (no list of an earlier call counts in this one)
   PairState& S = B.state[pair];
   for (int i = 0; i < 7; i++) S.est[i] = B.init ? B.init[pair * 7 + i] : (i == 3 ? 1.0 : 0.0);
   S.active = C.max_iterations > 0 ? 1u : 0u;
@@ -749,22 +750,29 @@ static_assert(!(LOAMX_HANDOFF & 2) || (LOAMX_HANDOFF & 1), "verification in the 
 #define LOAMX_ASSOC_WAVES5 (LOAMX_KNN_REQUERY ? 6 : 4)  // the round-1 kernels of k <= 5 (knn_round1_body: 80 registers with the requery)
 #endif
 
-// Workgroup -> (pair, chunk) mapping: workgroups are dealt round-robin over the 8 XCDs, so all
-// chunks of one pair are given ids with the same id % 8 and share one XCD's L2 (the pair's target
-// index + points are ~0.5 MB). With fewer than 8 pairs (single registrations, scan-to-map) that would
-// leave XCDs idle, so the chunks are spread over all of them instead. Placement only affects speed,
-// never results. (Grids are sized ceil(n_pairs / 8) * 8 * blocks_per_pair for both mappings.)
-__device__ __forceinline__ bool xcd_pair_map(uint32_t block, uint32_t blocks_per_pair, size_t n_pairs, size_t& pair,
-                                             uint32_t& chunk) {
-  if (n_pairs < 8) {
-    pair = block / blocks_per_pair;
-    chunk = block % blocks_per_pair;
-  } else {
-    const uint32_t xcd = block & 7u, slot = block >> 3;
-    pair = (size_t)xcd + 8u * (size_t)(slot / blocks_per_pair);
-    chunk = slot % blocks_per_pair;
-  }
-  return pair < n_pairs;
+// (xcd_map.h: xcd_pair_map, the placement of every pair's workgroups, and xcd_live_map, the same deal over a list of pairs)
+// From the third ICF iteration on a good part of the batch has finished, unevenly over the 8 XCD lanes xcd_pair_map deals the
+// pairs to: the fullest lane decides when a kernel ends. The pairs that go on are therefore listed at the end of an iteration
+// (outer_update_pair) and the kernels of the next one deal the list's entries over the lanes. Which list, if any, the kernels of
+// the running iteration place by — behind_begin: 0 in the association kernels, 1 behind lm_begin_kernel, which has counted
+// the iteration. Null: by xcd_pair_map (LiveLists in loamx_internal.h says when). Placement only affects speed, never results.
+__device__ __forceinline__ const uint32_t* live_list(const RegBatch& B, uint32_t behind_begin, uint32_t& n_live) {
+  n_live = 0u;
+  if (!B.live) return nullptr;
+  const LiveLists* __restrict__ L = B.live;  // (uniform: scalar loads; selects, no indexed copy — that would live in scratch or LDS)
+  const uint32_t iter = L->iter, n0 = L->n[0], n1 = L->n[1], stamp0 = L->stamp[0], stamp1 = L->stamp[1];
+  const uint32_t it = iter - behind_begin;
+  const bool odd = (it & 1u) != 0u;
+  if (it < kLiveFirstIter || (odd ? stamp1 : stamp0) != it) return nullptr;
+  n_live = odd ? n1 : n0;
+  return B.live_pairs + (odd ? B.n_pairs : (size_t)0);
+}
+// the association kernels' workgroup -> (pair, chunk)
+__device__ __forceinline__ bool assoc_map(const RegBatch& B, uint32_t block, uint32_t blocks_per_pair, size_t& pair, uint32_t& chunk) {
+  uint32_t n_live;
+  const uint32_t* live = live_list(B, 0u, n_live);
+  if (live) return xcd_live_map(block, blocks_per_pair, B.n_pairs, n_live, live, pair, chunk);
+  return xcd_pair_map(block, blocks_per_pair, B.n_pairs, pair, chunk);
 }
 
 // Small target sets (a few hundred edge features per scan) are searched exhaustively: the whole set
@@ -798,7 +806,7 @@ __device__ __forceinline__ void knn_brute_body(const RegBatch& B, const RegConfi
                                                GridPoint* s_tile) {
   size_t pair;
   uint32_t chunk;
-  if (!xcd_pair_map(block, blocks_per_pair, B.n_pairs, pair, chunk)) return;
+  if (!assoc_map(B, block, blocks_per_pair, pair, chunk)) return;
   const PairState& S = B.state[pair];
   if (!S.active) return;  // uniform per workgroup
   const RegKind& K = B.kind[PLANE];
@@ -949,7 +957,7 @@ __device__ __forceinline__ void knn_round1_body(const RegBatch& B, const RegConf
                                                 uint32_t* s_rows) {
   size_t pair;
   uint32_t chunk;
-  if (!xcd_pair_map(block, blocks_per_pair, B.n_pairs, pair, chunk)) return;
+  if (!assoc_map(B, block, blocks_per_pair, pair, chunk)) return;
   const uint32_t i = chunk * kAssocThreads + threadIdx.x;
   const PairState& S = B.state[pair];
   if (!S.active) return;  // uniform per workgroup
@@ -1059,7 +1067,7 @@ __global__ __launch_bounds__(kRestThreads, LOAMX_REST_WAVES(KM)) void associate_
   constexpr bool one_stage = ONE_STAGE;  // (two instantiations: each at its own register budget)
   size_t pair;
   uint32_t chunk0;
-  if (!xcd_pair_map(blockIdx.x, blocks_per_pair, B.n_pairs, pair, chunk0)) return;
+  if (!assoc_map(B, blockIdx.x, blocks_per_pair, pair, chunk0)) return;
   const PairState& S = B.state[pair];
   if (!S.active) return;                                              // uniform per workgroup
   const uint32_t queued = B.n_assoc[8 * pair + (PLANE ? 3 : 2)];
@@ -1121,7 +1129,7 @@ __global__ __launch_bounds__(kRestThreads, kLeftWaves) void associate_knn_left_k
                                                                                               uint32_t blocks_per_pair) {
   size_t pair;
   uint32_t chunk0;
-  if (!xcd_pair_map(blockIdx.x, blocks_per_pair, B.n_pairs, pair, chunk0)) return;
+  if (!assoc_map(B, blockIdx.x, blocks_per_pair, pair, chunk0)) return;
   const PairState& S = B.state[pair];
   if (!S.active) return;                                              // uniform per workgroup
   const uint32_t listed = B.n_assoc[8 * pair + (PLANE ? 5 : 4)];
@@ -1362,7 +1370,7 @@ template <bool PLANE, int KM>
 __global__ __launch_bounds__(kRestThreads, LOAMX_COOP_WAVES) void associate_knn_coop_kernel(RegBatch B, RegConfig C, uint32_t blocks_per_pair) {
   size_t pair;
   uint32_t chunk0;
-  if (!xcd_pair_map(blockIdx.x, blocks_per_pair, B.n_pairs, pair, chunk0)) return;
+  if (!assoc_map(B, blockIdx.x, blocks_per_pair, pair, chunk0)) return;
   const PairState& S = B.state[pair];
   if (!S.active) return;                                              // uniform per workgroup
   const uint32_t listed = B.n_assoc[8 * pair + (PLANE ? 5 : 4)];
@@ -1434,7 +1442,7 @@ __device__ __forceinline__ void knn_exact_one(const RegBatch& B, const RegConfig
 // fitLine / fitPlane on the neighbours of query i of `pair` and its association record; the neighbour
 // count and positions are read at index nidx of the (1 + KM)-field array nnsrc. Returns "valid".
 // HANDOFF (the round-1 kernel's, see LOAMX_HANDOFF): bit 1 = a count word may be an unverified selection: verified here on
-// the gathered points (knn_handoff_verify), the verified count written back over it; a query that fails is appended to the
+// the gathered points (knn_handoff_verify), the verified count written back over it for an association dump; a query that fails is appended to the
 // pair's late list (the tail of K.exact, filled from its end; counted in n_assoc[8 * pair + 6 + PLANE]) and left to
 // associate_fit_late_kernel.
 template <bool PLANE, int KM, bool QUEUED = false, int HANDOFF = 0>
@@ -1471,7 +1479,7 @@ __device__ __forceinline__ bool fit_one(const RegBatch& B, const RegConfig& C, c
       K.exact[pair * stride + (stride - 1 - at)] = i;
       return false;
     }
-    K.nn[nidx] = (uint32_t)kept;
+    if (B.want_nn_counts) K.nn[nidx] = (uint32_t)kept;  // (uniform; only assoc_dump_kernel reads the count again)
   }
   if (kept >= CK.min_pts) {  // registration.cpp:39 / :80
     Vec3 nb[KM];
@@ -1510,14 +1518,14 @@ template <bool PLANE, int KM, int HANDOFF = 0>
 __device__ __forceinline__ void fit_body(const RegBatch& B, const RegConfig& C, uint32_t blocks_per_pair, uint32_t block) {
   size_t pair;
   uint32_t chunk;
-  if (!xcd_pair_map(block, blocks_per_pair, B.n_pairs, pair, chunk)) return;
+  if (!assoc_map(B, block, blocks_per_pair, pair, chunk)) return;
   const uint32_t i = chunk * kAssocThreads + threadIdx.x;
   const PairState& S = B.state[pair];
   if (!S.active) return;  // uniform per workgroup
   const RegKind& K = B.kind[PLANE];
   const size_t stride = K.stride;
   const uint32_t n_src = K.n_src[pair * B.in_pitch];
-  const uint32_t* nn = K.nn;  // (HANDOFF: fit_one writes the verified count back)
+  const uint32_t* nn = K.nn;  // (HANDOFF: fit_one writes the verified count back for an association dump)
   bool valid = false;
   if (i < n_src && i < stride) valid = fit_one<PLANE, KM, false, HANDOFF>(B, C, S, pair, i, nn, pair * stride + i);  // (queued queries: skipped inside)
   // (one atomic per wavefront, no barrier: a wavefront that is done leaves)
@@ -1542,7 +1550,7 @@ template <bool PLANE, int KM>
 __global__ __launch_bounds__(kRestThreads, 3) void associate_fit_queued_kernel(RegBatch B, RegConfig C, uint32_t blocks_per_pair) {  // (3: <= 168 registers — unbounded it took 230 and waited for two fit wavefronts to leave a SIMD at once; at 128 it spills 376 bytes)
   size_t pair;
   uint32_t chunk0;
-  if (!xcd_pair_map(blockIdx.x, blocks_per_pair, B.n_pairs, pair, chunk0)) return;
+  if (!assoc_map(B, blockIdx.x, blocks_per_pair, pair, chunk0)) return;
   const PairState& S = B.state[pair];
   if (!S.active) return;                                              // uniform per workgroup
   const uint32_t queued = B.n_assoc[8 * pair + (PLANE ? 3 : 2)];
@@ -1571,7 +1579,7 @@ template <bool PLANE, int KM>
 __global__ __launch_bounds__(kRestThreads, 3) void associate_fit_late_kernel(RegBatch B, RegConfig C, uint32_t blocks_per_pair) {  // (3: as associate_fit_queued_kernel)
   size_t pair;
   uint32_t chunk0;
-  if (!xcd_pair_map(blockIdx.x, blocks_per_pair, B.n_pairs, pair, chunk0)) return;
+  if (!assoc_map(B, blockIdx.x, blocks_per_pair, pair, chunk0)) return;
   const uint32_t late = B.n_assoc[8 * pair + 6 + (PLANE ? 1 : 0)];
   if (late == 0u) return;                                             // uniform per workgroup
   const PairState& S = B.state[pair];
@@ -1598,6 +1606,12 @@ __global__ __launch_bounds__(64) void lm_begin_kernel(RegBatch B, RegConfig C) {
   const size_t pair = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (pair >= B.n_pairs) return;
   if (pair == 0) *B.n_active = 0u;  // outer_update_pair counts the pairs that go on (read back by the host after the iteration)
+  if (pair == 0 && B.live) {        // ... in the list of the next iteration's kernels where there are lists: empty, with that iteration's stamp
+    const uint32_t next = B.live->iter + 1u, slot = next & 1u;
+    B.live->n[slot] = 0u;
+    B.live->stamp[slot] = next >= kLiveFirstIter ? next : 0u;
+    B.live->iter = next;
+  }
   PairState& S = B.state[pair];
   if (!S.active) return;
   const uint32_t iteration = S.iterations;
@@ -1959,6 +1973,14 @@ __device__ __forceinline__ void outer_update_pair(const RegBatch& B, const RegCo
     S.active = 0;
   } else if (iteration + 1 >= C.max_iterations) {
     S.active = 0;  // termination stays MAX_ITER
+  } else if (B.live && B.live->iter >= kLiveFirstIter) {
+    // counted where the pair is listed (RegBatch::live_count): ONE atomic, which hands the pair its place. The pairs take their
+    // turns at the one address, 15 - 18 ns each where the value has to come back: measured + 10 us on the pair loop that ends the
+    // second iteration (~640 entries), + 19 us behind the first — whose list nobody would read: the plain count below there.
+    // (behind lm_begin_kernel: iter is the next iteration, the list its kernels will read; order inside the list is free)
+    const uint32_t slot = B.live->iter & 1u;
+    const uint32_t at = atomicAdd(&B.live->n[slot], 1u);
+    if (at < B.n_pairs) B.live_pairs[slot * B.n_pairs + at] = (uint32_t)pair;
   } else {
     atomicAdd(B.n_active, 1u);
   }
@@ -2134,8 +2156,17 @@ __global__ __launch_bounds__(64) void moment_kernel(RegBatch B) {  // one wavefr
   __shared__ double s_c[kMomStride][kMomLdsRow];
   const int wave = (int)(blockIdx.x & 3u), lane = (int)threadIdx.x;  // the wavefront's place in its chunk of kSweepChunk slots
   const int tix = wave * 64 + lane;
-  const size_t pair = (blockIdx.x >> 2) / B.mom_blocks_per_pair;
+  size_t pair = (blockIdx.x >> 2) / B.mom_blocks_per_pair;
   const uint32_t blk = (blockIdx.x >> 2) % B.mom_blocks_per_pair;
+  {  // the live pairs first (this kernel streams: its grid has no XCD lanes, the list only packs the work at its front)
+    uint32_t n_live;
+    const uint32_t* live = live_list(B, 1u, n_live);
+    if (live) {
+      if (pair >= n_live) return;  // uniform per workgroup
+      pair = live[pair];
+      if (pair >= B.n_pairs) return;
+    }
+  }
   const PairState& S = B.state[pair];
   if (!S.active || !S.lm.active || !S.use_moments) return;  // uniform per workgroup
   const uint32_t n_sp_raw = B.kind[kPlane].n_src[pair * B.in_pitch];
