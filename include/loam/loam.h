@@ -4,4 +4,5 @@
 #include "features.h"
 #include "geometry.h"
 #include "kdtree.h"
+#include "organize.h"
 #include "registration.h"

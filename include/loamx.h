@@ -586,6 +586,79 @@ int loamx_deskew_scans_dev_f32(loamx_ctx* ctx, const float* d_xyz, size_t n_scan
  * entry points refuse, LOAMX_ERR_BAD_PARAM for a null `out`. A test of "the remainder at shape X" asserts its shape from here. */
 int loamx_deskew_launch_geometry(size_t n_scans, uint64_t scan_lines, uint64_t points_per_line, uint32_t out[4]);
 
+/* ---- unordered clouds into scans (no reference counterpart: the reference demands an organised scan, common.h:104-113, and
+ * leaves the projection to its users). Every entry point above starts from scan_lines x points_per_line points, row-major
+ * [line][column]; sensor drivers and datasets deliver unordered x, y, z (with or without a ring number), with dropped returns
+ * missing and, for dual-return sensors, two points per beam. These entry points put such a cloud into the grid on the device,
+ * with a winner per cell that does not depend on how the threads are scheduled.
+ *
+ * A scan layout (H = scan_lines, W = points_per_line) holds two tables, computed once on the host in FP64 and kept on the device:
+ *   column boundaries  u_k = (cos phi_k, sin phi_k), phi_k = azimuth_zero + sgn 2 pi (k - 1/2) / W, k = 0 .. W - 1; sgn = +1
+ *                      counter-clockwise seen from +z, -1 when `clockwise` is set. With the defaults column c is centred on the
+ *                      azimuth 2 pi c / W (the convention of the synthetic generator).
+ *   line boundaries    t_0 .. t_H: the tangents of the elevations half way between neighbouring beams; the two outer ones lie
+ *                      half the adjacent spacing beyond the outer beams. Beam elevations: `elevations`[H] (radians, strictly
+ *                      ascending, line 0 the lowest beam) or, if NULL, linear from fov_bottom to fov_top. H == 1: {-inf, +inf}.
+ * Per point p = (x, y, z) (float input is widened first; every product and sum is rounded on its own, no fused multiply-add):
+ *   1. rho2 = x x + y y, r2 = rho2 + z z. INVALID (dropped): a non-finite coordinate, a non-finite r2, or !(rho2 >= 1e-100) —
+ *      "no azimuth", which includes the all-zero point of a beam without a return.
+ *   2. column: s_k = (sgn (u_k.x y - u_k.y x) >= 0); the column is the c with s_c true and s_(c + 1) mod W false (W == 1: 0).
+ *   3. line, without rings: rho = sqrt(rho2), cnt = the number of l in 0 .. H with z >= t_l rho; cnt == 0 or H + 1: OUTSIDE the
+ *      fan (dropped), else line cnt - 1. With rings (one uint16 per point): the line is ring, or ring_map[ring] if a map was
+ *      given; a ring >= H, a ring beyond the map or a map entry 0xFFFF: OUTSIDE.
+ *   4. winner of a cell among the points of one cloud: KEEP_FIRST the lowest input index (the voxel filter's rule);
+ *      KEEP_NEAREST the smallest r2 (as doubles), on equal r2 the lowest index. The others are counted as collisions.
+ *   5. the winner's three coordinates are copied bit for bit in the input's type; a cell without a winner is (+0, +0, +0) — for
+ *      the extraction a beam without a return. src_idx[cell]: the winner's index within its cloud or 0xFFFFFFFF. stats per
+ *      cloud: {filled, invalid, outside, collisions}; they add up to the cloud's point count.
+ * The same bytes on every run, and for a cloud alone or inside any batch. */
+enum { LOAMX_ORGANIZE_KEEP_FIRST = 0, LOAMX_ORGANIZE_KEEP_NEAREST = 1 };
+typedef struct {
+  double azimuth_zero;       /* 0.0: azimuth of the centre of column 0 (radians) */
+  uint32_t clockwise;        /* 0 */
+  uint32_t keep;             /* LOAMX_ORGANIZE_KEEP_FIRST */
+  const double* elevations;  /* NULL: linear from fov_bottom to fov_top */
+  double fov_bottom;         /* -15 degrees, in radians */
+  double fov_top;            /* +15 degrees */
+  const uint16_t* ring_map;  /* NULL: the ring number is the line. Entries: a line < scan_lines, or 0xFFFF (drop that ring) */
+  size_t n_ring_map;
+} loamx_organize_params;
+void loamx_default_organize_params(loamx_organize_params* p);
+typedef struct loamx_scan_layout loamx_scan_layout;
+/* Copies everything it needs from *params (the arrays included). LOAMX_ERR_BAD_PARAM: a null argument, scan_lines or
+ * points_per_line 0, an unknown `keep`, a non-finite value, elevations that do not ascend, fov_top <= fov_bottom with
+ * scan_lines > 1, a boundary elevation outside (-pi/2, pi/2), a ring_map entry >= scan_lines other than 0xFFFF.
+ * LOAMX_ERR_UNSUPPORTED: a shape the extraction refuses (points_per_line > 4096, more than 2^30 - 1 points). */
+int loamx_scan_layout_create(loamx_ctx* ctx, const loamx_lidar_params* lidar, const loamx_organize_params* params,
+                             loamx_scan_layout** out);
+void loamx_scan_layout_destroy(loamx_ctx* ctx, loamx_scan_layout* layout);
+/* The two tables exactly as the kernels use them (host copies of the uploaded bytes): col_dirs[W][2] = u_k, line_tans[H + 1].
+ * Either may be NULL. A model of the rule above that reads them depends on nobody's cos or tan. */
+int loamx_scan_layout_tables(const loamx_scan_layout* layout, double* col_dirs, double* line_tans);
+/* n_clouds clouds stored back to back -> n_clouds scans.
+ *   d_points       the points, point_stride scalars each (>= 3: x, y, z first; 4 is the x y z intensity of a KITTI file)
+ *   d_rings        one uint16 per point, or NULL (lines by elevation)
+ *   cloud_offsets  HOST array of n_clouds + 1 ascending point offsets (read before the call returns); a cloud may be empty,
+ *                  its scan is then all zero
+ *   d_scans        n_clouds x H W x 3 scalars of the input's type: what loamx_extract_features_batch_dev[_f32],
+ *                  loamx_register_scan_sequence_dev[_f32] and loamx_deskew_scans_dev[_f32] take
+ *   d_src_idx      n_clouds x H W uint32, or NULL;  d_stats: n_clouds x 4 uint32, or NULL
+ * Every entry of the three outputs is written. Asynchronous on the context's stream, no synchronisation (the claim table
+ * lives in the context's workspace and is reset by the call). LOAMX_ERR_BAD_PARAM: a null layout, d_points, cloud_offsets
+ * or d_scans (n_clouds > 0), point_stride < 3, descending offsets; LOAMX_ERR_UNSUPPORTED: a cloud of more than 2^32 - 2
+ * points. A refused call writes nothing. n_clouds == 0: LOAMX_OK. */
+int loamx_organize_clouds_dev(loamx_ctx* ctx, const loamx_scan_layout* layout, const double* d_points, size_t point_stride,
+                              const uint16_t* d_rings, const size_t* cloud_offsets, size_t n_clouds, double* d_scans,
+                              uint32_t* d_src_idx, uint32_t* d_stats);
+int loamx_organize_clouds_dev_f32(loamx_ctx* ctx, const loamx_scan_layout* layout, const float* d_points, size_t point_stride,
+                                  const uint16_t* d_rings, const size_t* cloud_offsets, size_t n_clouds, float* d_scans,
+                                  uint32_t* d_src_idx, uint32_t* d_stats);
+/* One cloud of n_points points, host memory in, host memory out, synchronous; src_idx and stats may be NULL. */
+int loamx_organize_cloud(loamx_ctx* ctx, const loamx_scan_layout* layout, const double* points, size_t point_stride,
+                         const uint16_t* rings, size_t n_points, double* scan, uint32_t* src_idx, uint32_t* stats);
+int loamx_organize_cloud_f32(loamx_ctx* ctx, const loamx_scan_layout* layout, const float* points, size_t point_stride,
+                             const uint16_t* rings, size_t n_points, float* scan, uint32_t* src_idx, uint32_t* stats);
+
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are
  * independent units). One process per GPU owns a contiguous block of pair ids and runs the single-GPU entry points

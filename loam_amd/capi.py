@@ -138,6 +138,44 @@ class AssocDump(C.Structure):
                                           "plane_nn_count", "plane_nn_idx", "plane_valid", "plane_moved", "plane_planes", "queue_lengths")]
 
 
+ORGANIZE_KEEP_FIRST, ORGANIZE_KEEP_NEAREST = 0, 1
+NO_POINT = 0xFFFFFFFF  # src_idx of a cell without a winner
+
+
+class OrganizeParamsStruct(C.Structure):
+    """loamx_organize_params (include/loamx.h)"""
+    _fields_ = [("azimuth_zero", C.c_double), ("clockwise", C.c_uint32), ("keep", C.c_uint32), ("elevations", C.POINTER(C.c_double)),
+                ("fov_bottom", C.c_double), ("fov_top", C.c_double), ("ring_map", C.POINTER(C.c_uint16)), ("n_ring_map", C.c_size_t)]
+
+
+class OrganizeParams:
+    """How an unordered cloud maps onto the scan grid (loamx_organize_params): azimuth of column 0 and sense of rotation, the
+    beams' elevations (an array of scan_lines ascending angles in radians, or None: linear from fov_bottom to fov_top), an
+    optional ring_map (ring number -> line, 0xFFFF drops the ring) and the winner of a cell (ORGANIZE_KEEP_FIRST / _NEAREST)."""
+
+    def __init__(self, azimuth_zero=0.0, clockwise=False, keep=ORGANIZE_KEEP_FIRST, elevations=None, fov_bottom=None, fov_top=None,
+                 ring_map=None):
+        d = OrganizeParamsStruct()
+        load().loamx_default_organize_params(C.byref(d))
+        self.azimuth_zero, self.clockwise, self.keep = float(azimuth_zero), bool(clockwise), int(keep)
+        self.elevations = None if elevations is None else np.ascontiguousarray(elevations, dtype=np.float64).reshape(-1)
+        self.fov_bottom = d.fov_bottom if fov_bottom is None else float(fov_bottom)
+        self.fov_top = d.fov_top if fov_top is None else float(fov_top)
+        self.ring_map = None if ring_map is None else np.ascontiguousarray(ring_map, dtype=np.uint16).reshape(-1)
+
+    def struct(self, scan_lines):
+        """the C struct (it points into this object's arrays: keep the object alive while the struct is in use)"""
+        if self.elevations is not None and self.elevations.size != scan_lines:
+            raise ValueError(f"OrganizeParams: {self.elevations.size} elevations for {scan_lines} scan lines")
+        if self.keep < 0 or self.keep > 0xFFFFFFFF:
+            raise ValueError("OrganizeParams: keep is one of ORGANIZE_KEEP_FIRST, ORGANIZE_KEEP_NEAREST")
+        return OrganizeParamsStruct(self.azimuth_zero, 1 if self.clockwise else 0, self.keep,
+                                    self.elevations.ctypes.data_as(C.POINTER(C.c_double)) if self.elevations is not None else None,
+                                    self.fov_bottom, self.fov_top,
+                                    self.ring_map.ctypes.data_as(C.POINTER(C.c_uint16)) if self.ring_map is not None and self.ring_map.size else None,
+                                    0 if self.ring_map is None else self.ring_map.size)
+
+
 EXPORTS = [
     "loamx_default_fe_params", "loamx_default_reg_params", "loamx_status_string", "loamx_last_error",
     "loamx_ctx_create", "loamx_ctx_destroy", "loamx_ctx_set_stream", "loamx_ctx_synchronize",
@@ -163,6 +201,8 @@ EXPORTS = [
     "loamx_registration_information", "loamx_registration_information_indexed", "loamx_registration_information_batch_dev",
     "loamx_register_scan_pairs_info_dev", "loamx_register_scan_pairs_info_dev_f32", "loamx_register_scan_sequence_info_dev",
     "loamx_register_scan_sequence_info_dev_f32",
+    "loamx_default_organize_params", "loamx_scan_layout_create", "loamx_scan_layout_destroy", "loamx_scan_layout_tables",
+    "loamx_organize_clouds_dev", "loamx_organize_clouds_dev_f32", "loamx_organize_cloud", "loamx_organize_cloud_f32",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -352,6 +392,16 @@ def load(build_if_missing=True):
     lib.loamx_register_scan_pairs_info_dev_f32.argtypes = lib.loamx_register_scan_pairs_info_dev.argtypes
     lib.loamx_register_scan_sequence_info_dev.argtypes = lib.loamx_register_scan_sequence_dev.argtypes + [vp]
     lib.loamx_register_scan_sequence_info_dev_f32.argtypes = lib.loamx_register_scan_sequence_info_dev.argtypes
+    lib.loamx_default_organize_params.argtypes = [C.POINTER(OrganizeParamsStruct)]
+    lib.loamx_default_organize_params.restype = None
+    lib.loamx_scan_layout_create.argtypes = [vp, C.POINTER(LidarParams), C.POINTER(OrganizeParamsStruct), C.POINTER(vp)]
+    lib.loamx_scan_layout_destroy.argtypes = [vp, vp]
+    lib.loamx_scan_layout_destroy.restype = None
+    lib.loamx_scan_layout_tables.argtypes = [vp, dp, dp]
+    lib.loamx_organize_clouds_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, szp, C.c_size_t, vp, vp, vp]
+    lib.loamx_organize_clouds_dev_f32.argtypes = lib.loamx_organize_clouds_dev.argtypes
+    lib.loamx_organize_cloud.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
+    lib.loamx_organize_cloud_f32.argtypes = lib.loamx_organize_cloud.argtypes
     _lib = lib
     return lib
 
@@ -460,6 +510,46 @@ class Comm:
         if getattr(self, "h", None):
             self.ctx.lib.loamx_comm_destroy(self.h)
             self.h = None
+
+
+class ScanLayout:
+    """The grid an unordered cloud is put into (loamx_scan_layout): lidar.scan_lines x lidar.points_per_line cells, with the
+    tables of column and line boundaries on the context's device. close() frees it; the context must still be open."""
+
+    def __init__(self, ctx, lidar, params=None):
+        self.ctx, self.params = ctx, params or OrganizeParams()
+        self.scan_lines, self.points_per_line = int(lidar.scan_lines), int(lidar.points_per_line)
+        st = self.params.struct(self.scan_lines)
+        h = C.c_void_p()
+        ctx._check(ctx.lib.loamx_scan_layout_create(ctx.h, C.byref(lidar), C.byref(st), C.byref(h)))
+        self.h = h
+
+    @property
+    def cells(self):
+        return self.scan_lines * self.points_per_line
+
+    def tables(self):
+        """(col_dirs (W, 2), line_tans (H + 1,)): the bytes the kernels read (loamx_scan_layout_tables)"""
+        col, tan = np.empty((self.points_per_line, 2)), np.empty(self.scan_lines + 1)
+        self.ctx._check(self.ctx.lib.loamx_scan_layout_tables(self._handle(), _dp(col), _dp(tan)))
+        return col, tan
+
+    def _handle(self):
+        if not getattr(self, "h", None):
+            raise ValueError("the scan layout is closed")
+        return self.h
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.ctx.lib.loamx_scan_layout_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceBuffer:
@@ -968,6 +1058,51 @@ class Context:
             return d_xyz.download(a.dtype, a.size).reshape(a.shape)
         finally:
             d_xyz.free(), d_m.free()
+
+    # ---- unordered clouds into scans (include/loamx.h, "unordered clouds into scans") ----------------------
+    def scan_layout(self, lidar, params=None):
+        return ScanLayout(self, lidar, params)
+
+    def organize_clouds_dev(self, layout, d_points, point_stride, cloud_offsets, d_scans, d_rings=0, d_src_idx=0, d_stats=0, f32=False):
+        """len(cloud_offsets) - 1 device-resident clouds back to back -> as many scans (loamx_organize_clouds_dev[_f32]).
+        cloud_offsets: host integers, ascending point offsets; d_rings / d_src_idx / d_stats: device addresses or 0.
+        Asynchronous on the context's stream."""
+        off = np.ascontiguousarray(cloud_offsets)
+        if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu":
+            raise ValueError("organize_clouds_dev: cloud_offsets is a 1-d integer array of n_clouds + 1 offsets")
+        if off.dtype.kind == "i" and (off < 0).any():
+            raise ValueError("organize_clouds_dev: negative offset")
+        off = off.astype(np.uint64)
+        fn = self.lib.loamx_organize_clouds_dev_f32 if f32 else self.lib.loamx_organize_clouds_dev
+        self._check(fn(self.h, layout._handle(), d_points or None, int(point_stride), d_rings or None,
+                       off.ctypes.data_as(C.POINTER(C.c_size_t)), off.size - 1, d_scans or None, d_src_idx or None, d_stats or None))
+
+    def organize_cloud(self, points, layout, rings=None):
+        """One unordered cloud in host memory, (n, 3) or (n, 4) float64 / float32 -> (scan (H W, 3) in the cloud's dtype,
+        src_idx (H W,) uint32 with NO_POINT for an empty cell, stats = uint32 [filled, invalid, outside, collisions])."""
+        pts = np.asarray(points)
+        if pts.dtype != np.float32:
+            pts = np.asarray(pts, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] < 3:
+            raise ValueError(f"organize_cloud: points must be (n, 3) or (n, k >= 3), not {pts.shape}")
+        pts = np.ascontiguousarray(pts)
+        n, stride = pts.shape
+        r = None
+        if rings is not None:
+            r = np.asarray(rings)
+            if r.dtype != np.uint16:
+                if r.dtype.kind not in "iu" or (r.size and (r.min() < 0 or r.max() > 0xFFFF)):
+                    raise ValueError("organize_cloud: rings must be integers in 0 .. 65535")
+                r = r.astype(np.uint16)
+            r = np.ascontiguousarray(r).reshape(-1)
+            if r.size != n:
+                raise ValueError(f"organize_cloud: {r.size} ring numbers for {n} points")
+        scan = np.empty((layout.cells, 3), dtype=pts.dtype)
+        src, stats = np.empty(layout.cells, dtype=np.uint32), np.empty(4, dtype=np.uint32)
+        fn = self.lib.loamx_organize_cloud_f32 if pts.dtype == np.float32 else self.lib.loamx_organize_cloud
+        self._check(fn(self.h, layout._handle(), pts.ctypes.data, stride, r.ctypes.data if r is not None else None, n, scan.ctypes.data,
+                       src.ctypes.data, stats.ctypes.data))
+        return scan, src, stats
 
     def synth_scan_pairs_dev(self, seed, first_pair, n_pairs, scan_lines, points_per_line, sigma, d_xyz):
         self._check(self.lib.loamx_synth_scan_pairs_dev(self.h, seed, first_pair, n_pairs, scan_lines,

@@ -23,6 +23,7 @@ enum WsId {
   WS_LINE_TOT, WS_EXTRACT_EVENTS, WS_BOX, WS_FINITE_FLAG, WS_COUNTERS, WS_ITERINFO, WS_STREAM_IN0, WS_STREAM_IN1, WS_STREAM_RES,
   WS_FIT_IN, WS_FIT_OUT, WS_FCOUNTS, WS_RESULTS, WS_INIT, WS_STREAM_INIT,
   WS_VOX_TABLE, WS_MAP_WORDS, WS_INFO_PARTIALS, WS_INFO, WS_LIVE,
+  WS_ORG_WINNER, WS_ORG_RANGE, WS_ORG_CELL, WS_ORG_COUNTS, WS_ORG_IN, WS_ORG_RINGS, WS_ORG_OUT,
   WS_COUNT
 };
 // the buffers that exist once per feature kind: loamx_ctx::wsk[id][kEdge | kPlane]

@@ -8,6 +8,7 @@
 #include "../../include/loamx.h"
 #include "extract_math.h"
 #include "reg_math.h"
+#include "organize_math.h"
 #include "xcd_map.h"
 
 namespace loamx {
@@ -375,6 +376,21 @@ DeskewGeometry deskew_launch_geometry(size_t n_scans, uint32_t H, uint32_t W);
 void launch_deskew(const void* d_xyz, void* d_out, bool f32, size_t n_scans, uint32_t H, uint32_t W, const double* d_motion, double rho,
                    hipStream_t s);
 void launch_trajectory(const loamx_reg_result* d_results, size_t n_pairs, const double origin[7], double* d_world_T_scan, hipStream_t s);
+
+/* ---- unordered clouds into scans (organize_kernels.hip; the rule: organize_math.h and loamx.h) -------------------------- */
+constexpr uint32_t kOrgChunkClouds = 256;  // clouds per launch: their offsets travel as a kernel argument (no staging copy)
+// the clouds of one launch: cloud c holds the points off[c] .. off[c + 1] - 1 of the call's array
+struct OrgOffsets {
+  unsigned long long off[kOrgChunkClouds + 1];
+};
+// words of a cloud's counters in the workspace (filled is written by the gather, the finish kernel derives the collisions)
+enum { kOrgFilled = 0, kOrgInvalid = 1, kOrgOutside = 2, kOrgCounterWords = 4 };
+// One chunk of at most kOrgChunkClouds clouds, max_points = its largest cloud (> 0). winner: n_clouds x H W words, range (only
+// when `nearest`): as many 64-bit words, both set to 0xFF bytes by the caller; cell (only when `nearest`): one word per point of
+// the chunk; counters: n_clouds x kOrgCounterWords zeroed words. d_scans / d_src_idx / d_stats: the chunk's share of the outputs.
+void launch_organize(const void* d_points, bool f32, uint32_t stride, const uint16_t* d_rings, const OrgOffsets& offs, uint32_t n_clouds,
+                     unsigned long long max_points, const OrgTables& L, bool nearest, uint32_t* winner, unsigned long long* range,
+                     uint32_t* cell, uint32_t* counters, void* d_scans, uint32_t* d_src_idx, uint32_t* d_stats, hipStream_t s);
 
 /* ---- map upkeep (map_kernels.hip): voxel filter against an occupancy table, crop, the stable compaction they share --- */
 constexpr uint32_t kMapTile = 256;             // points per tile of the compaction (one workgroup)

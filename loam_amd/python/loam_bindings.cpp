@@ -4,7 +4,8 @@
 // RegistrationParams, RegistrationIterationInfo, RegistrationTerminationType, RegistrationDetail,
 // registerFeatures — with the same keyword arguments; plus extensions the reference does not have: registerScanSequence
 // and deskewScan (include/loamx.h: "scan sequences"), and the class TargetIndex with a registerFeatures overload that
-// takes it (scan-to-map: "persistent target index" and "map upkeep"). Point clouds are contiguous (N,3) float64
+// takes it (scan-to-map: "persistent target index" and "map upkeep"), and OrganizeParams / ScanLayout / organizeCloud, the way
+// in for clouds that are not organised scans yet ("unordered clouds into scans"). Point clouds are contiguous (N,3) float64
 // arrays handed to the C ABI without per-point objects (a list of 3-vectors is converted once).
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -81,6 +82,34 @@ inline int c_deskew(loamx_ctx* c, const double* in, const loamx_lidar_params* l,
 }
 inline int c_deskew(loamx_ctx* c, const float* in, const loamx_lidar_params* l, const double* motion, double rho, float* out) {
   return loamx_deskew_scans_dev_f32(c, in, 1, l, motion, rho, out);
+}
+
+
+// organizeCloud: (N, 3) or (N, k >= 3) points as they lie in the array (the stride is the row length), rings or None
+inline int c_organize(loamx_ctx* c, const loamx_scan_layout* l, const double* p, size_t stride, const uint16_t* r, size_t n, double* s, uint32_t* i,
+                      uint32_t* st) {
+  return loamx_organize_cloud(c, l, p, stride, r, n, s, i, st);
+}
+inline int c_organize(loamx_ctx* c, const loamx_scan_layout* l, const float* p, size_t stride, const uint16_t* r, size_t n, float* s, uint32_t* i,
+                      uint32_t* st) {
+  return loamx_organize_cloud_f32(c, l, p, stride, r, n, s, i, st);
+}
+using ArrRings = py::array_t<uint16_t, py::array::c_style | py::array::forcecast>;
+template <typename T>
+py::tuple organize_cloud(const py::array_t<T, py::array::c_style>& points, const loam::ScanLayout& layout, const std::optional<ArrRings>& rings) {
+  if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
+  const size_t n = (size_t)points.shape(0), stride = (size_t)points.shape(1);
+  if (rings && (rings->ndim() != 1 || (size_t)rings->shape(0) != n)) throw std::runtime_error("rings: expected one ring number per point");
+  py::array_t<T> scan(std::vector<py::ssize_t>{(py::ssize_t)layout.cells(), 3});
+  py::array_t<uint32_t> src((py::ssize_t)layout.cells());
+  uint32_t stats[4];
+  loamx_ctx* ctx = loam::gpu::defaultContext();
+  {
+    py::gil_scoped_release release;
+    loam::gpu::check(ctx, c_organize(ctx, layout.handle(), points.data(), stride, rings ? rings->data() : nullptr, n, scan.mutable_data(),
+                                     src.mutable_data(), stats));
+  }
+  return py::make_tuple(scan, src);
 }
 
 loam::Vector3d vec_from(const Arr& a) {
@@ -437,6 +466,25 @@ PYBIND11_MODULE(loam_python, m) {
         return loam::registrationInformation<loam::ParenAccessor>(s, target, pose, params);
       },
       py::arg("source"), py::arg("target_index"), py::arg("target_T_source"), py::arg("params") = loam::RegistrationParams());
+  // unordered clouds into organised scans (include/loamx.h: "unordered clouds into scans"): extensions like TargetIndex
+  py::enum_<loam::OrganizeKeep>(m, "OrganizeKeep").value("First", loam::OrganizeKeep::First).value("Nearest", loam::OrganizeKeep::Nearest);
+  py::class_<loam::OrganizeParams>(m, "OrganizeParams")
+      .def(py::init<>())
+      .def_readwrite("azimuth_zero", &loam::OrganizeParams::azimuth_zero)
+      .def_readwrite("clockwise", &loam::OrganizeParams::clockwise)
+      .def_readwrite("keep", &loam::OrganizeParams::keep)
+      .def_readwrite("elevations", &loam::OrganizeParams::elevations)
+      .def_readwrite("fov_bottom", &loam::OrganizeParams::fov_bottom)
+      .def_readwrite("fov_top", &loam::OrganizeParams::fov_top)
+      .def_readwrite("ring_map", &loam::OrganizeParams::ring_map);
+  py::class_<loam::ScanLayout>(m, "ScanLayout")
+      .def(py::init<const loam::LidarParams&, const loam::OrganizeParams&>(), py::arg("lidar_params"), py::arg("params") = loam::OrganizeParams())
+      .def_property_readonly("scan_lines", &loam::ScanLayout::scanLines)
+      .def_property_readonly("points_per_line", &loam::ScanLayout::pointsPerLine)
+      .def("columnDirections", [](const loam::ScanLayout& l) { return matrix_to_array(l.columnDirections().data(), l.pointsPerLine(), 2); })
+      .def("lineTangents", [](const loam::ScanLayout& l) { return matrix_to_array(l.lineTangents().data(), l.scanLines() + 1, 1); });
+  m.def("organizeCloud", &organize_cloud<float>, py::arg("points"), py::arg("layout"), py::arg("rings") = py::none());
+  m.def("organizeCloud", &organize_cloud<double>, py::arg("points"), py::arg("layout"), py::arg("rings") = py::none());
   m.def("registerScanSequence", &register_scan_sequence<ArrF>, py::arg("scans"), py::arg("lidar_params"),
         py::arg("fe_params") = loam::FeatureExtractionParams(), py::arg("reg_params") = loam::RegistrationParams(),
         py::arg("inits") = py::none());
