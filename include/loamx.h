@@ -190,6 +190,54 @@ typedef struct {
   size_t tile_counts_cap;           /*     min(live_tiles, tile_counts_cap) live tiles */
 } loamx_solve_census;
 int loamx_ctx_last_solve_census(loamx_ctx* ctx, size_t pair, loamx_solve_census* out);
+/* Debug / measurement (no reference counterpart): the route census of the LAST loamx_associate on this context, for one feature
+ * kind (0 = edges, 1 = planes): which kernels the pass launched and how many queries took each route of the k-NN queue chain
+ * — what a test of "route R on scene X" really ran. The launch form is noted by the launcher at the branch that chooses it,
+ * or computed by the functions the kernels themselves call; the counts come from the workspace, and the two things later
+ * kernels overwrite (the count words behind round 1, the counts in front of the queued fit) from a small read-only kernel that
+ * ONLY loamx_associate enqueues: no registration or information call launches or records anything for it. Two things stay
+ * outside it: the stage at which the brute-force body finished a lane, and the cooperative search's "not applicable" return
+ * (a function of the grid, the query's cell distance `out` from the grid and the radius, all reported here:
+ * ceil(r / h) + 1 + out > 64 and max(nx, ny, nz) + out > 64). Valid from a loamx_associate until the next registration,
+ * association or information call on the context; LOAMX_ERR_BAD_PARAM before any and afterwards. Never part of a result. */
+enum { LOAMX_ASSOC_SEARCH_NONE = 0, LOAMX_ASSOC_SEARCH_BRUTE = 1, LOAMX_ASSOC_SEARCH_GRID = 2 }; /* (3: both kernels launched — batches only) */
+enum { LOAMX_ASSOC_LEFTOVER_NONE = 0, LOAMX_ASSOC_LEFTOVER_LEFT = 1, LOAMX_ASSOC_LEFTOVER_COOP = 2 };
+#define LOAMX_ASSOC_REASON_WIDE 0x80000000u /* bits of entry_reason: round 1 ran out of 8-bit running numbers (a dense block) */
+#define LOAMX_ASSOC_REASON_TIED 0x40000000u /* ... its FP32 keys were tied; neither bit: plain (its guard, or outside the grid) */
+typedef struct {
+  /* launch form */
+  uint32_t n_src, n_tgt;       /* queries (clamped to the capacity) and target points of the kind */
+  uint64_t stride;             /* slot capacity of the call */
+  uint32_t km;                 /* neighbour slots of the kernel instantiation: 5, 8 or 16 (0: the kind was not launched; n_tgt and the grid then read 0) */
+  uint32_t search;             /* LOAMX_ASSOC_SEARCH_* */
+  uint32_t mixed_launch;       /* first kernels of both kinds as one launch each (associate_knn_mixed_kernel / _fit_mixed_) */
+  uint32_t one_stage;          /* queue chain in one stage (0 as well where there is no queue chain: brute force) */
+  uint32_t leftover_kernel;    /* LOAMX_ASSOC_LEFTOVER_*: associate_knn_left_kernel or associate_knn_coop_kernel */
+  uint32_t rest_blocks, coop_blocks; /* workgroups per pair of the queue kernels / the cooperative kernel (0: not launched) */
+  uint32_t rest_spread, left_spread; /* the rest / left kernel dealt its entries across all workgroups (else dense) */
+  uint32_t lean_set;           /* the target set is small enough for the lean 5x5x5 search (16-bit positions) */
+  double origin[3], h;         /* the target GridDesc */
+  int32_t nx, ny, nz;
+  uint32_t n_points;
+  /* round 1: the count words behind the k-NN (or brute-force) kernel */
+  uint32_t verified, unverified, queued_words; /* plain counts / selections for the fit to verify / 0xFFFFFFFF */
+  uint32_t queued, queued_plain, queued_wide, queued_tied; /* the queue's length, by the reason bits of its entries */
+  /* queue chain */
+  uint32_t rest_searched;      /* entries associate_knn_rest_kernel's own condition searches (else handed straight on) */
+  uint32_t listed;             /* entries the rest kernel left negative (two stages: listed for the leftover kernel) */
+  uint32_t leftover_finished;  /* listed entries the leftover kernel finished */
+  uint32_t exact;              /* entries still negative in front of associate_fit_queued_kernel: the exact collector's */
+  uint32_t late;               /* selections the fit refused: the late list */
+  /* optional, per queue entry: in: room for entries_cap words each or NULL; out: the first min(queued, entries_cap) */
+  uint32_t* entry_query;       /* the query: its index in the caller's source array */
+  uint32_t* entry_reason;      /* LOAMX_ASSOC_REASON_* */
+  int32_t* count_after_rest;   /* count behind associate_knn_rest_kernel (negative: listed) */
+  int32_t* count_before_fit;   /* count in front of associate_fit_queued_kernel (negative: exact collector) */
+  size_t entries_cap;
+  uint32_t* late_query;        /* in: room for late_cap words or NULL; out: the first min(late, late_cap) queries of the late list */
+  size_t late_cap;             /*     (indices in the caller's source array, in the list's order) */
+} loamx_assoc_census;
+int loamx_ctx_last_assoc_census(loamx_ctx* ctx, int which_kind, loamx_assoc_census* out);
 /* Debug / measurement switches of ONE context (no reference counterpart). loamx_ctx_create reads the environment
  * variables LOAMX_<NAME> once as the defaults (set = 1); no entry point looks at the environment afterwards, and a
  * switch only ever affects the context it was set on. None changes a result beyond the order in which a pair's residual

@@ -193,6 +193,7 @@ EXPORTS = [
     "loamx_shard_range", "loamx_comm_get_unique_id", "loamx_comm_create", "loamx_comm_wrap", "loamx_comm_destroy",
     "loamx_comm_info", "loamx_gather_results_dev", "loamx_comm_barrier", "loamx_comm_stats", "loamx_ctx_extract_counters",
     "loamx_ctx_set_option", "loamx_ctx_get_option", "loamx_ctx_last_extract_route", "loamx_ctx_last_solve_census",
+    "loamx_ctx_last_assoc_census",
     "loamx_fit_lines", "loamx_fit_planes", "loamx_knn_search", "loamx_associate", "loamx_target_index_stats",
     "loamx_register_scan_sequence_dev", "loamx_register_scan_sequence_dev_f32", "loamx_register_scan_sequence",
     "loamx_register_scan_sequence_f32", "loamx_compose_trajectory_dev", "loamx_deskew_scans_dev", "loamx_deskew_scans_dev_f32",
@@ -245,6 +246,29 @@ WALK_NAMES = ("none", "flat", "tiled-by-count", "tiled-by-tiles")
 SolveCensus = collections.namedtuple(
     "SolveCensus", "iterations termination use_moments mom_ref_on mom_ref tiles live_tiles edge_stride planar_stride n_se n_sp walk "
                    "listed_total s0max v2max sweep_chunk edge_cache list_cache flat_cache tile_counts")
+
+
+class AssocCensusStruct(C.Structure):
+    """loamx_assoc_census (include/loamx.h)"""
+    _fields_ = ([("n_src", C.c_uint32), ("n_tgt", C.c_uint32), ("stride", C.c_uint64)] +
+                [(n, C.c_uint32) for n in ("km", "search", "mixed_launch", "one_stage", "leftover_kernel", "rest_blocks", "coop_blocks",
+                                           "rest_spread", "left_spread", "lean_set")] +
+                [("origin", C.c_double * 3), ("h", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32)] +
+                [(n, C.c_uint32) for n in ("n_points", "verified", "unverified", "queued_words", "queued", "queued_plain", "queued_wide",
+                                           "queued_tied", "rest_searched", "listed", "leftover_finished", "exact", "late")] +
+                [("entry_query", C.POINTER(C.c_uint32)), ("entry_reason", C.POINTER(C.c_uint32)),
+                 ("count_after_rest", C.POINTER(C.c_int32)), ("count_before_fit", C.POINTER(C.c_int32)), ("entries_cap", C.c_size_t),
+                 ("late_query", C.POINTER(C.c_uint32)), ("late_cap", C.c_size_t)])
+
+
+ASSOC_SEARCH_NONE, ASSOC_SEARCH_BRUTE, ASSOC_SEARCH_GRID = 0, 1, 2
+ASSOC_LEFTOVER_NONE, ASSOC_LEFTOVER_LEFT, ASSOC_LEFTOVER_COOP = 0, 1, 2
+ASSOC_REASON_WIDE, ASSOC_REASON_TIED = 0x80000000, 0x40000000
+ASSOC_CENSUS_SCALARS = ("n_src n_tgt stride km search mixed_launch one_stage leftover_kernel rest_blocks coop_blocks rest_spread left_spread "
+                        "lean_set h nx ny nz n_points verified unverified queued_words queued queued_plain queued_wide queued_tied "
+                        "rest_searched listed leftover_finished exact late").split()
+AssocCensus = collections.namedtuple("AssocCensus", ASSOC_CENSUS_SCALARS + ["origin", "entry_query", "entry_reason", "count_after_rest",
+                                                                            "count_before_fit", "late_query"])
 
 
 class IndexCensusStruct(C.Structure):
@@ -383,6 +407,7 @@ def load(build_if_missing=True):
     lib.loamx_ctx_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int)]
     lib.loamx_ctx_last_extract_route.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.loamx_ctx_last_solve_census.argtypes = [vp, C.c_size_t, C.POINTER(SolveCensusStruct)]
+    lib.loamx_ctx_last_assoc_census.argtypes = [vp, C.c_int, C.POINTER(AssocCensusStruct)]
     lib.loamx_registration_information.argtypes = [vp, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp,
                                                    C.POINTER(RegistrationParams), C.POINTER(RegInformation)]
     lib.loamx_registration_information_indexed.argtypes = [vp, vp, dp, C.c_size_t, dp, C.c_size_t, dp, C.POINTER(RegistrationParams),
@@ -645,6 +670,25 @@ class Context:
         return SolveCensus(v.iterations, v.termination, v.use_moments, v.mom_ref_on, np.array(list(v.mom_ref)), v.tiles, v.live_tiles,
                            v.edge_stride, v.planar_stride, v.n_se, v.n_sp, v.walk, v.listed_total, v.s0max, v.v2max, v.sweep_chunk,
                            v.edge_cache, v.list_cache, v.flat_cache, counts[:v.live_tiles].copy())
+
+    def last_assoc_census(self, kind):
+        """the route census of the last associate() on this context for one feature kind (0 / "edge", 1 / "plane"; include/loamx.h:
+        loamx_ctx_last_assoc_census), as an AssocCensus with the per-entry arrays of the kind's queue"""
+        kind = {"edge": 0, "plane": 1}.get(kind, kind)
+        v = AssocCensusStruct()
+        self._check(self.lib.loamx_ctx_last_assoc_census(self.h, kind, C.byref(v)))  # (no arrays: the queue's length)
+        q = int(v.queued)
+        eq, er = np.zeros(max(1, q), dtype=np.uint32), np.zeros(max(1, q), dtype=np.uint32)
+        ar, bf = np.zeros(max(1, q), dtype=np.int32), np.zeros(max(1, q), dtype=np.int32)
+        v.entry_query, v.entry_reason = eq.ctypes.data_as(C.POINTER(C.c_uint32)), er.ctypes.data_as(C.POINTER(C.c_uint32))
+        v.count_after_rest, v.count_before_fit = ar.ctypes.data_as(C.POINTER(C.c_int32)), bf.ctypes.data_as(C.POINTER(C.c_int32))
+        v.entries_cap = q
+        nl = int(v.late)
+        lq = np.zeros(max(1, nl), dtype=np.uint32)
+        v.late_query, v.late_cap = lq.ctypes.data_as(C.POINTER(C.c_uint32)), nl
+        self._check(self.lib.loamx_ctx_last_assoc_census(self.h, kind, C.byref(v)))
+        return AssocCensus(*[getattr(v, n) for n in ASSOC_CENSUS_SCALARS], np.array(list(v.origin)), eq[:q].copy(), er[:q].copy(),
+                           ar[:q].copy(), bf[:q].copy(), lq[:nl].copy())
 
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)

@@ -30,7 +30,7 @@ enum WsId {
 enum WsKindId {
   WSK_STAGE = 0, WSK_CNT, WSK_IDX, WSK_N, WSK_XYZ,
   WSK_GRID_DESC, WSK_CELLS, WSK_SORTED, WSK_REL, WSK_SGRID_DESC, WSK_SCELLS, WSK_SSORTED, WSK_ASSOC, WSK_NN, WSK_RNN, WSK_NEAREST,
-  WSK_REST, WSK_EXACT, WSK_DUMP, WSK_SRC, WSK_TGT, WSK_MAP_TMP, WSK_MAP_OUT,
+  WSK_REST, WSK_EXACT, WSK_DUMP, WSK_SRC, WSK_TGT, WSK_MAP_TMP, WSK_MAP_OUT, WSK_CENSUS,
   WSK_COUNT
 };
 
@@ -82,6 +82,15 @@ struct loamx_ctx {
   loamx::RegBatch last_solve_batch = {};
   uint32_t last_solve_flags = 0;  // RegConfig::flags of that call
   bool last_solve_valid = false;
+  // the last reg_dump's association census per feature kind (loamx_ctx_last_assoc_census): host copies, complete when reg_dump
+  // returns; the pointers of `c` are unused, the per-entry arrays live in the vectors. Good until the next reg_prepare.
+  struct AssocCensusKept {
+    loamx_assoc_census c;
+    std::vector<uint32_t> entry;  // the queue's entries: query index | reason bits
+    std::vector<int32_t> after_rest, before_fit;
+    std::vector<uint32_t> late;   // the late list's queries
+  } last_assoc_census[2];
+  bool last_assoc_census_valid = false;
 
   unsigned long long sweep_slots_base[2] = {0, 0};
   unsigned long long features_base = 0;  // events[2] at the last loamx_ctx_reset_kernel_stats

@@ -7,7 +7,8 @@ using namespace loamx;
 namespace {
 
 // the association kernels of one ICF iteration (all feature kinds, all chains), timed as LOAMX_K_ASSOC
-int enqueue_association(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, uint32_t what = kAssocEdges | kAssocPlanes) {
+int enqueue_association(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, uint32_t what = kAssocEdges | kAssocPlanes,
+                        AssocCensusRun* census = nullptr) {
   hipStream_t s = ctx->stream;
   {
     TimedScope t(ctx, LOAMX_K_ASSOC, 0.0);
@@ -24,7 +25,7 @@ int enqueue_association(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, u
       knn_ls = LaunchScope{knn.e0, knn.e1, true};
     }
     launch_associate(B, C, s, side ? ctx->aux_stream : nullptr, side ? ctx->aux2_stream : nullptr, ctx->ev_fork, ctx->ev_mid, ctx->ev_join,
-                     ctx->ev_join2, ctx->timing ? &knn_ls : nullptr, what);
+                     ctx->ev_join2, ctx->timing ? &knn_ls : nullptr, what, census);
     if (ctx->timing) {
       if (knn_ls.first) ctx->event_pool.push_back(knn.e0), ctx->event_pool.push_back(knn.e1);  // (kernel not launched)
       else ctx->pending.push_back(knn);
@@ -102,6 +103,7 @@ namespace loamx {
 int reg_prepare(loamx_ctx* ctx, const RegInputs& in, RegConfig& C, const loamx_target_index* prebuilt, const RegPrepareOpts& opts, RegBatch& B) {
   B = RegBatch{};
   ctx->last_solve_valid = false;  // (the workspace the solve readout points into may move below)
+  ctx->last_assoc_census_valid = false;  // (the census is its own dump's: a later call of any kind ends it)
   if (in.n_pairs == 0) return LOAMX_OK;
   if (opts.one_pass && C.max_iterations == 0) C.max_iterations = 1;
   untimed(ctx);
@@ -243,7 +245,17 @@ int reg_dump(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, const loamx_
   if (B.n_pairs != 1) return fail(ctx, LOAMX_ERR_BAD_PARAM, "association dump: one pair at a time");
   RegBatch Bd = B;
   Bd.want_nn_counts = 1u;  // (assoc_dump_kernel reads the verified counts out of nn: only here does fit_one write them back)
-  int rc_a = enqueue_association(ctx, Bd, C);
+  // the association census (loamx_ctx_last_assoc_census): only here is launch_associate handed a census to fill
+  AssocCensusRun census = {};
+  for (int kind = 0; kind < 2; kind++) {
+    const size_t st = B.kind[kind].stride, bytes = 8 * sizeof(uint32_t) + 2 * st * sizeof(int32_t);
+    ENSURE(ctx, ctx->wsk[WSK_CENSUS][kind], bytes);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->wsk[WSK_CENSUS][kind].p, 0, bytes, s));
+    census.buf[kind].counts = wskp<uint32_t>(ctx, WSK_CENSUS, kind);
+    census.buf[kind].after_rest = reinterpret_cast<int32_t*>(census.buf[kind].counts + 8);
+    census.buf[kind].before_fit = census.buf[kind].after_rest + st;
+  }
+  int rc_a = enqueue_association(ctx, Bd, C, kAssocEdges | kAssocPlanes, &census);
   if (rc_a != LOAMX_OK) return rc_a;
   untimed(ctx);
   const size_t n[2] = {n_src[kEdge], n_src[kPlane]}, kq[2] = {(size_t)C.kind[kEdge].k, (size_t)C.kind[kPlane].k}, pw[2] = {6, 4};
@@ -272,6 +284,60 @@ int reg_dump(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, const loamx_
     if (o.host && o.bytes && o.dev) HIP_TRY(ctx, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, s));
   if (dump->queue_lengths) HIP_TRY(ctx, hipMemcpyAsync(dump->queue_lengths, B.n_assoc + 2, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
+  // the census, kept on the context as host copies: the workspace may be handed on by the next call
+  uint32_t na[8];
+  HIP_TRY(ctx, hipMemcpy(na, B.n_assoc, sizeof(na), hipMemcpyDeviceToHost));
+  for (int kind = 0; kind < 2; kind++) {
+    const RegKind& K = B.kind[kind];
+    const AssocCensusForm& F = census.form[kind];
+    loamx_ctx::AssocCensusKept& keep = ctx->last_assoc_census[kind];
+    loamx_assoc_census& c = keep.c;
+    c = loamx_assoc_census{};
+    GridDesc g;
+    uint32_t counts[8];
+    HIP_TRY(ctx, hipMemcpy(&g, K.grid.desc, sizeof(g), hipMemcpyDeviceToHost));
+    if (F.km == 0u) g = GridDesc{};  // (the kind was not launched: whatever the descriptor holds is an earlier call's)
+    HIP_TRY(ctx, hipMemcpy(counts, census.buf[kind].counts, sizeof(counts), hipMemcpyDeviceToHost));
+    c.n_src = (uint32_t)(n[kind] < K.stride ? n[kind] : K.stride), c.n_tgt = g.n_points, c.stride = K.stride;
+    c.km = F.km, c.search = F.search, c.mixed_launch = F.mixed_launch, c.one_stage = F.one_stage, c.leftover_kernel = F.leftover_kernel;
+    c.rest_blocks = F.rest_blocks, c.coop_blocks = F.coop_blocks;
+    c.origin[0] = g.ox, c.origin[1] = g.oy, c.origin[2] = g.oz, c.h = g.h, c.nx = g.nx, c.ny = g.ny, c.nz = g.nz, c.n_points = g.n_points;
+    c.verified = counts[0], c.unverified = counts[1], c.queued_words = counts[2];
+    c.queued = na[2 + kind], c.listed = na[4 + kind], c.exact = counts[4], c.leftover_finished = counts[3] - counts[4], c.late = na[6 + kind];
+    const uint32_t q = c.queued < K.stride ? c.queued : (uint32_t)K.stride;
+    keep.entry.assign(q, 0u), keep.after_rest.assign(q, 0), keep.before_fit.assign(q, 0);
+    if (q) {
+      HIP_TRY(ctx, hipMemcpy(keep.entry.data(), K.rest, q * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      HIP_TRY(ctx, hipMemcpy(keep.after_rest.data(), census.buf[kind].after_rest, q * sizeof(int32_t), hipMemcpyDeviceToHost));
+      HIP_TRY(ctx, hipMemcpy(keep.before_fit.data(), census.buf[kind].before_fit, q * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    uint32_t derived[4];  // (from the entries as the kernels read them: index in the source set's cell order | reason bits)
+    assoc_census_derive(F, B.n_pairs, g, keep.entry.data(), q, na[4 + kind], derived);
+    c.rest_spread = derived[0], c.left_spread = derived[1], c.lean_set = derived[2], c.rest_searched = derived[3];
+    // the late list: the tail of K.exact, filled from its end (fit_one)
+    const uint32_t nl = c.late < K.stride ? c.late : (uint32_t)K.stride;
+    keep.late.assign(nl, 0u);
+    if (nl) HIP_TRY(ctx, hipMemcpy(keep.late.data(), K.exact + (K.stride - nl), nl * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (q || nl) {  // kept by the CALLER's source index: the cell-sorted copy of the source set names it
+      std::vector<GridPoint> sorted(c.n_src);
+      HIP_TRY(ctx, hipMemcpy(sorted.data(), K.src_grid.sorted, (size_t)c.n_src * sizeof(GridPoint), hipMemcpyDeviceToHost));
+      for (uint32_t t = 0; t < q; t++) {
+        const uint32_t i = keep.entry[t] & 0x3FFFFFFFu;
+        keep.entry[t] = (keep.entry[t] & ~0x3FFFFFFFu) | (i < c.n_src ? (sorted[i].orig & 0x3FFFFFFFu) : 0x3FFFFFFFu);
+      }
+      std::vector<uint32_t> tail(keep.late);
+      for (uint32_t t = 0; t < nl; t++) {  // (entry t of the list sits at stride - 1 - t)
+        const uint32_t i = tail[nl - 1 - t];
+        keep.late[t] = i < c.n_src ? sorted[i].orig : 0xFFFFFFFFu;
+      }
+    }
+    for (uint32_t t = 0; t < q; t++) {
+      if (keep.entry[t] & LOAMX_ASSOC_REASON_WIDE) c.queued_wide++;
+      else if (keep.entry[t] & LOAMX_ASSOC_REASON_TIED) c.queued_tied++;
+      else c.queued_plain++;
+    }
+  }
+  ctx->last_assoc_census_valid = true;
   return LOAMX_OK;
 }
 
@@ -549,6 +615,30 @@ int loamx_ctx_last_solve_census(loamx_ctx* ctx, size_t pair, loamx_solve_census*
   }
   // lm_pair_loop_kernel: the flat list needs the tile counts in LDS (tiles <= kListCache) and room for the records
   out->walk = out->tiles > kListCache ? LOAMX_WALK_TILED_BY_TILES : (out->listed_total > kFlatCache ? LOAMX_WALK_TILED_BY_COUNT : LOAMX_WALK_FLAT);
+  return LOAMX_OK;
+}
+
+/* ---- association readout (debug / tests): the census the last loamx_associate left on the context, no device access ---- */
+int loamx_ctx_last_assoc_census(loamx_ctx* ctx, int which_kind, loamx_assoc_census* out) {
+  if (!out) return LOAMX_ERR_BAD_PARAM;
+  API_LOCK(ctx);
+  if (which_kind != 0 && which_kind != 1) return fail(ctx, LOAMX_ERR_BAD_PARAM, "which_kind: 0 = edges, 1 = planes");
+  if (!ctx->last_assoc_census_valid) return fail(ctx, LOAMX_ERR_BAD_PARAM, "no association dump on this context to read (or another call came after it)");
+  const loamx_ctx::AssocCensusKept& keep = ctx->last_assoc_census[which_kind];
+  uint32_t *const eq = out->entry_query, *const er = out->entry_reason;
+  int32_t *const ar = out->count_after_rest, *const bf = out->count_before_fit;
+  const size_t cap = out->entries_cap, lcap = out->late_cap;
+  uint32_t* const lq = out->late_query;
+  *out = keep.c;
+  out->late_query = lq, out->late_cap = lcap;
+  for (size_t t = 0; lq && t < keep.late.size() && t < lcap; t++) lq[t] = keep.late[t];
+  out->entry_query = eq, out->entry_reason = er, out->count_after_rest = ar, out->count_before_fit = bf, out->entries_cap = cap;
+  for (size_t t = 0; t < keep.entry.size() && t < cap; t++) {
+    if (eq) eq[t] = keep.entry[t] & 0x3FFFFFFFu;
+    if (er) er[t] = keep.entry[t] & (LOAMX_ASSOC_REASON_WIDE | LOAMX_ASSOC_REASON_TIED);
+    if (ar) ar[t] = keep.after_rest[t];
+    if (bf) bf[t] = keep.before_fit[t];
+  }
   return LOAMX_OK;
 }
 

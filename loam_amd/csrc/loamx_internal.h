@@ -309,12 +309,39 @@ struct GridBuildForm {
 GridBuildForm launch_grid_build_target(const RegBatch& B, const RegConfig& C, int kind, hipStream_t s);  // one feature kind
 void launch_grid_build_source(const RegBatch& B, const RegConfig& C, int kind, hipStream_t s);
 void launch_state_init(const RegBatch& B, const RegConfig& C, hipStream_t s);
+// The association census of an association dump (loamx_ctx_last_assoc_census). Per feature kind: what
+// launch_associate chose, noted at the branch that chooses it (a read-out, never a second copy of a predicate), and the
+// device words assoc_census_kernel fills at the two points of the chain whose words later kernels overwrite. Only reg_dump
+// hands one to launch_associate: no other caller launches anything for it.
+struct AssocCensusForm {
+  uint32_t search;           // LOAMX_ASSOC_SEARCH_*: bit 0 the brute-force kernel was launched, bit 1 the grid kernel
+  uint32_t km;               // neighbour slots of the instantiation (5 / 8 / 16)
+  uint32_t mixed_launch;     // the first kernels of both kinds ran as ONE launch each
+  uint32_t one_stage;        // queue_one_stage's answer (0 where no queue chain was launched)
+  uint32_t leftover_kernel;  // LOAMX_ASSOC_LEFTOVER_*
+  uint32_t rest_blocks, coop_blocks;  // workgroups per pair of the queue kernels / of the cooperative kernel (0: not launched)
+};
+struct AssocCensusBuf {
+  uint32_t* counts;     // [8] zeroed by the caller: [0..2] verified / unverified / queued count words behind round 1,
+                        // [3] negative counts behind associate_knn_rest_kernel, [4] in front of associate_fit_queued_kernel
+  int32_t* after_rest;  // [stride] the counts by queue position behind associate_knn_rest_kernel ...
+  int32_t* before_fit;  // ... and in front of associate_fit_queued_kernel
+};
+struct AssocCensusRun {
+  AssocCensusForm form[2];
+  AssocCensusBuf buf[2];
+};
+// what the queue kernels decide from a queue's length and its entries, through the functions the kernels themselves call:
+// out = {rest_spread, left_spread, lean_set, rest_searched}; rest = the queue's `queued` entries (host copy)
+void assoc_census_derive(const AssocCensusForm& F, size_t n_pairs, const GridDesc& g, const uint32_t* rest, uint32_t queued, uint32_t listed,
+                         uint32_t out[4]);
 // aux == nullptr: everything on s; aux2 == nullptr: the plane queue chain follows the edge chain on aux
 // knn_scope != nullptr: the plane round-1 k-NN kernel is launched with that timing scope attached
+// census != nullptr (reg_dump, one pair): the choices are noted in census->form and assoc_census_kernel reads the chain's words
 constexpr uint32_t kAssocEdges = 1u, kAssocPlanes = 2u;
 void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipStream_t aux, hipStream_t aux2, hipEvent_t ev_fork,
                       hipEvent_t ev_mid, hipEvent_t ev_join, hipEvent_t ev_join2, LaunchScope* knn_scope = nullptr,
-                      uint32_t what = kAssocEdges | kAssocPlanes);
+                      uint32_t what = kAssocEdges | kAssocPlanes, AssocCensusRun* census = nullptr);
 #ifdef LOAMX_NN_SAME_STATS
 void debug_nn_same(const RegBatch& B, uint32_t it, hipStream_t s);
 #endif

@@ -946,6 +946,8 @@ __global__ __launch_bounds__(kAssocThreads) void associate_knn_brute_kernel(RegB
 
 // entries of the queues rest_*: a query index and why round 1 queued it
 constexpr uint32_t kQueueIndex = 0x3FFFFFFFu, kQueueWide = 0x80000000u, kQueueTied = 0x40000000u;
+static_assert(kQueueWide == LOAMX_ASSOC_REASON_WIDE && kQueueTied == LOAMX_ASSOC_REASON_TIED && kQueueIndex == 0x3FFFFFFFu,
+              "loamx_ctx_last_assoc_census hands the reason bits out as they are");
 
 // Association is split in two kernels so that each runs at its own register budget:
 //   associate_knn_kernel : the latency-bound grid walk; writes the neighbour count and the positions
@@ -1054,6 +1056,18 @@ constexpr int kRestThreads = LOAMX_REST_THREADS;  // small workgroups: the queue
 __host__ __device__ inline bool queue_leftovers_coop(const RegConfig& C, int kind) {
   return !(C.flags & kRegFlagNoCoopLeft) && C.kind[kind].r > 0.0;
 }
+// What the queue kernels decide from a queue's length, the target set and an entry's reason bits: one function each, called
+// by the kernel and by the association census (assoc_census_derive) alike, so that the census cannot drift from the kernels.
+// Which queue entries a wavefront takes (see associate_knn_rest_kernel): dealt out across all workgroups, or dense.
+__host__ __device__ inline bool queue_spread(size_t n_pairs, uint32_t entries, uint32_t blocks_per_pair) {
+  return n_pairs < 8 && (size_t)entries * 4 <= (size_t)blocks_per_pair * kRestThreads;
+}
+// (a property of the set: the lean search carries positions as 16-bit halves)
+__host__ __device__ inline bool queue_lean_set(const GridDesc& g) { return g.n_points <= kLeanMaxPoints; }
+// Does associate_knn_rest_kernel search this entry itself? (coop: the listed leftovers go to the cooperative kernel)
+__host__ __device__ inline bool queue_rest_searches(uint32_t entry, bool one_stage, bool lean_set, bool coop) {
+  return one_stage || (!(entry & kQueueTied) && ((lean_set && !(entry & kQueueWide)) || ((entry & kQueueWide) && !coop)));
+}
 #ifndef LOAMX_COOP_WAVES
 #define LOAMX_COOP_WAVES 4
 #endif
@@ -1088,10 +1102,10 @@ __global__ __launch_bounds__(kRestThreads, LOAMX_REST_WAVES(KM)) void associate_
   // to the plane fit and should cost as few issue slots as possible); a handful of pairs leaves the chip empty, and then
   // the latency of the slowest wavefront is the kernel's time: the entries are dealt out across ALL workgroups, one or
   // two per wavefront (one 64 x 1024 pair: 480 entries on 276 wavefronts instead of 8 — 71 -> 25 us per launch).
-  const bool spread = B.n_pairs < 8 && (size_t)queued * 4 <= (size_t)blocks_per_pair * kRestThreads;
+  const bool spread = queue_spread(B.n_pairs, queued, blocks_per_pair);
   const uint32_t t0 = spread ? chunk0 + blocks_per_pair * threadIdx.x : chunk0 * kRestThreads + threadIdx.x;
   const uint32_t dt = spread ? 0xFFFFFFFFu - t0 : blocks_per_pair * kRestThreads;  // (spread: one entry per lane)
-  const bool lean_set = g.n_points <= kLeanMaxPoints;  // (uniform: a property of the set; positions travel as 16-bit halves)
+  const bool lean_set = queue_lean_set(g);  // (uniform: a property of the set; positions travel as 16-bit halves)
   const int kq = CK.k;
   const double max_dist = CK.r, pass_max = CK.pass;
   for (uint32_t t = t0; t < queued; t += dt) {
@@ -1102,7 +1116,7 @@ __global__ __launch_bounds__(kRestThreads, LOAMX_REST_WAVES(KM)) void associate_
     for (int j = 0; j < KM; j++) pos[j] = 0;
     int kept = -1;
     const bool coop = !one_stage && queue_leftovers_coop(C, PLANE);  // (wide entries: a dense block is the cooperative kernel's business)
-    if (one_stage || (!(entry & kQueueTied) && ((lean_set && !(entry & kQueueWide)) || ((entry & kQueueWide) && !coop)))) {
+    if (queue_rest_searches(entry, one_stage, lean_set, coop)) {
       const GridPoint sq = src_gs.sorted[pair * src_gs.stride + i];
       const Vec3 p = pose_act(S.est, v3(sq.x, sq.y, sq.z));
       if (entry & kQueueWide)
@@ -1146,7 +1160,7 @@ __global__ __launch_bounds__(kRestThreads, kLeftWaves) void associate_knn_left_k
   const GridDesc g = gs.desc[pair];
   const uint32_t* __restrict__ cs = gs.cell_start + pair * (size_t)(kGridCellsCap + 1);
   const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
-  const bool spread = B.n_pairs < 8 && (size_t)listed * 4 <= (size_t)blocks_per_pair * kRestThreads;  // (as above)
+  const bool spread = queue_spread(B.n_pairs, listed, blocks_per_pair);  // (as above)
   const uint32_t t0 = spread ? chunk0 + blocks_per_pair * threadIdx.x : chunk0 * kRestThreads + threadIdx.x;
   const uint32_t dt = spread ? 0xFFFFFFFFu - t0 : blocks_per_pair * kRestThreads;
   for (uint32_t t = t0; t < listed; t += dt) {
@@ -2424,6 +2438,37 @@ void launch_knn_queries(const GridSet& gs, const double* d_q, size_t n_q, int k,
   else launch_kernel((knn_queries_kernel<16>), grid, dim3(64), 0, s, gs, d_q, n_q, k, max_dist, pass_max, d_idx, d_count);
 }
 
+// The association census (loamx_ctx_last_assoc_census) of the ONE pair of an association dump: the two things of the chain
+// that later kernels overwrite, read where launch_associate enqueues this kernel. stage 0: the count words of K.nn behind the
+// round-1 (or brute-force) kernel, counted by class — the fit writes verified counts over them; stage 1 / 2: the counts of
+// K.rnn by queue position behind associate_knn_rest_kernel / in front of associate_fit_queued_kernel, copied, the negative
+// ones counted — the leftover kernel and the exact collector write over them.
+__global__ __launch_bounds__(256) void assoc_census_kernel(RegBatch B, int kind, AssocCensusBuf out, int stage) {
+  const RegKind& K = B.kind[kind];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= K.stride) return;
+  if (stage == 0) {
+    if (i >= K.n_src[0]) return;
+    const uint32_t w = K.nn[i];
+    atomicAdd(&out.counts[w == kNnQueued ? 2 : ((w & kNnUnverified) ? 1 : 0)], 1u);
+    return;
+  }
+  if (i >= B.n_assoc[kind ? 3 : 2]) return;
+  const int32_t c = (int32_t)K.rnn[i];
+  (stage == 1 ? out.after_rest : out.before_fit)[i] = c;
+  if (c < 0) atomicAdd(&out.counts[2 + stage], 1u);
+}
+void assoc_census_derive(const AssocCensusForm& F, size_t n_pairs, const GridDesc& g, const uint32_t* rest, uint32_t queued, uint32_t listed,
+                         uint32_t out[4]) {
+  const bool chain = F.rest_blocks != 0u, lean_set = queue_lean_set(g);
+  out[0] = chain && queue_spread(n_pairs, queued, F.rest_blocks) ? 1u : 0u;
+  out[1] = F.leftover_kernel == LOAMX_ASSOC_LEFTOVER_LEFT && queue_spread(n_pairs, listed, F.rest_blocks) ? 1u : 0u;
+  out[2] = lean_set ? 1u : 0u;
+  out[3] = 0u;
+  for (uint32_t t = 0; chain && t < queued; t++)
+    out[3] += queue_rest_searches(rest[t], F.one_stage != 0u, lean_set, F.leftover_kernel == LOAMX_ASSOC_LEFTOVER_COOP) ? 1u : 0u;
+}
+
 void launch_assoc_dump(const RegBatch& B, const RegConfig& C, const AssocDumpSet (&out)[2], hipStream_t s) {
 #define LOAMX_DUMP(PL)                                                                                                                  \
   if (out[PL].nn_count) {                                                                                                               \
@@ -2610,8 +2655,16 @@ static uint32_t rest_blocks(size_t n_pairs, uint32_t nblk) {
 // what: bit 0 = the edge chains, bit 1 = the plane chains (the first ICF iteration's edge chains can run early, next to the
 // planar index builds: launch_associate(..., kAssocEdges) on the stream that built the edge sets, then kAssocPlanes)
 void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipStream_t aux, hipStream_t aux2, hipEvent_t ev_fork,
-                      hipEvent_t ev_mid, hipEvent_t ev_join, hipEvent_t ev_join2, LaunchScope* knn_scope, uint32_t what) {
+                      hipEvent_t ev_mid, hipEvent_t ev_join, hipEvent_t ev_join2, LaunchScope* knn_scope, uint32_t what,
+                      AssocCensusRun* census) {
   if (B.n_pairs == 0) return;
+  // (association census, reg_dump only: `note` keeps a choice where it is made, `census_at` reads the chain's words there)
+  auto census_at = [&](int kind, int stage, hipStream_t st) {
+    if (census && census->buf[kind].counts && B.kind[kind].stride)
+      launch_kernel(assoc_census_kernel, dim3((unsigned)((B.kind[kind].stride + 255) / 256)), dim3(256), 0, st, B, kind, census->buf[kind], stage);
+  };
+  AssocCensusRun unread = {};
+  AssocCensusForm* const note = census ? census->form : unread.form;
   auto blocks = [](const RegKind& K) { return K.assoc_blocks != 0xFFFFFFFFu ? K.assoc_blocks : (uint32_t)((K.stride + kAssocThreads - 1) / kAssocThreads); };
   const uint32_t be = blocks(B.kind[kEdge]), bp = blocks(B.kind[kPlane]);
   const size_t pair_groups = (B.n_pairs + 7) / 8;  // grid covers 8 XCD lanes x pair_groups x chunks
@@ -2625,14 +2678,19 @@ void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipS
   do {                                                                                                            \
     const dim3 grid_((unsigned)(pair_groups * 8 * (nblk)));                                                       \
     const uint32_t mode_ = B.kind[PL].knn_mode; /* a kernel no pair needs is not launched */                      \
+    note[PL].km = (KMV);                                                                                          \
     if (mode_ != 2u) {                                                                                            \
+      note[PL].search |= LOAMX_ASSOC_SEARCH_GRID;                                                                 \
       LaunchScope* outer_ = g_launch_scope;                                                                       \
       if ((PL) && knn_scope) g_launch_scope = knn_scope;                                                          \
       launch_kernel((associate_knn_kernel<PL, KMV>), grid_, dim3(kAssocThreads), 0, (st), B, C, (nblk));     \
       g_launch_scope = outer_;                                                                                    \
     }                                                                                                             \
-    if (mode_ != 1u)                                                                                              \
+    if (mode_ != 1u) {                                                                                            \
+      note[PL].search |= LOAMX_ASSOC_SEARCH_BRUTE;                                                                \
       launch_kernel((associate_knn_brute_kernel<PL, KMV>), grid_, dim3(kAssocThreads), 0, (st), B, C, (nblk)); \
+    }                                                                                                             \
+    census_at((PL), 0, (st));                                                                                     \
   } while (0)
 #define LOAMX_ASSOC_A2(PL, KMV, nblk, st)                                                                         \
   launch_kernel((associate_fit_kernel<PL, KMV>), dim3((unsigned)(pair_groups * 8 * (nblk))), dim3(kAssocThreads), 0, \
@@ -2641,21 +2699,27 @@ void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipS
   do {                                                                                                            \
     const uint32_t rblk_ = rest_blocks(B.n_pairs, (nblk));                                                        \
     const uint32_t one_ = queue_one_stage(B, C, (PL)) ? 1u : 0u;                                                  \
+    note[PL].km = (KMV), note[PL].rest_blocks = rblk_, note[PL].one_stage = one_;                                 \
     if (one_) {                                                                                                   \
       launch_kernel((associate_knn_rest_kernel<PL, KMV, true>), dim3((unsigned)(pair_groups * 8 * rblk_)),   \
                          dim3(kRestThreads), 0, (st), B, C, rblk_);                                               \
+      census_at((PL), 1, (st));                                                                                   \
     } else {                                                                                                      \
       launch_kernel((associate_knn_rest_kernel<PL, KMV, false>), dim3((unsigned)(pair_groups * 8 * rblk_)),  \
                          dim3(kRestThreads), 0, (st), B, C, rblk_);                                               \
+      census_at((PL), 1, (st));                                                                                   \
       if (!queue_leftovers_coop(C, (PL))) {                                                                       \
+        note[PL].leftover_kernel = LOAMX_ASSOC_LEFTOVER_LEFT;                                                     \
         launch_kernel((associate_knn_left_kernel<PL, KMV>), dim3((unsigned)(pair_groups * 8 * rblk_)),       \
                            dim3(kRestThreads), 0, (st), B, C, rblk_);                                             \
       } else {                                                                                                    \
         const uint32_t cblk_ = coop_blocks(B.n_pairs);                                                            \
+        note[PL].leftover_kernel = LOAMX_ASSOC_LEFTOVER_COOP, note[PL].coop_blocks = cblk_;                       \
         launch_kernel((associate_knn_coop_kernel<PL, KMV>), dim3((unsigned)(pair_groups * 8 * cblk_)),       \
                            dim3(kRestThreads), 0, (st), B, C, cblk_);                                             \
       }                                                                                                           \
     }                                                                                                             \
+    census_at((PL), 2, (st));                                                                                     \
     launch_kernel((associate_fit_queued_kernel<PL, KMV>), dim3((unsigned)(pair_groups * 8 * rblk_)),         \
                        dim3(kRestThreads), 0, (st), B, C, rblk_);                                                 \
   } while (0)
@@ -2677,6 +2741,9 @@ void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipS
     if (knn_scope) g_launch_scope = knn_scope;
     launch_kernel((associate_knn_mixed_kernel<5, 5>), grid, dim3(kAssocThreads), 0, s, B, C, be, bp, edge_blocks);
     g_launch_scope = outer;
+    note[kEdge].mixed_launch = note[kPlane].mixed_launch = 1u, note[kEdge].km = note[kPlane].km = 5u;
+    note[kEdge].search = LOAMX_ASSOC_SEARCH_BRUTE, note[kPlane].search = LOAMX_ASSOC_SEARCH_GRID;
+    census_at(kEdge, 0, s), census_at(kPlane, 0, s);  // (in front of the fork, as in the other path, and of the fit, which writes verified counts over the words)
     hipStream_t sb = aux2 ? aux2 : aux;
     // (Round 5: the fork / join events as the kernels' own completion events — hipExtLaunchKernelGGL's stop event instead of
     // hipEventRecord — shorten the gap in front of the fit from 6.4 to 5.3 us, but the host's wait at the end of the step

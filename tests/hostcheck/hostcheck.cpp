@@ -435,6 +435,69 @@ uint64_t hostcheck_knn(const double* pts, uint64_t n, const double q[3], uint64_
   return (uint64_t)kept;
 }
 
+// The route of every query through the association's k-NN queue chain, piece by piece, by the functions the kernels call in
+// the kernels' order (tests/test_assoc_routes_hostcheck.py composes the forms of the chain from the pieces):
+//   out[4 i]     = round 1: 0 finished, 1 queued plain, 2 queued wide, 3 queued tied | LOAMX_LEAN_REASON << 8 (where it returned -1)
+//                  | bit 16: the count word is an unverified selection (hand-off form) | bit 17: ... which the fit's verification refuses
+//                  | bit 18: ... and would refuse with the selected neighbours in exact ascending order too (a refusal for a reason
+//                  other than their order: bit 17 alone depends on the order of the target points INSIDE a cell, which the device
+//                  builds do not fix — FP32 keys that tie are ordered by their running numbers)
+//   out[4 i + 1] = the lean 5x5x5 search's return + 4 (0: not applicable — the set is above kLeanMaxPoints)
+//   out[4 i + 2] = the wide-number search's return + 4
+//   out[4 i + 3] = the keyed search's return + 4 (below 4: left to the exact collector)
+// handoff: the round-1 form of the mixed launch's plane side (KM = 5: selection from the keys, verified by the fit), as
+// tests/hostcheck_handoff runs it. The three later pieces are filled for queued queries only.
+extern "C++" {
+template <int KM>
+static void knn_route(const HostGrid& G, Vec3 q, int k, double max_dist, bool handoff, uint32_t out[4]) {
+  uint32_t rows[kLean4RowWords] = {}, pos[KM], word = 0;
+  const double pass_max = knn_radius_pass_max(max_dist);
+  const uint32_t plane = (uint32_t)G.sp.size();
+  g_lean_reason = 0;
+  const int r1 = handoff ? knn_search_f32_round1<KM, false, KnnSameQuery, 3>(G.g, G.cell_start.data(), G.sp.data(), G.rel.data(), plane, q, k, max_dist,
+                                                                             pass_max, pos, rows, 1, KnnSameQuery(), &word)
+                         : knn_search_f32_round1<KM>(G.g, G.cell_start.data(), G.sp.data(), G.rel.data(), plane, q, k, max_dist, pass_max, pos, rows, 1);
+  out[0] = r1 >= 0 ? 0u : (r1 == -2 ? 2u : (r1 == -3 ? 3u : 1u));
+  out[1] = out[2] = out[3] = 0u;
+  if (r1 == -1) out[0] |= g_lean_reason << 8;
+  if (r1 >= 0) {
+    if (word != 0u) {  // the fit's side (fit_one): the neighbours gathered from the positions, the selection verified on them
+      const int shift = KM - (k < KM ? k : KM);
+      GridPoint nb[KM];
+      for (int j = 0; j < KM; j++) {
+        const uint32_t at = shift + j < KM ? pos[shift + j] : 0u;
+        nb[j] = G.sp[at < plane ? at : 0u];
+      }
+      out[0] |= 1u << 16;
+      if (knn_handoff_verify<KM>(word, q, nb, k, pass_max, knn_f32_err_unit(G.g)) < 0) out[0] |= 1u << 17;
+      const int count = (int)(word & kNnCountMask);
+      auto d2 = [&](const GridPoint& t) { const double dx = q.x - t.x, dy = q.y - t.y, dz = q.z - t.z; return dx * dx + dy * dy + dz * dz; };
+      std::stable_sort(nb, nb + (count < KM ? count : KM), [&](const GridPoint& a, const GridPoint& b) { return d2(a) < d2(b); });
+      if (knn_handoff_verify<KM>(word, q, nb, k, pass_max, knn_f32_err_unit(G.g)) < 0) out[0] |= 1u << 18;
+    }
+    return;
+  }
+  if (G.g.n_points <= kLeanMaxPoints)
+    out[1] = (uint32_t)(4 + knn_lean_round2<KM>(G.g, G.cell_start.data(), G.sp.data(), G.rel.data(), plane, q, k, max_dist, pass_max, pos, rows, 1));
+  out[2] = (uint32_t)(4 + knn_search_f32_round1<KM, true>(G.g, G.cell_start.data(), G.sp.data(), G.rel.data(), plane, q, k, max_dist, pass_max, pos, rows, 1));
+  out[3] = (uint32_t)(4 + knn_search_keyed<KM>(G.g, G.cell_start.data(), G.sp.data(), q, k, max_dist, pass_max, pos, rows, 1));
+}
+}
+// desc = {ox, oy, oz, h}, dims = {nx, ny, nz} of the grid the routes were taken on
+void hostcheck_knn_routes(const double* pts, uint64_t n, const double* queries, uint64_t nq, uint64_t k, double max_dist, int handoff,
+                          uint32_t* out, double desc[4], int32_t dims[3]) {
+  HostGrid G;
+  build_grid(pts, (uint32_t)n, max_dist, G);
+  desc[0] = G.g.ox, desc[1] = G.g.oy, desc[2] = G.g.oz, desc[3] = G.g.h;
+  dims[0] = G.g.nx, dims[1] = G.g.ny, dims[2] = G.g.nz;
+  for (uint64_t i = 0; i < nq; i++) {
+    const Vec3 q = v3(queries[3 * i], queries[3 * i + 1], queries[3 * i + 2]);
+    if (k <= 5) knn_route<5>(G, q, (int)k, max_dist, handoff != 0, out + 4 * i);
+    else if (k <= 8) knn_route<8>(G, q, (int)k, max_dist, false, out + 4 * i);
+    else knn_route<16>(G, q, (int)k, max_dist, false, out + 4 * i);
+  }
+}
+
 // the target grid the kernels choose for a set (grid_choose over its bounding box, the scan-pair cell cap):
 // out = {h, nx, ny, nz}
 void hostcheck_grid_choose(const double* pts, uint64_t n, double max_dist, double out[4]) {

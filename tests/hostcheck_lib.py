@@ -144,6 +144,24 @@ def grid_choose(pts, max_dist):
     return float(out[0]), (int(out[1]), int(out[2]), int(out[3]))
 
 
+def knn_routes(pts, queries, k, max_dist, handoff=False):
+    """every query's route through the association's k-NN queue chain, piece by piece (hostcheck.cpp: hostcheck_knn_routes):
+    dict(r1 (0 finished, 1 queued plain, 2 wide, 3 tied), reason, unverified, refused, refused_any_order, lean2, wide, keyed (the pieces' returns;
+    -99 where a piece did not apply), origin, h, dims)"""
+    pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+    q = np.ascontiguousarray(queries, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros((max(1, len(q)), 4), dtype=np.uint32)
+    desc, dims = np.empty(4), np.zeros(3, dtype=np.int32)
+    lib().hostcheck_knn_routes(_dp(pts), C.c_uint64(len(pts)), _dp(q), C.c_uint64(len(q)), C.c_uint64(k), C.c_double(max_dist),
+                               C.c_int(1 if handoff else 0), out.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(desc),
+                               dims.ctypes.data_as(C.POINTER(C.c_int32)))
+    out = out[:len(q)].astype(np.int64)
+    piece = lambda col: np.where(out[:, col] == 0, -99, out[:, col] - 4)
+    return dict(r1=out[:, 0] & 0xFF, reason=out[:, 0] >> 8 & 0xFF, unverified=(out[:, 0] >> 16 & 1).astype(bool),
+                refused=(out[:, 0] >> 17 & 1).astype(bool), refused_any_order=(out[:, 0] >> 18 & 1).astype(bool), lean2=piece(1), wide=piece(2), keyed=piece(3),
+                origin=desc[:3].copy(), h=float(desc[3]), dims=tuple(int(d) for d in dims))
+
+
 def grid_choose_cap(pts, max_dist, cells_cap=65536):
     """grid_choose over the exact bounding box of `pts` with the cell cap as an argument -> (h, (nx, ny, nz))"""
     pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)

@@ -258,10 +258,18 @@ def test_cooperative_leftover_search_on_the_queries_it_exists_for(oracle, case):
         reg.max_plane_neighbor_dist = oreg.max_plane_neighbor_dist = radius
         with option("QUEUE_TWO_STAGE"):
             dump = ctx().associate(none, src_p, none, tgt_p, IDENT, reg)
+            cen = ctx().last_assoc_census("plane")
             with option("NO_COOP_LEFT"):
                 lanes = ctx().associate(none, src_p, none, tgt_p, IDENT, reg)
+                cen_lanes = ctx().last_assoc_census("plane")
         queued, listed = dump["plane"]["queued"]
         assert queued > 20 and listed > 5, (case, k, queued, listed)  # (the leftover kernel really had work)
+        # ... and it was the kernel meant (the census): the cooperative one, but the one-lane kernel where there is no
+        # radius (the launcher does not start the cooperative kernel for such a search at all), and finished what was listed
+        want = capi.ASSOC_LEFTOVER_COOP if radius > 0 else capi.ASSOC_LEFTOVER_LEFT
+        assert (cen.leftover_kernel, cen.one_stage, cen.queued, cen.listed) == (want, 0, queued, listed), (case, k, cen)
+        assert cen.leftover_finished + cen.exact == listed
+        assert (cen_lanes.leftover_kernel, cen_lanes.one_stage) == (capi.ASSOC_LEFTOVER_LEFT, 0)
         check_kind(oracle, f"plane coop-{case}-{k}", dump, src_p, tgt_p, IDENT, True, oreg, ties=(case == "mixed"))
         assert all(np.array_equal(a, b) for a, b in zip(dump["plane"]["nn"], lanes["plane"]["nn"])) or case == "mixed"
         assert np.array_equal(dump["plane"]["valid"], lanes["plane"]["valid"])
