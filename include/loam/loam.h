@@ -5,4 +5,5 @@
 #include "geometry.h"
 #include "kdtree.h"
 #include "organize.h"
+#include "place.h"
 #include "registration.h"

@@ -707,6 +707,91 @@ int loamx_organize_cloud(loamx_ctx* ctx, const loamx_scan_layout* layout, const 
 int loamx_organize_cloud_f32(loamx_ctx* ctx, const loamx_scan_layout* layout, const float* points, size_t point_stride,
                              const uint16_t* rings, size_t n_points, float* scan, uint32_t* src_idx, uint32_t* stats);
 
+/* ---- place recognition (no reference counterpart: SURVEY 2 negatives). A mapper notices that it has been somewhere before by
+ * comparing a descriptor of the current scan with the descriptors of earlier scans: here the Scan Context form, a polar grid of
+ * maximum heights with a rotation-invariant ring key as pre-filter, compared under every column shift; the best shift is a yaw
+ * guess for the registration that makes the loop edge. Everything below is integer or individually rounded FP64, the device
+ * uses no libm beyond sqrt and floor, and nothing depends on thread scheduling: a model can be compared by equality of bytes.
+ *
+ * Parameters: R = n_rings, S = n_sectors, L = max_range, z_offset, z_scale. ring_scale = R / L is formed once on the host in
+ * double. The S sector boundaries are those of a scan layout of S columns with azimuth_zero 0, counter-clockwise: sector c is
+ * centred on the azimuth 2 pi c / S. The table is computed on the host, kept on the device, and handed out byte for byte.
+ * Per point p = (x, y, z) in the sensor frame (float input is widened first; every product and sum is rounded on its own):
+ *   1. validity as in "unordered clouds into scans", step 1: dropped if a coordinate or r2 is not finite or !(rho2 >= 1e-100),
+ *      which includes the all-zero cell of an organised scan.
+ *   2. ring: rho = sqrt(rho2), f = rho ring_scale; dropped if !(f < R), else ring = floor(f).
+ *   3. sector: the column of "unordered clouds into scans", step 2, on the table of S boundaries.
+ *   4. code: h = floor((z + z_offset) z_scale) clamped to [0, 65534], code = h + 1 (1 .. 65535; 0 means no point).
+ * Descriptor: R x S uint16, row-major [ring][sector], the maximum code of each cell; an empty cloud gives all zeros.
+ *   ring key     R x uint32: the sum of each ring's codes.
+ *   column norm  S x uint64: the sum of the squared codes of each sector.
+ * Key distance of a query and an entry: sum_r (key_q[r] - key_e[r])^2, exact in uint64 (< 2^63).
+ * Distance under shift s in [0, S): for sector j, column q[:, j] against e[:, (j + s) mod S]:
+ *   dot_j  exact in uint64. The pair of columns counts when both norms are non-zero; m = the number of such pairs.
+ *   c_j    = (double) dot_j / sqrt((double) nq_j (double) ne_j'), each operation rounded on its own. (The product comes
+ *            before the root so that a column against itself has c_j = 1.0 exactly: sqrt(fl(n n)) = n for an integer
+ *            n < 2^53, while sqrt(n) sqrt(n) misses n for most n. A descriptor against a rolled copy has distance 0.0.)
+ *   k_j    = min((uint64) floor(c_j 2^30), 2^30)
+ *   score  = sum_j k_j;  dist = 1.0 - (double) score / ((double) m 2^30), or 1.0 when m == 0
+ * The distance of the pair is the smallest dist over s; on a tie the lowest s. s is the number of sectors the query sensor is
+ * turned counter-clockwise (seen from +z) relative to the entry's: a rotation about z by s 2 pi / S is the entry_T_query guess.
+ * Search of one query with K = num_candidates and id_end: among the entries with id < id_end the K smallest by (key distance,
+ * id) — exhaustively — get their shift distance over all S shifts; the K records come back ascending by (distance, id), the
+ * slots beyond the number of eligible entries as {0xFFFFFFFF, 0, 2^64 - 1, 2.0}. */
+typedef struct {
+  uint32_t n_rings;   /* 20 */
+  uint32_t n_sectors; /* 60 */
+  double max_range;   /* 80.0 */
+  double z_offset;    /* 2.0: sensor height above ground; makes heights positive */
+  double z_scale;     /* 64.0: codes per metre; a power of two keeps the product exact */
+} loamx_place_params;
+void loamx_default_place_params(loamx_place_params* p);
+typedef struct {
+  uint32_t id;       /* the entry, or 0xFFFFFFFF */
+  uint32_t shift;    /* sectors the query is turned counter-clockwise relative to the entry */
+  uint64_t key_dist; /* squared ring-key distance */
+  double distance;   /* 0 .. 1; 2.0 without an entry */
+} loamx_place_match;
+typedef struct loamx_place_db loamx_place_db;
+/* The database owns the parameters, the sector table and the stored entries (descriptor, ring key, column norms per entry; ids
+ * are consecutive from 0, at most 2^24). LOAMX_ERR_BAD_PARAM: a null argument, n_rings or n_sectors 0, a non-finite or
+ * non-positive max_range or z_scale, a non-finite z_offset. LOAMX_ERR_UNSUPPORTED: n_rings > 64, n_sectors < 3 (the column has
+ * no unique answer at two boundaries or fewer) or > 360. */
+int loamx_place_db_create(loamx_ctx* ctx, const loamx_place_params* params, loamx_place_db** out);
+void loamx_place_db_destroy(loamx_ctx* ctx, loamx_place_db* db);
+/* dirs[S][2]: the sector table exactly as the kernels use it (a host copy of the uploaded bytes) */
+int loamx_place_db_sector_dirs(const loamx_place_db* db, double* dirs);
+int loamx_place_db_size(const loamx_place_db* db, size_t* n_entries);
+/* n_clouds clouds stored back to back -> n_clouds descriptors of R S uint16 in d_desc; d_points, point_stride and cloud_offsets
+ * (HOST, n_clouds + 1) as for loamx_organize_clouds_dev: an organised scan is a cloud of H W points. Every entry of d_desc is
+ * written. Asynchronous on the context's stream; no synchronisation unless the workspace has to grow. The database is not
+ * changed. LOAMX_ERR_BAD_PARAM: a null db, d_points (with points), cloud_offsets or d_desc, point_stride < 3, descending
+ * offsets; LOAMX_ERR_UNSUPPORTED: a cloud of more than 2^32 - 2 points. A refused call writes nothing. n_clouds == 0: LOAMX_OK. */
+int loamx_place_descriptors_dev(loamx_ctx* ctx, const loamx_place_db* db, const double* d_points, size_t point_stride,
+                                const size_t* cloud_offsets, size_t n_clouds, uint16_t* d_desc);
+int loamx_place_descriptors_dev_f32(loamx_ctx* ctx, const loamx_place_db* db, const float* d_points, size_t point_stride,
+                                    const size_t* cloud_offsets, size_t n_clouds, uint16_t* d_desc);
+/* Appends n descriptors (device) as the entries *first_id .. *first_id + n - 1 (first_id may be NULL) and derives their keys
+ * and norms. Asynchronous unless the database has to grow. LOAMX_ERR_UNSUPPORTED beyond 2^24 entries; a refused call leaves
+ * the database as it was. n == 0: LOAMX_OK. */
+int loamx_place_db_add_dev(loamx_ctx* ctx, loamx_place_db* db, const uint16_t* d_desc, size_t n, uint32_t* first_id);
+/* Host read-back of the entries first .. first + count - 1: desc[count][R S], keys[count][R], norms[count][S]; any may be NULL.
+ * Synchronises. LOAMX_ERR_BAD_PARAM beyond the database's size. */
+int loamx_place_db_read(loamx_ctx* ctx, const loamx_place_db* db, size_t first, size_t count, uint16_t* desc, uint32_t* keys,
+                        uint64_t* norms);
+/* n_queries descriptors (device) -> n_queries x num_candidates records in d_out, every one written. id_end: HOST array of
+ * n_queries values (read before the call returns), or NULL: every entry. Asynchronous unless the workspace has to grow.
+ * LOAMX_ERR_BAD_PARAM: a null db, d_query_desc or d_out, num_candidates outside 1 .. 64. n_queries == 0: LOAMX_OK. */
+int loamx_place_search_dev(loamx_ctx* ctx, const loamx_place_db* db, const uint16_t* d_query_desc, size_t n_queries,
+                           const uint32_t* id_end, uint32_t num_candidates, loamx_place_match* d_out);
+/* Host memory in, host memory out, synchronous: one cloud -> its descriptor; n_queries descriptors -> their records. */
+int loamx_place_descriptor(loamx_ctx* ctx, const loamx_place_db* db, const double* points, size_t point_stride, size_t n_points,
+                           uint16_t* desc);
+int loamx_place_descriptor_f32(loamx_ctx* ctx, const loamx_place_db* db, const float* points, size_t point_stride,
+                               size_t n_points, uint16_t* desc);
+int loamx_place_search(loamx_ctx* ctx, const loamx_place_db* db, const uint16_t* query_desc, size_t n_queries,
+                       const uint32_t* id_end, uint32_t num_candidates, loamx_place_match* out);
+
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are
  * independent units). One process per GPU owns a contiguous block of pair ids and runs the single-GPU entry points

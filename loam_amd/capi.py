@@ -176,6 +176,37 @@ class OrganizeParams:
                                     0 if self.ring_map is None else self.ring_map.size)
 
 
+class PlaceParamsStruct(C.Structure):
+    """loamx_place_params (include/loamx.h)"""
+    _fields_ = [("n_rings", C.c_uint32), ("n_sectors", C.c_uint32), ("max_range", C.c_double), ("z_offset", C.c_double),
+                ("z_scale", C.c_double)]
+
+
+class PlaceParams:
+    """The shape and scaling of a scan descriptor (loamx_place_params): n_rings x n_sectors cells out to max_range, heights
+    counted from z_offset below the sensor in steps of 1 / z_scale. Anything left out takes the C ABI's default."""
+
+    def __init__(self, n_rings=None, n_sectors=None, max_range=None, z_offset=None, z_scale=None):
+        d = PlaceParamsStruct()
+        load().loamx_default_place_params(C.byref(d))
+        self.n_rings = d.n_rings if n_rings is None else int(n_rings)
+        self.n_sectors = d.n_sectors if n_sectors is None else int(n_sectors)
+        self.max_range = d.max_range if max_range is None else float(max_range)
+        self.z_offset = d.z_offset if z_offset is None else float(z_offset)
+        self.z_scale = d.z_scale if z_scale is None else float(z_scale)
+
+    def struct(self):
+        for name in ("n_rings", "n_sectors"):
+            if not 0 <= getattr(self, name) <= 0xFFFFFFFF:
+                raise ValueError(f"PlaceParams: {name} does not fit 32 bits")
+        return PlaceParamsStruct(self.n_rings, self.n_sectors, self.max_range, self.z_offset, self.z_scale)
+
+
+# loamx_place_match: one record of a search
+PLACE_MATCH_DTYPE = np.dtype([("id", np.uint32), ("shift", np.uint32), ("key_dist", np.uint64), ("distance", np.float64)])
+PLACE_NO_ID = 0xFFFFFFFF  # id of a record without an entry (fewer eligible entries than candidates asked for)
+
+
 EXPORTS = [
     "loamx_default_fe_params", "loamx_default_reg_params", "loamx_status_string", "loamx_last_error",
     "loamx_ctx_create", "loamx_ctx_destroy", "loamx_ctx_set_stream", "loamx_ctx_synchronize",
@@ -204,6 +235,9 @@ EXPORTS = [
     "loamx_register_scan_sequence_info_dev_f32",
     "loamx_default_organize_params", "loamx_scan_layout_create", "loamx_scan_layout_destroy", "loamx_scan_layout_tables",
     "loamx_organize_clouds_dev", "loamx_organize_clouds_dev_f32", "loamx_organize_cloud", "loamx_organize_cloud_f32",
+    "loamx_default_place_params", "loamx_place_db_create", "loamx_place_db_destroy", "loamx_place_db_sector_dirs", "loamx_place_db_size",
+    "loamx_place_descriptors_dev", "loamx_place_descriptors_dev_f32", "loamx_place_db_add_dev", "loamx_place_db_read",
+    "loamx_place_search_dev", "loamx_place_descriptor", "loamx_place_descriptor_f32", "loamx_place_search",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -427,6 +461,21 @@ def load(build_if_missing=True):
     lib.loamx_organize_clouds_dev_f32.argtypes = lib.loamx_organize_clouds_dev.argtypes
     lib.loamx_organize_cloud.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
     lib.loamx_organize_cloud_f32.argtypes = lib.loamx_organize_cloud.argtypes
+    lib.loamx_default_place_params.argtypes = [C.POINTER(PlaceParamsStruct)]
+    lib.loamx_default_place_params.restype = None
+    lib.loamx_place_db_create.argtypes = [vp, C.POINTER(PlaceParamsStruct), C.POINTER(vp)]
+    lib.loamx_place_db_destroy.argtypes = [vp, vp]
+    lib.loamx_place_db_destroy.restype = None
+    lib.loamx_place_db_sector_dirs.argtypes = [vp, dp]
+    lib.loamx_place_db_size.argtypes = [vp, szp]
+    lib.loamx_place_descriptors_dev.argtypes = [vp, vp, vp, C.c_size_t, szp, C.c_size_t, vp]
+    lib.loamx_place_descriptors_dev_f32.argtypes = lib.loamx_place_descriptors_dev.argtypes
+    lib.loamx_place_db_add_dev.argtypes = [vp, vp, vp, C.c_size_t, u32p]
+    lib.loamx_place_db_read.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp]
+    lib.loamx_place_search_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_uint32, vp]
+    lib.loamx_place_descriptor.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
+    lib.loamx_place_descriptor_f32.argtypes = lib.loamx_place_descriptor.argtypes
+    lib.loamx_place_search.argtypes = lib.loamx_place_search_dev.argtypes
     _lib = lib
     return lib
 
@@ -568,6 +617,142 @@ class ScanLayout:
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):
                 self.ctx.lib.loamx_scan_layout_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _offsets(cloud_offsets, who):
+    off = np.ascontiguousarray(cloud_offsets)
+    if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu":
+        raise ValueError(who + ": cloud_offsets is a 1-d integer array of n_clouds + 1 offsets")
+    if off.dtype.kind == "i" and (off < 0).any():
+        raise ValueError(who + ": negative offset")
+    return off.astype(np.uint64)
+
+
+class PlaceDb:
+    """A place-recognition database (loamx_place_db; include/loamx.h, "place recognition"): the parameters, the table of sector
+    boundaries and the stored descriptors with their ring keys and column norms, on the context's device. Descriptors are
+    (n_rings, n_sectors) uint16 arrays. close() frees it; the context must still be open."""
+
+    def __init__(self, ctx, params=None):
+        self.ctx, self.params = ctx, params or PlaceParams()
+        st = self.params.struct()
+        h = C.c_void_p()
+        ctx._check(ctx.lib.loamx_place_db_create(ctx.h, C.byref(st), C.byref(h)))
+        self.h = h
+        self.n_rings, self.n_sectors = self.params.n_rings, self.params.n_sectors
+
+    @property
+    def cells(self):
+        return self.n_rings * self.n_sectors
+
+    def _handle(self):
+        if not getattr(self, "h", None):
+            raise ValueError("the place database is closed")
+        return self.h
+
+    def sector_dirs(self):
+        """(n_sectors, 2): the sector boundaries as the kernels read them (loamx_place_db_sector_dirs)"""
+        d = np.empty((self.n_sectors, 2))
+        self.ctx._check(self.ctx.lib.loamx_place_db_sector_dirs(self._handle(), _dp(d)))
+        return d
+
+    def size(self):
+        n = C.c_size_t(0)
+        self.ctx._check(self.ctx.lib.loamx_place_db_size(self._handle(), C.byref(n)))
+        return n.value
+
+    def descriptors_dev(self, d_points, point_stride, cloud_offsets, d_desc, f32=False):
+        """len(cloud_offsets) - 1 device-resident clouds back to back -> as many descriptors at the device address d_desc
+        (loamx_place_descriptors_dev[_f32]). Asynchronous on the context's stream."""
+        off = _offsets(cloud_offsets, "descriptors_dev")
+        fn = self.ctx.lib.loamx_place_descriptors_dev_f32 if f32 else self.ctx.lib.loamx_place_descriptors_dev
+        self.ctx._check(fn(self.ctx.h, self._handle(), d_points or None, int(point_stride), off.ctypes.data_as(C.POINTER(C.c_size_t)),
+                           off.size - 1, d_desc or None))
+
+    def descriptor(self, points):
+        """One cloud (or organised scan) in host memory, (n, k >= 3) float64 / float32 -> its (n_rings, n_sectors) uint16 descriptor."""
+        pts = np.asarray(points)
+        if pts.dtype != np.float32:
+            pts = np.asarray(pts, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] < 3:
+            raise ValueError(f"descriptor: points must be (n, 3) or (n, k >= 3), not {pts.shape}")
+        pts = np.ascontiguousarray(pts)
+        desc = np.empty((self.n_rings, self.n_sectors), dtype=np.uint16)
+        fn = self.ctx.lib.loamx_place_descriptor_f32 if pts.dtype == np.float32 else self.ctx.lib.loamx_place_descriptor
+        self.ctx._check(fn(self.ctx.h, self._handle(), pts.ctypes.data, pts.shape[1], pts.shape[0], desc.ctypes.data))
+        return desc
+
+    def _descs(self, desc, who):
+        d = np.ascontiguousarray(desc, dtype=np.uint16)
+        if d.size % self.cells or (d.ndim >= 2 and d.shape[-2:] != (self.n_rings, self.n_sectors) and d.shape[-1] != self.cells):
+            raise ValueError(f"{who}: descriptors are (n, {self.n_rings}, {self.n_sectors}) uint16, not {d.shape}")
+        return d.reshape(-1, self.n_rings, self.n_sectors)
+
+    def add_dev(self, d_desc, n):
+        """appends n descriptors at the device address d_desc; returns the id of the first (loamx_place_db_add_dev)"""
+        first = C.c_uint32(0)
+        self.ctx._check(self.ctx.lib.loamx_place_db_add_dev(self.ctx.h, self._handle(), d_desc or None, int(n), C.byref(first)))
+        return first.value
+
+    def add(self, desc):
+        """appends host descriptors, (n_rings, n_sectors) or (n, n_rings, n_sectors); returns the id of the first"""
+        d = self._descs(desc, "add")
+        if len(d) == 0:
+            return self.add_dev(0, 0)
+        buf = self.ctx.alloc(d.nbytes)
+        try:
+            buf.upload(d)
+            first = self.add_dev(buf.ptr, len(d))
+            self.ctx.synchronize()
+            return first
+        finally:
+            buf.free()
+
+    def read(self, first=0, count=None):
+        """(descriptors (count, R, S) uint16, ring keys (count, R) uint32, column norms (count, S) uint64) of stored entries"""
+        count = self.size() - first if count is None else count
+        desc = np.empty((count, self.n_rings, self.n_sectors), dtype=np.uint16)
+        keys, norms = np.empty((count, self.n_rings), dtype=np.uint32), np.empty((count, self.n_sectors), dtype=np.uint64)
+        self.ctx._check(self.ctx.lib.loamx_place_db_read(self.ctx.h, self._handle(), first, count, desc.ctypes.data, keys.ctypes.data,
+                                                         norms.ctypes.data))
+        return desc, keys, norms
+
+    @staticmethod
+    def _id_end(id_end, n_queries):
+        if id_end is None:
+            return None
+        e = np.ascontiguousarray(np.broadcast_to(np.asarray(id_end), (n_queries,)))
+        if e.dtype.kind not in "iu" or (e.size and (e.min() < 0 or e.max() > 0xFFFFFFFF)):
+            raise ValueError("search: id_end holds integers in 0 .. 2^32 - 1")
+        return e.astype(np.uint32)
+
+    def search_dev(self, d_query_desc, n_queries, num_candidates, d_out, id_end=None):
+        """n_queries descriptors at the device address d_query_desc -> n_queries x num_candidates PLACE_MATCH_DTYPE records at
+        d_out (loamx_place_search_dev). id_end: None, one integer or one per query (host). Asynchronous."""
+        e = self._id_end(id_end, n_queries)
+        self.ctx._check(self.ctx.lib.loamx_place_search_dev(self.ctx.h, self._handle(), d_query_desc or None, int(n_queries),
+                                                            e.ctypes.data if e is not None else None, int(num_candidates), d_out or None))
+
+    def search(self, desc, num_candidates, id_end=None):
+        """host descriptors (R, S) or (n, R, S) -> (n, num_candidates) PLACE_MATCH_DTYPE records, ascending by (distance, id)"""
+        d = self._descs(desc, "search")
+        e = self._id_end(id_end, len(d))
+        out = np.empty((len(d), int(num_candidates)), dtype=PLACE_MATCH_DTYPE)
+        self.ctx._check(self.ctx.lib.loamx_place_search(self.ctx.h, self._handle(), d.ctypes.data, len(d),
+                                                        e.ctypes.data if e is not None else None, int(num_candidates), out.ctypes.data))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.ctx.lib.loamx_place_db_destroy(self.ctx.h, self.h)
             self.h = None
 
     def __del__(self):
@@ -1147,6 +1332,10 @@ class Context:
         self._check(fn(self.h, layout._handle(), pts.ctypes.data, stride, r.ctypes.data if r is not None else None, n, scan.ctypes.data,
                        src.ctypes.data, stats.ctypes.data))
         return scan, src, stats
+
+    # ---- place recognition (include/loamx.h, "place recognition") --------------------------------------------
+    def place_db(self, params=None):
+        return PlaceDb(self, params)
 
     def synth_scan_pairs_dev(self, seed, first_pair, n_pairs, scan_lines, points_per_line, sigma, d_xyz):
         self._check(self.lib.loamx_synth_scan_pairs_dev(self.h, seed, first_pair, n_pairs, scan_lines,

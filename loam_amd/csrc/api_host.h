@@ -24,6 +24,7 @@ enum WsId {
   WS_FIT_IN, WS_FIT_OUT, WS_FCOUNTS, WS_RESULTS, WS_INIT, WS_STREAM_INIT,
   WS_VOX_TABLE, WS_MAP_WORDS, WS_INFO_PARTIALS, WS_INFO, WS_LIVE,
   WS_ORG_WINNER, WS_ORG_RANGE, WS_ORG_CELL, WS_ORG_COUNTS, WS_ORG_IN, WS_ORG_RINGS, WS_ORG_OUT,
+  WS_PLACE_TABLE, WS_PLACE_QKEYS, WS_PLACE_QNORMS, WS_PLACE_CAND_A, WS_PLACE_CAND_B, WS_PLACE_MATCH, WS_PLACE_IN, WS_PLACE_OUT,
   WS_COUNT
 };
 // the buffers that exist once per feature kind: loamx_ctx::wsk[id][kEdge | kPlane]

@@ -9,6 +9,7 @@
 #include "extract_math.h"
 #include "reg_math.h"
 #include "organize_math.h"
+#include "place_math.h"
 #include "xcd_map.h"
 
 namespace loamx {
@@ -418,6 +419,47 @@ enum { kOrgFilled = 0, kOrgInvalid = 1, kOrgOutside = 2, kOrgCounterWords = 4 };
 void launch_organize(const void* d_points, bool f32, uint32_t stride, const uint16_t* d_rings, const OrgOffsets& offs, uint32_t n_clouds,
                      unsigned long long max_points, const OrgTables& L, bool nearest, uint32_t* winner, unsigned long long* range,
                      uint32_t* cell, uint32_t* counters, void* d_scans, uint32_t* d_src_idx, uint32_t* d_stats, hipStream_t s);
+
+/* ---- place recognition (place_kernels.hip; the rule: place_math.h and loamx.h) ---------------------------------------------- */
+constexpr uint32_t kPlaceSelectChunk = 1024;  // records a workgroup of the selection ranks at once
+// one candidate of the key stage: squared key distance and entry id (kPlaceNoKeyDist / kPlaceNoId: none)
+struct PlaceCand {
+  unsigned long long dist;
+  uint32_t id, pad;
+};
+// the stored entries of a database as the kernels read them
+struct PlaceEntries {
+  const uint16_t* desc;             // [n][R S]
+  const uint32_t* keys;             // [n][R]
+  const unsigned long long* norms;  // [n][S]
+  uint32_t n;
+};
+// One chunk of at most kOrgChunkClouds clouds, max_points = its largest cloud. table: n_clouds x R S zeroed words;
+// d_desc: the chunk's share of the output.
+void launch_place_descriptors(const void* d_points, bool f32, uint32_t stride, const OrgOffsets& offs, uint32_t n_clouds,
+                              unsigned long long max_points, const PlaceShape& P, const double* d_dirs, uint32_t* table, uint16_t* d_desc,
+                              hipStream_t s);
+// ring keys [n][R] and column norms [n][S] of n descriptors
+void launch_place_keys(const uint16_t* d_desc, size_t n, const PlaceShape& P, uint32_t* d_keys, unsigned long long* d_norms, hipStream_t s);
+// chunks of the key stage's first pass over n_entries entries (>= 1) and the records its passes leave per query in each of the
+// two buffers at most
+uint32_t place_select_chunks(uint32_t n_entries);
+size_t place_select_records(uint32_t n_entries, uint32_t K);
+// the id_end of the queries of one launch: they travel as a kernel argument like OrgOffsets (no staging copy of a host array)
+constexpr uint32_t kPlaceIdEndQueries = 256;
+struct PlaceIdEnd {
+  uint32_t v[kPlaceIdEndQueries];
+  uint32_t given;
+};
+// The K entries nearest by (key distance, id) among those with id < min(E.n, id_end[q]) for n_queries queries (id_end: HOST
+// array or nullptr; with one, n_queries <= kPlaceIdEndQueries); the result, ascending, stands in the buffer the function
+// returns (one of the two given).
+PlaceCand* launch_place_key_stage(const PlaceEntries& E, const PlaceShape& P, const uint32_t* d_qkeys, const uint32_t* id_end, uint32_t n_queries,
+                                  uint32_t K, PlaceCand* buf_a, PlaceCand* buf_b, hipStream_t s);
+// the shift distance of every candidate, then the records of each query ascending by (distance, id) in d_out
+void launch_place_shift_stage(const PlaceEntries& E, const PlaceShape& P, const uint16_t* d_qdesc, const unsigned long long* d_qnorms,
+                              const PlaceCand* cands, uint32_t n_queries, uint32_t K, loamx_place_match* d_tmp, loamx_place_match* d_out,
+                              hipStream_t s);
 
 /* ---- map upkeep (map_kernels.hip): voxel filter against an occupancy table, crop, the stable compaction they share --- */
 constexpr uint32_t kMapTile = 256;             // points per tile of the compaction (one workgroup)

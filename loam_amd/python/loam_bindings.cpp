@@ -5,7 +5,8 @@
 // registerFeatures — with the same keyword arguments; plus extensions the reference does not have: registerScanSequence
 // and deskewScan (include/loamx.h: "scan sequences"), and the class TargetIndex with a registerFeatures overload that
 // takes it (scan-to-map: "persistent target index" and "map upkeep"), and OrganizeParams / ScanLayout / organizeCloud, the way
-// in for clouds that are not organised scans yet ("unordered clouds into scans"). Point clouds are contiguous (N,3) float64
+// in for clouds that are not organised scans yet ("unordered clouds into scans"), and PlaceParams / PlaceMatch / PlaceDatabase
+// ("place recognition"). Point clouds are contiguous (N,3) float64
 // arrays handed to the C ABI without per-point objects (a list of 3-vectors is converted once).
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -95,6 +96,30 @@ inline int c_organize(loamx_ctx* c, const loamx_scan_layout* l, const float* p, 
   return loamx_organize_cloud_f32(c, l, p, stride, r, n, s, i, st);
 }
 using ArrRings = py::array_t<uint16_t, py::array::c_style | py::array::forcecast>;
+
+// PlaceDatabase: descriptors are (n_rings, n_sectors) uint16 arrays; points as for organizeCloud
+using ArrDesc = py::array_t<uint16_t, py::array::c_style | py::array::forcecast>;
+inline int c_place_descriptor(loamx_ctx* c, const loamx_place_db* d, const double* p, size_t stride, size_t n, uint16_t* out) {
+  return loamx_place_descriptor(c, d, p, stride, n, out);
+}
+inline int c_place_descriptor(loamx_ctx* c, const loamx_place_db* d, const float* p, size_t stride, size_t n, uint16_t* out) {
+  return loamx_place_descriptor_f32(c, d, p, stride, n, out);
+}
+template <typename T>
+py::array_t<uint16_t> place_descriptor(const loam::PlaceDatabase& db, const py::array_t<T, py::array::c_style>& points) {
+  if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
+  py::array_t<uint16_t> desc({(py::ssize_t)db.params().n_rings, (py::ssize_t)db.params().n_sectors});
+  loamx_ctx* ctx = loam::gpu::defaultContext();
+  {
+    py::gil_scoped_release release;
+    loam::gpu::check(ctx, c_place_descriptor(ctx, db.handle(), points.data(), (size_t)points.shape(1), (size_t)points.shape(0), desc.mutable_data()));
+  }
+  return desc;
+}
+inline loam::PlaceDescriptor place_desc_arg(const loam::PlaceDatabase& db, const ArrDesc& desc) {
+  if ((size_t)desc.size() != db.cells()) throw std::runtime_error("descriptor: expected an (n_rings, n_sectors) uint16 array");
+  return loam::PlaceDescriptor(desc.data(), desc.data() + desc.size());
+}
 template <typename T>
 py::tuple organize_cloud(const py::array_t<T, py::array::c_style>& points, const loam::ScanLayout& layout, const std::optional<ArrRings>& rings) {
   if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
@@ -485,6 +510,37 @@ PYBIND11_MODULE(loam_python, m) {
       .def("lineTangents", [](const loam::ScanLayout& l) { return matrix_to_array(l.lineTangents().data(), l.scanLines() + 1, 1); });
   m.def("organizeCloud", &organize_cloud<float>, py::arg("points"), py::arg("layout"), py::arg("rings") = py::none());
   m.def("organizeCloud", &organize_cloud<double>, py::arg("points"), py::arg("layout"), py::arg("rings") = py::none());
+  // place recognition (include/loamx.h: "place recognition"): an extension like TargetIndex
+  py::class_<loam::PlaceParams>(m, "PlaceParams")
+      .def(py::init<>())
+      .def_readwrite("n_rings", &loam::PlaceParams::n_rings)
+      .def_readwrite("n_sectors", &loam::PlaceParams::n_sectors)
+      .def_readwrite("max_range", &loam::PlaceParams::max_range)
+      .def_readwrite("z_offset", &loam::PlaceParams::z_offset)
+      .def_readwrite("z_scale", &loam::PlaceParams::z_scale);
+  py::class_<loam::PlaceMatch>(m, "PlaceMatch")
+      .def_readonly("id", &loam::PlaceMatch::id)
+      .def_readonly("shift", &loam::PlaceMatch::shift)
+      .def_readonly("key_dist", &loam::PlaceMatch::key_dist)
+      .def_readonly("distance", &loam::PlaceMatch::distance)
+      .def_property_readonly("valid", &loam::PlaceMatch::valid)
+      .def_property_readonly("yaw", &loam::PlaceMatch::yaw)
+      .def("initialGuess", &loam::PlaceMatch::initialGuess);
+  py::class_<loam::PlaceDatabase>(m, "PlaceDatabase")
+      .def(py::init<const loam::PlaceParams&>(), py::arg("params") = loam::PlaceParams())
+      .def_property_readonly("params", &loam::PlaceDatabase::params)
+      .def("size", &loam::PlaceDatabase::size)
+      .def("__len__", &loam::PlaceDatabase::size)
+      .def("sectorDirections", [](const loam::PlaceDatabase& d) { return matrix_to_array(d.sectorDirections().data(), d.params().n_sectors, 2); })
+      .def("descriptor", &place_descriptor<float>, py::arg("points"))
+      .def("descriptor", &place_descriptor<double>, py::arg("points"))
+      .def("add", [](loam::PlaceDatabase& d, const ArrDesc& desc) { return d.add(place_desc_arg(d, desc)); }, py::arg("descriptor"))
+      .def(
+          "search",
+          [](const loam::PlaceDatabase& d, const ArrDesc& query, uint32_t num_candidates, std::optional<uint32_t> id_end) {
+            return d.search(place_desc_arg(d, query), num_candidates, id_end.value_or(0xFFFFFFFFu));
+          },
+          py::arg("query"), py::arg("num_candidates"), py::arg("id_end") = py::none());
   m.def("registerScanSequence", &register_scan_sequence<ArrF>, py::arg("scans"), py::arg("lidar_params"),
         py::arg("fe_params") = loam::FeatureExtractionParams(), py::arg("reg_params") = loam::RegistrationParams(),
         py::arg("inits") = py::none());
