@@ -292,7 +292,11 @@ int loamx_compute_valid_points_f32(loamx_ctx* ctx, const float* xyz, size_t n_po
 int loamx_extract_features_f32(loamx_ctx* ctx, const float* xyz, size_t n_points, const loamx_lidar_params* lidar,
                                const loamx_fe_params* fe, uint32_t* edge_idx, size_t edge_cap, size_t* n_edge,
                                uint32_t* planar_idx, size_t planar_cap, size_t* n_planar);
-/* loam::registerFeatures (registration.h:128-131, registration-inl.h:11-78). detail may be NULL. */
+/* loam::registerFeatures (registration.h:128-131, registration-inl.h:11-78). detail may be NULL.
+ * Every entry point that takes a loamx_reg_params answers LOAMX_ERR_UNSUPPORTED for num_*_neighbors > 16 and for
+ * max_iterations > 1000, and LOAMX_ERR_BAD_PARAM for min_line_fit_points < 2 or min_plane_fit_points < 3 while that kind's
+ * num_*_neighbors is above 0; min_*_fit_points above 64 count as 64 and min_associations above 2^32 - 1 as 2^32 - 1.
+ * max_avg_point_plane_dist is compared with a value that is never positive: the gate acts below 0 only. */
 int loamx_register_features(loamx_ctx* ctx, const double* src_edge, size_t n_src_edge, const double* src_planar,
                             size_t n_src_planar, const double* tgt_edge, size_t n_tgt_edge,
                             const double* tgt_planar, size_t n_tgt_planar, const double init_pose[7],

@@ -5,7 +5,9 @@
 // Built and run by tests/test_gpu_cpp_shim.py (needs a GPU).
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <limits>
 #include <memory>
 #include <vector>
@@ -331,7 +333,84 @@ static void test_internal_namespaces() {
   }
 }
 
-int main() {
+// RegistrationParams through the shim, field by field: thresholds that nothing lies below run to max_iterations, infinite ones
+// stop after the first iteration, and a min_associations one above the scene's 162 + 8941 features ends before anything moved.
+static void test_registration_params() {
+  const Quaterniond q(0.9993921140970299, 0.014692022378442412, 0.030140550562090015, 0.009544316157523478);
+  const LoamFeatures<Vector3d> target = constructSimpleScene();
+  const LoamFeatures<Vector3d> source = transformFeatures(target, Pose3d(q, Vector3d(-0.1, 0.1, 0.0)));
+  const double inf = std::numeric_limits<double>::infinity();
+  auto run = [&](const RegistrationParams& p, const Pose3d& init) {
+    auto detail = std::make_shared<RegistrationDetail>();
+    const Pose3d pose = registerFeatures<ParenAccessor>(source, target, init, p, detail);
+    return std::make_pair(pose, detail);
+  };
+  RegistrationParams zero;
+  zero.rotation_convergence_thresh = 0.0, zero.position_convergence_thresh = 0.0, zero.max_iterations = 2;
+  auto r = run(zero, Pose3d());
+  CHECK(r.second->termination_type == RegistrationDetail::MAX_ITER && r.second->iteration_info.size() == 2);
+  RegistrationParams loose;
+  loose.rotation_convergence_thresh = inf, loose.position_convergence_thresh = inf;
+  r = run(loose, Pose3d());
+  CHECK(r.second->termination_type == RegistrationDetail::CONVERGED && r.second->iteration_info.size() == 1);
+  RegistrationParams many;
+  many.min_associations = 162 + 8941 + 1;
+  const Pose3d init(q.conjugate(), Vector3d(0.05, -0.02, 0.01));
+  r = run(many, init);
+  CHECK(r.second->termination_type == RegistrationDetail::INSUFFICIENT_ASSOCIATIONS && r.second->iteration_info.empty());
+  CHECK(r.first.rotation.w() == init.rotation.w() && r.first.rotation.x() == init.rotation.x());
+  CHECK(r.first.rotation.y() == init.rotation.y() && r.first.rotation.z() == init.rotation.z());
+  for (int i = 0; i < 3; i++) CHECK(r.first.translation(i) == init.translation(i));
+  // exactly as many as associate (TestSimpleCase: all 162 + 8941 at the first iteration) is enough: the first iteration runs
+  many.min_associations = 162 + 8941;
+  auto detail = std::make_shared<RegistrationDetail>();
+  registerFeatures<ParenAccessor>(transformFeatures(target, Pose3d(q, Vector3d(0.01, 0.03, -0.01))), target, Pose3d(), many, detail);
+  CHECK(!detail->iteration_info.empty());
+}
+
+// File mode (tests/test_gpu_reg_params.py): `test_shim <in> <out>` registers the feature sets of <in> under the twelve parameter
+// fields of <in> and writes the pose, the termination type and the association counts of every iteration to <out>.
+// <in>: uint64 n[4] (source edge, source planar, target edge, target planar), the twelve fields in the order and types of
+// RegistrationParams, double init[7] (qx qy qz qw tx ty tz), then the four sets as rows of three doubles.
+// <out>: double pose[7], uint64 termination, uint64 n_iterations, then uint64 n_edge, n_plane per iteration.
+static int file_mode(const char* in_path, const char* out_path) {
+  std::FILE* f = std::fopen(in_path, "rb");
+  if (!f) return 2;
+  uint64_t n[4];
+  unsigned char raw[96];
+  double init[7];
+  bool ok = std::fread(n, sizeof(n), 1, f) == 1 && std::fread(raw, sizeof(raw), 1, f) == 1 && std::fread(init, sizeof(init), 1, f) == 1;
+  auto u64 = [&](int slot) { uint64_t v; std::memcpy(&v, raw + 8 * slot, 8); return (size_t)v; };
+  auto f64 = [&](int slot) { double v; std::memcpy(&v, raw + 8 * slot, 8); return v; };
+  RegistrationParams p;
+  p.num_edge_neighbors = u64(0), p.max_edge_neighbor_dist = f64(1), p.min_line_fit_points = u64(2);
+  p.min_line_condition_number = f64(3), p.num_plane_neighbors = u64(4), p.max_plane_neighbor_dist = f64(5);
+  p.min_plane_fit_points = u64(6), p.max_avg_point_plane_dist = f64(7), p.max_iterations = u64(8);
+  p.rotation_convergence_thresh = f64(9), p.position_convergence_thresh = f64(10), p.min_associations = u64(11);
+  LoamFeatures<Vector3d> source, target;
+  std::vector<Vector3d>* sets[4] = {&source.edge_points, &source.planar_points, &target.edge_points, &target.planar_points};
+  for (int s = 0; ok && s < 4; s++) {
+    std::vector<double> xyz(3 * n[s]);
+    ok = n[s] == 0 || std::fread(xyz.data(), sizeof(double), xyz.size(), f) == xyz.size();
+    for (size_t i = 0; ok && i < n[s]; i++) sets[s]->push_back(Vector3d(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]));
+  }
+  std::fclose(f);
+  if (!ok) return 2;
+  auto detail = std::make_shared<RegistrationDetail>();
+  const Pose3d pose = registerFeatures<ParenAccessor>(source, target, Pose3d::fromArray(init), p, detail);
+  double out[7];
+  pose.toArray(out);
+  std::vector<uint64_t> words = {(uint64_t)detail->termination_type, (uint64_t)detail->iteration_info.size()};
+  for (const auto& it : detail->iteration_info) words.push_back(it.edge_associations.size()), words.push_back(it.plane_associations.size());
+  f = std::fopen(out_path, "wb");
+  if (!f) return 2;
+  ok = std::fwrite(out, sizeof(out), 1, f) == 1 && std::fwrite(words.data(), sizeof(uint64_t), words.size(), f) == words.size();
+  return std::fclose(f) == 0 && ok ? 0 : 2;
+}
+
+int main(int argc, char** argv) {
+  if (argc == 3) return file_mode(argv[1], argv[2]);
+  test_registration_params();
   test_internal_namespaces();
   test_curvature();
   test_valid_points();

@@ -101,3 +101,30 @@ def test_covariance_equals_the_numpy_helper(oracle):
     info = ctx().registration_information(*sets, pose=registered)
     want = I.covariance_numpy(info.information, info.weighted_sq_error, int(info.n_edge) + int(info.n_plane))
     assert np.abs(info.covariance() - want).max() <= 1e-12 * np.abs(want).max()
+
+
+def test_all_twelve_registration_fields_reach_the_information_pass(oracle):
+    """a parameter set with every field off its default and pairwise distinct (tests/reg_param_scenes.py: binding_sets), the plane
+    gate negative so that it acts: n_edge / n_plane are the model's, built from the association dump under the same parameters,
+    and differ from the counts under the default parameters and under each association field reset alone."""
+    import reg_param_scenes as S
+    over = S.binding_sets(oracle)["converged"]
+    sets = S.binding_room()
+    c = ctx()
+
+    def counts(fields):
+        reg = S.params(capi.RegistrationParams, **fields)
+        info = c.registration_information(*sets, pose=IDENT, reg=reg)
+        m = I.model(*I.records_of_dump(c.associate(*sets, IDENT, reg)))
+        I.check_against_model(info, m, "binding set")
+        return int(info.n_edge), int(info.n_plane)
+
+    base = counts(over)
+    valid_e, _, _, _ = oracle.associate(sets[0], sets[2], IDENT, False, S.params(oracle.RegParams, **over))
+    valid_p, _, _, _ = oracle.associate(sets[1], sets[3], IDENT, True, S.params(oracle.RegParams, **over))
+    assert base == (int(valid_e.sum()), int(valid_p.sum())) and base[0] > 20 and 100 < base[1] < len(sets[1]) - 100
+    assert counts({}) != base
+    for f in ("num_edge_neighbors", "max_edge_neighbor_dist", "min_line_fit_points", "num_plane_neighbors", "max_plane_neighbor_dist",
+              "min_plane_fit_points", "max_avg_point_plane_dist"):
+        assert counts({**over, f: S.DEFAULTS[f]}) != base, f
+    assert counts({**over, "min_line_condition_number": float("inf")}) == (0, base[1])

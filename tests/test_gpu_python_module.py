@@ -81,3 +81,34 @@ def test_float32_scans_take_the_fp32_input_path(oracle):
     assert np.array_equal(f.edge_points, wide[oe]) and np.array_equal(f.planar_points, wide[op])
     assert np.array_equal(loam.computeCurvature(A32, lp).view(np.uint64), oracle.compute_curvature(wide, H, W).view(np.uint64))
     assert np.array_equal(loam.computeValidPoints(A32, lp), oracle.compute_valid_points(wide, H, W, 1.0, 120.0))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["converged", "insufficient", "max_iter"])
+def test_all_twelve_registration_fields_through_the_module(oracle, name):
+    """RegistrationParams with all twelve fields off their defaults and pairwise distinct (tests/reg_param_scenes.py:
+    binding_sets; every field changes the oracle's result in one of the three sets when it alone is reset): the module returns
+    the bytes the C ABI returns for the same struct, and the oracle's termination and iteration count."""
+    import reg_param_scenes as S
+    from gpu_common import ctx
+    loam = _loam()
+    over = S.binding_sets(oracle)[name]
+    sets = S.binding_room()
+    params = loam.RegistrationParams()
+    for field, value in over.items():
+        setattr(params, field, value)
+    assert all(getattr(params, f) == over[f] for f in S.REG_FIELDS)  # (2^40-sized counts and infinities survive the attribute)
+    src, tgt = loam.LoamFeatures(), loam.LoamFeatures()
+    src.edge_points, src.planar_points, tgt.edge_points, tgt.planar_points = sets
+    detail = loam.RegistrationDetail()
+    pose = loam.registerFeatures(source=src, target=tgt, target_T_source_init=loam.Pose3d.Identity(), params=params, detail=detail)
+    r = pose.rotation
+    got = np.array([r.x(), r.y(), r.z(), r.w(), *pose.translation])
+    pg, tg, ig, det = ctx().register_features(*sets, reg=S.params(capi.RegistrationParams, **over), want_detail=True)
+    assert got.tobytes() == pg.tobytes() and int(detail.termination_type) == tg and len(detail.iteration_info) == ig
+    assert [(len(i.edge_associations), len(i.plane_associations)) for i in detail.iteration_info] == \
+           [(d["n_edge"], d["n_plane"]) for d in det["iterations"]]
+    po, to, io = oracle.register_features(*sets, None, S.params(oracle.RegParams, **over))
+    assert (tg, ig) == (to, io)
+    rot, trans = pose_diff(oracle, po, got)
+    assert rot < 1e-5 and trans < 1e-5
