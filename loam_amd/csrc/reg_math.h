@@ -769,6 +769,187 @@ LOAMX_HD int knn_search(const GridDesc& g, const uint32_t* __restrict__ cell_sta
   return knn_finish(r, k, max_dist);
 }
 
+/* ------------------------------------------------------------------------------------------------
+ * The exact search of ONE query by a row of 16 lanes (associate_fit_late_kernel): knn_search's result, bit for bit, whenever
+ * the 3x3x3 block around the query's cell proves it — which round 1's guard has already found for every query on the late list.
+ *
+ * One lane walks the block's rows one behind the other, four gathers a trip, each trip a round trip to memory behind the last;
+ * here the nine ranges are one flattened stream dealt to the row's lanes (lane l: candidates l, l + 16, ...), a lane's loads of
+ * a batch (kRow16Batch points: the registers that hold them are the limit) are all in flight together, every lane keeps its own
+ * k best by (d2, orig) (knn_insert), and k rounds of a row-wide minimum over the lanes' heads (DPP row operations) merge them.
+ * (d2, orig) is a strict total order, so the result does not depend on the deal.
+ *
+ * knn_round1 leaves out rows whose slab lies beyond the radius bound (their points fail the radius filter) and rows beyond the
+ * running k-th distance (their points cannot enter the list). The first is repeated here, so that the entries behind `kept`
+ * are knn_search's as well; the second changes nothing in a list of the k smallest.
+ *
+ * The functions are written over NL lanes held by the caller: 1 on the device (its own; the other 15 are the row's), 16 on the
+ * host (a plain loop over virtual lanes: tests/hostcheck_late_rows). Only the row-wide minimum differs between the two.
+ * ---------------------------------------------------------------------------------------------- */
+constexpr int kRow16Lanes = 16;
+constexpr int kRow16Batch = 8;      // candidates a lane loads together: 8 x 32 bytes in flight, 64 registers
+constexpr int kRow16PerLane = 16;   // a lane's share of a block at most: two batches
+constexpr uint32_t kRow16Cap = kRow16Lanes * kRow16PerLane;  // 256 candidates: the trip_budget scenes' 252 points of one cell fit; beyond: the one-lane search
+
+struct KnnHead {
+  double d2;
+  uint32_t orig, pos;
+};
+LOAMX_HD bool knn_head_before(const KnnHead& a, const KnnHead& b) { return a.d2 < b.d2 || (a.d2 == b.d2 && a.orig < b.orig); }
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// v of lane (l ^ J) of the same row of 16, J = 1, 2, 4, 8 (the forms of tools/probes/dpp_xor.hip)
+template <int J>
+__device__ __forceinline__ uint32_t row16_xor_b32(uint32_t v) {
+  static_assert(J == 1 || J == 2 || J == 4 || J == 8, "inside a row of 16 lanes");
+  if constexpr (J == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);        // quad_perm [1,0,3,2]
+  else if constexpr (J == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
+  else if constexpr (J == 4) {
+    const int t = __builtin_amdgcn_update_dpp(0, (int)v, 0x104, 0xF, 0x5, false);     // row_shl:4 -> quads 0, 2 take lane + 4
+    return (uint32_t)__builtin_amdgcn_update_dpp(t, (int)v, 0x114, 0xF, 0xA, false);  // row_shr:4 -> quads 1, 3 take lane - 4
+  } else return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true);  // row_ror:8
+}
+template <int J>
+__device__ __forceinline__ KnnHead row16_min_step(const KnnHead& m) {
+  KnnHead o;
+  o.d2 = knn_key_join(row16_xor_b32<J>(knn_key_hi(m.d2)), row16_xor_b32<J>(knn_key_lo(m.d2)));
+  o.orig = row16_xor_b32<J>(m.orig), o.pos = row16_xor_b32<J>(m.pos);
+  return knn_head_before(o, m) ? o : m;
+}
+#endif
+
+// the smallest head (d2, orig) of the row's 16 lanes, on every lane. Empty lists hold (DBL_MAX, 0xFFFFFFFF, position 0) on every
+// lane alike.
+template <int KM, int NL>
+LOAMX_HD KnnHead knn_row16_min_head(const KnnResult<KM> (&lanes)[NL]) {
+  KnnHead m{lanes[0].d2[0], lanes[0].orig[0], lanes[0].pos[0]};
+#if defined(__HIP_DEVICE_COMPILE__)
+  static_assert(NL == 1, "a device lane holds its own list; the row is the other 15");
+  m = row16_min_step<1>(m), m = row16_min_step<2>(m), m = row16_min_step<4>(m), m = row16_min_step<8>(m);
+#else
+  for (int v = 1; v < NL; v++) {  // (the host holds the whole row: NL = 16)
+    const KnnHead o{lanes[v].d2[0], lanes[v].orig[0], lanes[v].pos[0]};
+    if (knn_head_before(o, m)) m = o;
+  }
+#endif
+  return m;
+}
+
+// The selection step: the k smallest of the lanes' lists (each ascending by (d2, orig), padded as knn_init leaves them) into
+// `out`, ascending, on every lane; the lanes' lists are used up. k rounds: row-wide minimum of the heads, the owner pops its own.
+template <int KM, int NL>
+LOAMX_HD void knn_row16_select(KnnResult<KM> (&lanes)[NL], int k, KnnResult<KM>& out) {
+  knn_init(out);
+#pragma unroll
+  for (int j = 0; j < KM; j++) {
+    if (j < k) {  // (uniform)
+      const KnnHead m = knn_row16_min_head<KM, NL>(lanes);
+      out.d2[j] = m.d2, out.orig[j] = m.orig, out.pos[j] = m.pos;
+#pragma unroll
+      for (int v = 0; v < NL; v++) {
+        KnnResult<KM>& r = lanes[v];
+        const bool own = m.orig != 0xFFFFFFFFu && r.orig[0] == m.orig;  // (original indices are distinct)
+#pragma unroll
+        for (int u = 0; u < KM - 1; u++) {
+          r.d2[u] = own ? r.d2[u + 1] : r.d2[u];
+          r.pos[u] = own ? r.pos[u + 1] : r.pos[u];
+          r.orig[u] = own ? r.orig[u + 1] : r.orig[u];
+        }
+        r.d2[KM - 1] = own ? kDblMax : r.d2[KM - 1];
+        r.pos[KM - 1] = own ? 0u : r.pos[KM - 1];
+        r.orig[KM - 1] = own ? 0xFFFFFFFFu : r.orig[KM - 1];
+      }
+    }
+  }
+  double w = out.d2[KM - 1];
+#pragma unroll
+  for (int j = 0; j < KM - 1; j++)
+    if (j == k - 1) w = out.d2[j];
+  out.worst = w;  // as knn_insert leaves it: DBL_MAX until k points are held
+}
+
+// knn_search of q by a row of 16 lanes, `lane0` = the number in its row of the first lane the caller holds (device: its own;
+// host: 0). true: r and kept are knn_search's, on every lane. false: the block does not decide the query (the search would go
+// on to wider shells, or starts away from the query's cell, or the block holds more than kRow16Cap candidates): the caller runs
+// knn_search. The rows and cells of the block are clamped as knn_round1_list clamps them.
+template <int KM, int NL>
+LOAMX_HD bool knn_exact_block_row16(const GridDesc& g, const uint32_t* __restrict__ cell_start, const GridPoint* __restrict__ sp,
+                                    Vec3 q, int k, double max_dist, int lane0, KnnResult<KM>& r, int& kept) {
+  knn_init(r);
+  kept = 0;
+  if (g.n_points == 0 || k <= 0) return true;
+  const int32_t cx = grid_cell_coord(q.x, g.ox, g.inv_h);
+  const int32_t cy = grid_cell_coord(q.y, g.oy, g.inv_h);
+  const int32_t cz = grid_cell_coord(q.z, g.oz, g.inv_h);
+  const int32_t out = grid_outside_distance(g, cx, cy, cz);
+  if (max_dist > 0.0 && out >= 1 && (double)(out - 1) * g.h >= max_dist) return true;  // (knn_search: nothing passes the radius filter)
+  if (out > 1) return false;                                                             // (the search starts at shell `out`)
+  // ---- the nine rows: 18 cell_start entries in flight together, rows beyond the radius bound emptied, one running total
+  const double r2 = knn_radius_bound(max_dist);
+  double sy2m = slab_dist(q.y, g.oy, g.h, cy - 1), sy2p = slab_dist(q.y, g.oy, g.h, cy + 1);
+  double sz2m = slab_dist(q.z, g.oz, g.h, cz - 1), sz2p = slab_dist(q.z, g.oz, g.h, cz + 1);
+  sy2m *= sy2m, sy2p *= sy2p, sz2m *= sz2m, sz2p *= sz2p;
+  const int32_t xa = cx - 1 < 0 ? 0 : cx - 1, xb = cx + 1 > g.nx - 1 ? g.nx - 1 : cx + 1;
+  uint32_t rb[9], re[9];
+#pragma unroll
+  for (int j = 0; j < 9; j++) {
+    const int32_t iy = cy + (j % 3) - 1, iz = cz + (j / 3) - 1;
+    const bool ok = xa <= xb && iy >= 0 && iy <= g.ny - 1 && iz >= 0 && iz <= g.nz - 1;
+    const uint32_t row = ok ? (uint32_t)((iz * g.ny + iy) * g.nx) : 0u;
+    rb[j] = ok ? cell_start_at(cell_start, row + (uint32_t)xa) : 0u;
+    re[j] = ok ? cell_start_at(cell_start, row + (uint32_t)xb + 1u) : 0u;
+  }
+  uint32_t pre[10];  // candidates in front of row j of the stream
+  pre[0] = 0u;
+#pragma unroll
+  for (int j = 0; j < 9; j++) {
+    const double sy2 = j % 3 == 0 ? sy2m : (j % 3 == 1 ? 0.0 : sy2p), sz2 = j / 3 == 0 ? sz2m : (j / 3 == 1 ? 0.0 : sz2p);
+    const bool in_reach = sy2 + sz2 <= r2;  // (knn_round1's test against the radius bound)
+    pre[j + 1] = pre[j] + ((in_reach && rb[j] < re[j]) ? re[j] - rb[j] : 0u);
+  }
+  const uint32_t total = pre[9];
+  if (total > kRow16Cap) return false;
+  // ---- the stream, dealt to the lanes: every lane its own k best
+  KnnResult<KM> mine[NL];
+#pragma unroll
+  for (int v = 0; v < NL; v++) knn_init(mine[v]);
+  for (uint32_t base = 0; base < total; base += (uint32_t)(kRow16Lanes * kRow16Batch)) {  // (uniform over the row)
+#pragma unroll
+    for (int v = 0; v < NL; v++) {
+      uint32_t at[kRow16Batch];
+      bool real[kRow16Batch];
+#pragma unroll
+      for (int u = 0; u < kRow16Batch; u++) {
+        const uint32_t n = base + (uint32_t)(lane0 + v) + (uint32_t)(u * kRow16Lanes);
+        real[u] = n < total;
+        uint32_t p = 0u;
+#pragma unroll
+        for (int j = 0; j < 9; j++)
+          if (n >= pre[j] && n < pre[j + 1]) p = rb[j] + (n - pre[j]);
+        at[u] = p;  // (position 0 for the lanes past the end: a valid entry, masked below)
+      }
+      GridPoint t[kRow16Batch];
+#pragma unroll
+      for (int u = 0; u < kRow16Batch; u++)
+        t[u] = *reinterpret_cast<const GridPoint*>(reinterpret_cast<const char*>(sp) + (uint32_t)(at[u] << 5));
+#pragma unroll
+      for (int u = 0; u < kRow16Batch; u++) {
+        const double dx = q.x - t[u].x, dy = q.y - t[u].y, dz = q.z - t[u].z;
+        const double d2 = dx * dx + dy * dy + dz * dz;  // nanoflann L2_Simple, as knn_scan_batch
+        if (real[u] && d2 <= mine[v].worst) knn_insert(mine[v], k, d2, at[u], t[u].orig);
+      }
+    }
+  }
+  // ---- the k best of the row, the radius filter, and knn_done's test for the block
+  knn_row16_select<KM, NL>(mine, k, r);
+  kept = knn_finish(r, k, max_dist);
+  if (!knn_done(g, q, k, max_dist, cx, cy, cz, r, 1)) {
+    kept = 0;
+    return false;
+  }
+  return true;
+}
+
 // The keyed search on its own: number of neighbours kept, or -1 when the keys cannot decide the
 // query (the caller then runs knn_search). Neighbour j (ascending) is pos[(KM - k) + j] — the keyed
 // collector keeps its k-th key in a fixed register, which shifts the list by KM - k.

@@ -1589,25 +1589,60 @@ __global__ __launch_bounds__(kRestThreads, 3) void associate_fit_queued_kernel(R
 // The late list of associate_fit_mixed_kernel (selections the fit's verification refused: tied or inverted exact
 // distances, a rejected key too close to the k-th — fractions of a percent of a scan's queries): the exact collector, then
 // the fit, with the results in the query's own slot of nn. On the main stream behind the queue chain's join.
+//
+// (round 9) One ROW of 16 lanes per late query, four rows a workgroup: entry t of a pair's list goes to row t mod (4 x the pair's
+// workgroups), so that a few dozen entries are spread over all of the pair's workgroups. The row searches the query's 3x3x3 block
+// together (knn_exact_block_row16: every lane's candidate loads in flight at once, where one lane made a dependent round trip per
+// four candidates); lane 0 of the row stores the list and fits. A query the block does not decide is searched by lane 0 alone
+// (knn_search), as every query was. What does not depend on the list entry — the list's length, the pair's state and pose, the
+// grid — is uniform: scalar loads, issued together in front of the first test.
+constexpr int kLateRows = kRestThreads / kRow16Lanes;  // rows (late queries) of a workgroup at a time
 template <bool PLANE, int KM>
-__global__ __launch_bounds__(kRestThreads, 3) void associate_fit_late_kernel(RegBatch B, RegConfig C, uint32_t blocks_per_pair) {  // (3: as associate_fit_queued_kernel)
+__global__ __launch_bounds__(kRestThreads, 3) void associate_fit_late_kernel(RegBatch B, RegConfig C, uint32_t blocks_per_pair) {  // (3: 168 registers, 184 bytes of scratch, fit_one's as before; at 4 — 128 registers — the row search spills 156 bytes more and the kernel takes 175 / 127 / 106 us instead of 115 / 93 / 71: EXPERIMENTS.md, round 9)
   size_t pair;
   uint32_t chunk0;
   if (!assoc_map(B, blockIdx.x, blocks_per_pair, pair, chunk0)) return;
-  const uint32_t late = B.n_assoc[8 * pair + 6 + (PLANE ? 1 : 0)];
-  if (late == 0u) return;                                             // uniform per workgroup
-  const PairState& S = B.state[pair];
-  if (!S.active) return;                                              // uniform per workgroup
-  __shared__ uint32_t s_rows[18 * kRestThreads];
   const RegKind& K = B.kind[PLANE];
+  const RegKindConfig& CK = C.kind[PLANE];
+  const GridSet &gs = K.grid, &src_gs = K.src_grid;
+  const PairState& S = B.state[pair];
+  const uint32_t late = B.n_assoc[8 * pair + 6 + (PLANE ? 1 : 0)];
+  const uint32_t active = S.active;
+  const GridDesc g = gs.desc[pair];
+  double est[7];
+#pragma unroll
+  for (int c = 0; c < 7; c++) est[c] = S.est[c];
+  if (late == 0u || !active) return;                                  // uniform per workgroup
+  __shared__ uint32_t s_rows[18 * kLateRows];                         // (the one-lane search of lane 0 of every row)
   const size_t stride = K.stride;
+  const size_t field = B.n_pairs * stride;
   uint32_t* nn = K.nn;  // (written and read back here: no __restrict__)
   const uint32_t* __restrict__ list = K.exact + pair * stride;
+  const uint32_t* __restrict__ cs = gs.cell_start + pair * (size_t)(kGridCellsCap + 1);
+  const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
+  const GridPoint* __restrict__ src = src_gs.sorted + pair * src_gs.stride;
+  int k = CK.k;
+  k = k < KM ? k : KM;
+  const int row = (int)(threadIdx.x / kRow16Lanes), lane = (int)(threadIdx.x % kRow16Lanes);
   uint32_t count = 0;
-  for (uint32_t t = chunk0 * kRestThreads + threadIdx.x; t < late && t < stride; t += blocks_per_pair * kRestThreads) {
+  // (t is uniform over a row; the four entries of a pass lie side by side: one load instruction of the wavefront)
+  for (uint32_t t = chunk0 * kLateRows + row; t < late && t < stride; t += blocks_per_pair * kLateRows) {
     const uint32_t i = list[stride - 1 - t];
-    knn_exact_one<PLANE, KM>(B, C, S, pair, i, pair * stride + i, nn, s_rows + threadIdx.x, kRestThreads);
-    count += fit_one<PLANE, KM, true>(B, C, S, pair, i, nn, pair * stride + i) ? 1u : 0u;
+    const GridPoint sq = src[i];
+    const Vec3 p = pose_act(est, v3(sq.x, sq.y, sq.z));
+    KnnResult<KM> r;
+    int kept;
+    const bool decided = knn_exact_block_row16<KM, 1>(g, cs, sp, p, k, CK.r, lane, r, kept);
+    if (lane == 0) {
+      if (!decided) kept = knn_search(g, cs, sp, p, k, CK.r, r, s_rows + row, kLateRows);
+      const size_t slot = pair * stride + i;
+      uint32_t pos[KM];
+      knn_shift_positions<KM>(r.pos, k, pos);  // neighbour j is slot (KM - k) + j
+      nn[slot] = (uint32_t)kept;
+#pragma unroll
+      for (int j = 0; j < KM; j++) nn[(size_t)(1 + j) * field + slot] = pos[j];
+      count += fit_one<PLANE, KM, true>(B, C, S, pair, i, nn, slot) ? 1u : 0u;
+    }
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) count += __shfl_xor(count, off);
