@@ -6,4 +6,5 @@
 #include "kdtree.h"
 #include "organize.h"
 #include "place.h"
+#include "posegraph.h"
 #include "registration.h"

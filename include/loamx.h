@@ -796,6 +796,109 @@ int loamx_place_descriptor_f32(loamx_ctx* ctx, const loamx_place_db* db, const f
 int loamx_place_search(loamx_ctx* ctx, const loamx_place_db* db, const uint16_t* query_desc, size_t n_queries,
                        const uint32_t* id_end, uint32_t num_candidates, loamx_place_match* out);
 
+/* ---- pose graph (no reference counterpart). The consumer of everything above: odometry edges from a scan sequence, loop edges
+ * from place recognition and a registration, each weighted by its loamx_reg_information matrix, corrected together by a sparse
+ * SE(3) least-squares solve: Levenberg-Marquardt over block-Jacobi preconditioned conjugate gradients. Poses, edges and the result
+ * stay on the device; a solve reads nothing back. Everything is FP64 rounded operation by operation, the device uses no libm
+ * beyond sqrt and no floating-point atomics, and nothing depends on thread scheduling: the same bytes on every run, and a
+ * host build of the same arithmetic (loam_amd/csrc/posegraph_math.h) can be compared by equality of bytes.
+ *
+ * Poses are world_T_i as pose7, composed with the arithmetic of Pose3d::compose; inv(T) = (conj(q), -(conj(q) rotating t)).
+ * Edge: Z = a_T_b measures pose b in the frame of pose a (a in the target role, b in the source role): pair p of a sequence is
+ *   the edge (p, p + 1, results[p].pose, info[p].information), a loop edge is (old, new, old_T_new, its information).
+ *   information is in the basis of loamx_reg_information: left perturbation Z <- (Exp(omega), t) o Z, rotation first; only its
+ *   upper triangle is read, and it is mirrored.
+ * Error of an edge:  zhat = inv(T_a) o T_b;  q_D = q_zhat (x) conj(q_Z);  t_D = t_zhat - q_D rotating t_Z;
+ *   e = [2 sgn(w_D) (x_D, y_D, z_D), t_D] with sgn(0) = +1 (to first order the (omega, t) of the information's basis; no atan2);
+ *   chi2 = e . (Omega e), Omega e row by row. A measurement composed from the poses by the same arithmetic has e = 0 exactly.
+ * Variables: a right perturbation delta_i = (omega_i, tau_i) of every pose that is not fixed, with the retraction
+ *   T_i <- T_i o (normalise([omega_i / 2, 1]), tau_i).  A = de/d delta_a and B = de/d delta_b at delta = 0 are closed forms
+ *   (posegraph_math.h: pgo_jacobians), row-major 6 x 6, columns omega then tau.
+ * Huber (huber_delta > 0 and chi2 > delta^2): the edge's blocks and gradients are scaled by w = delta / chi and its cost is
+ *   2 delta chi - delta^2; otherwise w = 1 and the cost is chi2. The cost of a graph is the sum of its edges' costs.
+ * Normal equations: per edge H_aa = w A^T Omega A, H_ab = w A^T Omega B, H_bb = w B^T Omega B, g_a = w A^T Omega e,
+ *   g_b = w B^T Omega e; per pose the diagonal block and gradient are the sums over its incident (edge, side) entries in
+ *   ascending (edge, side) order (side 0: the pose is the edge's a). Fixed poses have delta = 0 and leave the system.
+ * Levenberg-Marquardt: the diagonal entry D_kk becomes D_kk + lambda max(D_kk, 1e-6) (the floor keeps a pose whose edges carry
+ *   no information solvable); lambda starts at initial_lambda. An iteration solves for delta, forms the candidate poses and
+ *   their cost c1 and then, with c0 the cost before and m = max |delta_k| over all poses:
+ *     m <= step_tolerance                          STEP_CONVERGED, the poses stay as they were (checked first);
+ *     c1 < c0                                      accepted: the candidate becomes the poses, lambda <- max(lambda / 10, 1e-12),
+ *                                                  and COST_CONVERGED if c0 - c1 <= cost_tolerance c0;
+ *     otherwise                                    rejected: lambda <- 10 lambda, LAMBDA_OVERFLOW if lambda > 1e12;
+ *     then MAX_ITERATIONS once max_iterations iterations have run.
+ * Inner solve: PCG from x = 0 on (H + damping) x = -g, preconditioned by the Cholesky inverses of the damped 6 x 6 diagonal
+ *   blocks (a block whose Cholesky meets a non-positive pivot takes its pose out of the system for that iteration). It stops
+ *   at r.z <= pcg_tolerance^2 r0.z0, after min(max_pcg_iterations, 6 n_poses) iterations (conjugate gradients end within as
+ *   many steps as there are unknowns in exact arithmetic), or at p.q <= 0, where it keeps x. A truncated solve is still a
+ *   descent step.
+ * Sums that cross threads (the cost, r.z, p.q, max |delta|): per edge or per pose in index order, fixed chunks of 256 reduced by
+ *   the tree of posegraph_math.h (strides 128 ... 1), the chunks added in ascending order.
+ * Edge indices are checked before anything is indexed with them: an edge with a == b, a >= n_poses or b >= n_poses is counted
+ *   and never followed. */
+enum {
+  LOAMX_PGO_COST_CONVERGED = 0,
+  LOAMX_PGO_STEP_CONVERGED = 1,
+  LOAMX_PGO_MAX_ITERATIONS = 2,
+  LOAMX_PGO_LAMBDA_OVERFLOW = 3,
+  LOAMX_PGO_NOTHING_TO_DO = 4, /* no poses, no edges, or no pose that is not fixed */
+  LOAMX_PGO_BAD_INPUT = 5      /* some edge is invalid: n_bad_edges of them; the poses are untouched */
+};
+typedef struct {
+  uint32_t a, b;
+  double a_T_b[7];
+  double information[36];
+} loamx_pgo_edge; /* 352 bytes */
+typedef struct {
+  uint32_t max_iterations;     /* 20 */
+  uint32_t max_pcg_iterations; /* 500 */
+  double pcg_tolerance;        /* 1e-8 */
+  double initial_lambda;       /* 1e-4 */
+  double cost_tolerance;       /* 1e-9 */
+  double step_tolerance;       /* 1e-10 */
+  double huber_delta;          /* 0: off */
+} loamx_pgo_params;
+void loamx_pgo_default_params(loamx_pgo_params* p);
+typedef struct {
+  double initial_cost, final_cost;
+  double lambda;               /* after the last iteration */
+  double max_update;           /* max |delta_k| of the last iteration */
+  uint32_t iterations;         /* LM iterations run */
+  uint32_t accepted;           /* of those, accepted */
+  uint32_t pcg_iterations;     /* total over the solve */
+  uint32_t termination;        /* LOAMX_PGO_* */
+  uint32_t n_bad_edges;
+  uint32_t reserved;           /* 0 */
+} loamx_pgo_summary; /* 56 bytes */
+/* one edge as the solver's linearisation kernel sees it */
+typedef struct {
+  double e[6];
+  double chi2;
+  double weight;
+  double A[36], B[36];
+} loamx_pgo_linearization; /* 640 bytes */
+/* d_poses: n_poses x 7, in and out; d_fixed: n_poses bytes, non-zero = fixed, or NULL = pose 0 only; d_summary: one record, or
+ * NULL. Asynchronous on the context's stream; no synchronisation unless the workspace has to grow. With an invalid edge the
+ * poses are left untouched and the summary says LOAMX_PGO_BAD_INPUT with n_bad_edges. n_poses == 0 or n_edges == 0:
+ * LOAMX_PGO_NOTHING_TO_DO. LOAMX_ERR_BAD_PARAM: a null ctx, params, d_poses or d_edges (with poses / edges), a non-finite
+ * parameter, a negative tolerance or huber_delta, initial_lambda <= 0, max_iterations == 0; LOAMX_ERR_UNSUPPORTED: 2^31 poses
+ * or edges or more. The device form does not look at the values of the poses and edges. */
+int loamx_pose_graph_optimize_dev(loamx_ctx* ctx, double* d_poses, size_t n_poses, const uint8_t* d_fixed, const loamx_pgo_edge* d_edges,
+                                  size_t n_edges, const loamx_pgo_params* params, loamx_pgo_summary* d_summary);
+/* Host memory in, host memory out, synchronous. Further LOAMX_ERR_BAD_PARAM: a null summary, a non-finite pose, measurement or
+ * information entry, an invalid edge, no fixed pose. n_poses == 0 or n_edges == 0: LOAMX_OK, LOAMX_PGO_NOTHING_TO_DO, the poses
+ * unchanged. A refused call writes nothing. */
+int loamx_pose_graph_optimize(loamx_ctx* ctx, double* poses, size_t n_poses, const uint8_t* fixed, const loamx_pgo_edge* edges,
+                              size_t n_edges, const loamx_pgo_params* params, loamx_pgo_summary* summary);
+/* Host form: e, chi2, weight, A, B of every edge at the given poses, by the solver's own linearisation kernel read out instead
+ * of consumed (what loamx_associate is to the registration). huber_delta as in the parameters (0: off). Refusals as above. */
+int loamx_pose_graph_linearize(loamx_ctx* ctx, const double* poses, size_t n_poses, const loamx_pgo_edge* edges, size_t n_edges,
+                               double huber_delta, loamx_pgo_linearization* out);
+/* The odometry edges of a sequence: pair p becomes d_edges[p] = (first_id + p, first_id + p + 1, d_results[p].pose,
+ * d_info[p].information), so that a drive goes sequence -> edges -> optimise without leaving the device. Asynchronous. */
+int loamx_pose_graph_edges_from_results_dev(loamx_ctx* ctx, const loamx_reg_result* d_results, const loamx_reg_information* d_info,
+                                            size_t n_pairs, uint32_t first_id, loamx_pgo_edge* d_edges);
+
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are
  * independent units). One process per GPU owns a contiguous block of pair ids and runs the single-GPU entry points

@@ -207,6 +207,45 @@ PLACE_MATCH_DTYPE = np.dtype([("id", np.uint32), ("shift", np.uint32), ("key_dis
 PLACE_NO_ID = 0xFFFFFFFF  # id of a record without an entry (fewer eligible entries than candidates asked for)
 
 
+class PgoParamsStruct(C.Structure):
+    """loamx_pgo_params (include/loamx.h)"""
+    _fields_ = [("max_iterations", C.c_uint32), ("max_pcg_iterations", C.c_uint32), ("pcg_tolerance", C.c_double),
+                ("initial_lambda", C.c_double), ("cost_tolerance", C.c_double), ("step_tolerance", C.c_double),
+                ("huber_delta", C.c_double)]
+
+
+class PgoParams:
+    """The parameters of a pose-graph solve (loamx_pgo_params). Anything left out takes the C ABI's default."""
+    FIELDS = tuple(f[0] for f in PgoParamsStruct._fields_)
+
+    def __init__(self, **kw):
+        d = PgoParamsStruct()
+        load().loamx_pgo_default_params(C.byref(d))
+        for name in self.FIELDS:
+            setattr(self, name, getattr(d, name))
+        for name, v in kw.items():
+            if name not in self.FIELDS:
+                raise TypeError(f"PgoParams has no field {name}")
+            setattr(self, name, v)
+
+    def struct(self):
+        for name in self.FIELDS[:2]:
+            if not 0 <= int(getattr(self, name)) <= 0xFFFFFFFF:
+                raise ValueError(f"PgoParams: {name} does not fit 32 bits")
+        return PgoParamsStruct(int(self.max_iterations), int(self.max_pcg_iterations), *(float(getattr(self, n)) for n in self.FIELDS[2:]))
+
+
+# loamx_pgo_edge, loamx_pgo_summary, loamx_pgo_linearization
+PGO_EDGE_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("a_T_b", np.float64, 7), ("information", np.float64, (6, 6))])
+PGO_SUMMARY_DTYPE = np.dtype([("initial_cost", np.float64), ("final_cost", np.float64), ("lambda", np.float64), ("max_update", np.float64),
+                              ("iterations", np.uint32), ("accepted", np.uint32), ("pcg_iterations", np.uint32),
+                              ("termination", np.uint32), ("n_bad_edges", np.uint32), ("reserved", np.uint32)])
+PGO_LINEARIZATION_DTYPE = np.dtype([("e", np.float64, 6), ("chi2", np.float64), ("weight", np.float64), ("A", np.float64, (6, 6)),
+                                    ("B", np.float64, (6, 6))])
+PGO_TERMINATIONS = ("COST_CONVERGED", "STEP_CONVERGED", "MAX_ITERATIONS", "LAMBDA_OVERFLOW", "NOTHING_TO_DO", "BAD_INPUT")
+(PGO_COST_CONVERGED, PGO_STEP_CONVERGED, PGO_MAX_ITERATIONS, PGO_LAMBDA_OVERFLOW, PGO_NOTHING_TO_DO, PGO_BAD_INPUT) = range(6)
+
+
 EXPORTS = [
     "loamx_default_fe_params", "loamx_default_reg_params", "loamx_status_string", "loamx_last_error",
     "loamx_ctx_create", "loamx_ctx_destroy", "loamx_ctx_set_stream", "loamx_ctx_synchronize",
@@ -238,6 +277,8 @@ EXPORTS = [
     "loamx_default_place_params", "loamx_place_db_create", "loamx_place_db_destroy", "loamx_place_db_sector_dirs", "loamx_place_db_size",
     "loamx_place_descriptors_dev", "loamx_place_descriptors_dev_f32", "loamx_place_db_add_dev", "loamx_place_db_read",
     "loamx_place_search_dev", "loamx_place_descriptor", "loamx_place_descriptor_f32", "loamx_place_search",
+    "loamx_pgo_default_params", "loamx_pose_graph_optimize_dev", "loamx_pose_graph_optimize", "loamx_pose_graph_linearize",
+    "loamx_pose_graph_edges_from_results_dev",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -476,6 +517,12 @@ def load(build_if_missing=True):
     lib.loamx_place_descriptor.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.loamx_place_descriptor_f32.argtypes = lib.loamx_place_descriptor.argtypes
     lib.loamx_place_search.argtypes = lib.loamx_place_search_dev.argtypes
+    lib.loamx_pgo_default_params.argtypes = [C.POINTER(PgoParamsStruct)]
+    lib.loamx_pgo_default_params.restype = None
+    lib.loamx_pose_graph_optimize_dev.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(PgoParamsStruct), vp]
+    lib.loamx_pose_graph_optimize.argtypes = lib.loamx_pose_graph_optimize_dev.argtypes  # (host pointers)
+    lib.loamx_pose_graph_linearize.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_double, vp]
+    lib.loamx_pose_graph_edges_from_results_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
     _lib = lib
     return lib
 
@@ -1336,6 +1383,46 @@ class Context:
     # ---- place recognition (include/loamx.h, "place recognition") --------------------------------------------
     def place_db(self, params=None):
         return PlaceDb(self, params)
+
+    @staticmethod
+    def _pgo_params(params):
+        return (params or PgoParams()).struct()
+
+    def pose_graph_optimize_dev(self, d_poses, n_poses, d_edges, n_edges, d_fixed=0, params=None, d_summary=0):
+        """loamx_pose_graph_optimize_dev: d_poses (n_poses x 7) corrected in place on the context's stream; d_fixed: n_poses bytes or 0
+        (pose 0 only); d_summary: one PGO_SUMMARY_DTYPE record or 0"""
+        ptr = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        p = self._pgo_params(params)
+        self._check(self.lib.loamx_pose_graph_optimize_dev(self.h, ptr(d_poses), n_poses, ptr(d_fixed) or None, ptr(d_edges), n_edges,
+                                                           C.byref(p), ptr(d_summary) or None))
+
+    def pose_graph_optimize(self, poses, edges, fixed=None, params=None):
+        """The host form -> (poses (n, 7), summary record of PGO_SUMMARY_DTYPE). edges: PGO_EDGE_DTYPE records."""
+        poses = np.array(poses, dtype=np.float64).reshape(-1, 7)
+        edges = np.ascontiguousarray(edges, dtype=PGO_EDGE_DTYPE)
+        fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed) != 0, dtype=np.uint8)
+        if fx is not None and len(fx) != len(poses):
+            raise ValueError("pose_graph_optimize: one fixed flag per pose")
+        summary = np.zeros(1, dtype=PGO_SUMMARY_DTYPE)
+        p = self._pgo_params(params)
+        self._check(self.lib.loamx_pose_graph_optimize(self.h, poses.ctypes.data, len(poses), None if fx is None else fx.ctypes.data,
+                                                       edges.ctypes.data if len(edges) else None, len(edges), C.byref(p), summary.ctypes.data))
+        return poses, summary[0]
+
+    def pose_graph_linearize(self, poses, edges, huber_delta=0.0):
+        """e, chi2, weight, A, B of every edge at the given poses (PGO_LINEARIZATION_DTYPE), by the solver's own kernel"""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        edges = np.ascontiguousarray(edges, dtype=PGO_EDGE_DTYPE)
+        out = np.zeros(len(edges), dtype=PGO_LINEARIZATION_DTYPE)
+        self._check(self.lib.loamx_pose_graph_linearize(self.h, poses.ctypes.data if len(poses) else None, len(poses),
+                                                        edges.ctypes.data if len(edges) else None, len(edges), float(huber_delta),
+                                                        out.ctypes.data if len(edges) else None))
+        return out
+
+    def pose_graph_edges_from_results_dev(self, d_results, d_info, n_pairs, d_edges, first_id=0):
+        """the odometry edges (first_id + p, first_id + p + 1) of a sequence's result and information records, on the device"""
+        ptr = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        self._check(self.lib.loamx_pose_graph_edges_from_results_dev(self.h, ptr(d_results), ptr(d_info), n_pairs, first_id, ptr(d_edges)))
 
     def synth_scan_pairs_dev(self, seed, first_pair, n_pairs, scan_lines, points_per_line, sigma, d_xyz):
         self._check(self.lib.loamx_synth_scan_pairs_dev(self.h, seed, first_pair, n_pairs, scan_lines,

@@ -461,6 +461,29 @@ void launch_place_shift_stage(const PlaceEntries& E, const PlaceShape& P, const 
                               const PlaceCand* cands, uint32_t n_queries, uint32_t K, loamx_place_match* d_tmp, loamx_place_match* d_out,
                               hipStream_t s);
 
+/* ---- pose graph (posegraph_kernels.hip; the rule: posegraph_math.h and loamx.h) ----------------------------------------------- */
+// byte offsets of a solve's arrays in its one workspace block (every array starts on a 256-byte boundary)
+struct PgoLayout {
+  size_t state;                    // PgoState[2]
+  size_t zeroed, zeroed_bytes;     // the bad-edge count and the degrees: zeroed before every solve
+  size_t off, cursor, list, fixed;
+  size_t blocks, pose_blocks;
+  size_t vec[6];                   // x, r, z, q, p[0], p[1]
+  size_t cand;
+  size_t cost_part, cand_cost_part, rz_part, pq_part, max_part;
+  size_t bytes;
+};
+PgoLayout pgo_layout(size_t n_poses, size_t n_edges);
+// the whole solve, enqueued: n_poses, n_edges >= 1 and < 2^31, params checked by the caller; ws: pgo_layout(...).bytes
+void launch_pgo_solve(double* d_poses, size_t n_poses, const uint8_t* d_fixed, const loamx_pgo_edge* d_edges, size_t n_edges,
+                      const loamx_pgo_params& params, loamx_pgo_summary* d_summary, void* ws, hipStream_t s);
+void launch_pgo_nothing(const loamx_pgo_params& params, loamx_pgo_summary* d_summary, hipStream_t s);
+size_t pgo_readout_ws_bytes(size_t n_edges);
+void launch_pgo_linearize_readout(const double* d_poses, const loamx_pgo_edge* d_edges, size_t n_edges, double huber_delta,
+                                  loamx_pgo_linearization* d_lin, double* cost_part, hipStream_t s);
+void launch_pgo_edges_from_results(const loamx_reg_result* d_results, const loamx_reg_information* d_info, size_t n_pairs, uint32_t first_id,
+                                   loamx_pgo_edge* d_edges, hipStream_t s);
+
 /* ---- map upkeep (map_kernels.hip): voxel filter against an occupancy table, crop, the stable compaction they share --- */
 constexpr uint32_t kMapTile = 256;             // points per tile of the compaction (one workgroup)
 constexpr uint32_t kMapNoSlot = 0xFFFFFFFFu;   // slot of a point that has no voxel (or whose probe gave up)

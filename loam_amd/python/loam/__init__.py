@@ -6,3 +6,4 @@ from .loam_python import (FeatureExtractionParams, LidarParams, LoamFeatures, Po
                           registerFeatures)
 from .loam_python import deskewScan, registerScanSequence  # noqa: F401  (extensions: scan sequences)
 from .loam_python import RegistrationInformation, registrationInformation  # noqa: F401  (extension: information matrix)
+from .loam_python import PoseGraph, PoseGraphParams, PoseGraphSummary  # noqa: F401  (extension: pose graph)

@@ -6,7 +6,7 @@
 // and deskewScan (include/loamx.h: "scan sequences"), and the class TargetIndex with a registerFeatures overload that
 // takes it (scan-to-map: "persistent target index" and "map upkeep"), and OrganizeParams / ScanLayout / organizeCloud, the way
 // in for clouds that are not organised scans yet ("unordered clouds into scans"), and PlaceParams / PlaceMatch / PlaceDatabase
-// ("place recognition"). Point clouds are contiguous (N,3) float64
+// ("place recognition"), and PoseGraphParams / PoseGraphSummary / PoseGraph ("pose graph"). Point clouds are contiguous (N,3) float64
 // arrays handed to the C ABI without per-point objects (a list of 3-vectors is converted once).
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -541,6 +541,56 @@ PYBIND11_MODULE(loam_python, m) {
             return d.search(place_desc_arg(d, query), num_candidates, id_end.value_or(0xFFFFFFFFu));
           },
           py::arg("query"), py::arg("num_candidates"), py::arg("id_end") = py::none());
+  py::class_<loam::PoseGraphParams>(m, "PoseGraphParams")
+      .def(py::init<>())
+      .def_readwrite("max_iterations", &loam::PoseGraphParams::max_iterations)
+      .def_readwrite("max_pcg_iterations", &loam::PoseGraphParams::max_pcg_iterations)
+      .def_readwrite("pcg_tolerance", &loam::PoseGraphParams::pcg_tolerance)
+      .def_readwrite("initial_lambda", &loam::PoseGraphParams::initial_lambda)
+      .def_readwrite("cost_tolerance", &loam::PoseGraphParams::cost_tolerance)
+      .def_readwrite("step_tolerance", &loam::PoseGraphParams::step_tolerance)
+      .def_readwrite("huber_delta", &loam::PoseGraphParams::huber_delta);
+  py::enum_<loam::PoseGraphSummary::TerminationType>(m, "PoseGraphTerminationType")
+      .value("COST_CONVERGED", loam::PoseGraphSummary::TerminationType::COST_CONVERGED)
+      .value("STEP_CONVERGED", loam::PoseGraphSummary::TerminationType::STEP_CONVERGED)
+      .value("MAX_ITERATIONS", loam::PoseGraphSummary::TerminationType::MAX_ITERATIONS)
+      .value("LAMBDA_OVERFLOW", loam::PoseGraphSummary::TerminationType::LAMBDA_OVERFLOW)
+      .value("NOTHING_TO_DO", loam::PoseGraphSummary::TerminationType::NOTHING_TO_DO)
+      .value("BAD_INPUT", loam::PoseGraphSummary::TerminationType::BAD_INPUT);
+  py::class_<loam::PoseGraphSummary>(m, "PoseGraphSummary")
+      .def_readonly("initial_cost", &loam::PoseGraphSummary::initial_cost)
+      .def_readonly("final_cost", &loam::PoseGraphSummary::final_cost)
+      .def_readonly("lambda_", &loam::PoseGraphSummary::lambda)
+      .def_readonly("max_update", &loam::PoseGraphSummary::max_update)
+      .def_readonly("iterations", &loam::PoseGraphSummary::iterations)
+      .def_readonly("accepted", &loam::PoseGraphSummary::accepted)
+      .def_readonly("pcg_iterations", &loam::PoseGraphSummary::pcg_iterations)
+      .def_readonly("termination_type", &loam::PoseGraphSummary::termination_type)
+      .def_readonly("n_bad_edges", &loam::PoseGraphSummary::n_bad_edges);
+  py::class_<loam::PoseGraph>(m, "PoseGraph")
+      .def(py::init<const loam::PoseGraphParams&>(), py::arg("params") = loam::PoseGraphParams())
+      .def_property("params", [](const loam::PoseGraph& g) { return g.params(); },
+                    [](loam::PoseGraph& g, const loam::PoseGraphParams& p) { g.params() = p; })
+      .def("addPose", &loam::PoseGraph::addPose, py::arg("world_T_pose"))
+      .def("setFixed", &loam::PoseGraph::setFixed, py::arg("id"), py::arg("fixed") = true)
+      .def(
+          "addEdge",
+          [](loam::PoseGraph& g, size_t a, size_t b, const loam::Pose3d& a_T_b, const loam::RegistrationInformation& info) {
+            g.addEdge(a, b, a_T_b, info);
+          },
+          py::arg("a"), py::arg("b"), py::arg("a_T_b"), py::arg("information"))
+      .def(
+          "addEdge",
+          [](loam::PoseGraph& g, size_t a, size_t b, const loam::Pose3d& a_T_b, const Arr& info) {
+            if (info.size() != 36) throw std::runtime_error("loam.PoseGraph.addEdge: the information matrix holds 6 x 6 entries");
+            g.addEdge(a, b, a_T_b, info.data());
+          },
+          py::arg("a"), py::arg("b"), py::arg("a_T_b"), py::arg("information"))
+      .def("numPoses", &loam::PoseGraph::numPoses)
+      .def("numEdges", &loam::PoseGraph::numEdges)
+      .def("pose", &loam::PoseGraph::pose, py::arg("id"))
+      .def("fixed", &loam::PoseGraph::fixed, py::arg("id"))
+      .def("optimize", &loam::PoseGraph::optimize);
   m.def("registerScanSequence", &register_scan_sequence<ArrF>, py::arg("scans"), py::arg("lidar_params"),
         py::arg("fe_params") = loam::FeatureExtractionParams(), py::arg("reg_params") = loam::RegistrationParams(),
         py::arg("inits") = py::none());

@@ -1,0 +1,175 @@
+"""CPU-only: the pose-graph optimiser's arithmetic (loam_amd/csrc/posegraph_math.h, built for the host by tests/hostcheck_posegraph
+with a loop that runs the whole solve in the kernels' orders) against the numpy model of the rule (tests/posegraph_common.py),
+against central differences and against an independent solver."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import posegraph_common as G
+from loam_amd import capi
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+# Whole solve against scipy: the largest relative difference of the final costs the host build shows on the three graphs below
+# is 6.9e-14 (ring40 6.86e-14, full8 1.98e-14, chain300 5.18e-14); the bound is ten times that.
+COST_REL_BOUND = 6.9e-13
+
+
+def _bytes_equal(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
+
+
+def test_layouts_and_defaults():
+    assert G.host_sizes() == (352, 48, 56, 640)
+    assert (capi.PGO_EDGE_DTYPE.itemsize, capi.PGO_SUMMARY_DTYPE.itemsize, capi.PGO_LINEARIZATION_DTYPE.itemsize) == (352, 56, 640)
+    assert (G.EDGE_DTYPE, G.SUMMARY_DTYPE, G.LIN_DTYPE) == (capi.PGO_EDGE_DTYPE, capi.PGO_SUMMARY_DTYPE, capi.PGO_LINEARIZATION_DTYPE)
+    import ctypes as C
+    assert C.sizeof(capi.PgoParamsStruct) == 48
+    p = capi.PgoParams()
+    assert {k: getattr(p, k) for k in p.FIELDS} == G.DEFAULTS
+    assert capi.PGO_TERMINATIONS[G.BAD_INPUT] == "BAD_INPUT" and len(capi.PGO_TERMINATIONS) == 6
+
+
+def _random_edges(n, seed):
+    rng = np.random.default_rng(seed)
+    poses = np.stack([G.rand_pose(rng, 3.0) for _ in range(2 * n)])
+    Z = np.stack([G.rand_pose(rng, 3.0) for _ in range(n)])
+    info = np.stack([G.rand_information(rng, scale=1.0) for _ in range(n)])
+    info[:, np.tril_indices(6, -1)[0], np.tril_indices(6, -1)[1]] = 777.0  # (the lower triangle is never read)
+    return poses, G.make_edges([(2 * i, 2 * i + 1) if i % 2 else (2 * i + 1, 2 * i) for i in range(n)], Z, info)
+
+
+def test_error_and_chi2_match_the_model_by_bytes():
+    poses, edges = _random_edges(400, 1)
+    lin = G.host_linearize(poses, edges)
+    e = G.edge_errors(poses, edges)
+    assert _bytes_equal(lin["e"], e)
+    assert _bytes_equal(lin["chi2"], G.chi2(edges["information"], e))
+    assert (lin["weight"] == 1.0).all()
+    w, _ = G.weight_cost(lin["chi2"], 3.0)
+    lin_h = G.host_linearize(poses, edges, huber_delta=3.0)
+    assert _bytes_equal(lin_h["weight"], w) and (w < 1.0).any() and _bytes_equal(lin_h["A"], lin["A"])
+
+
+def test_jacobians_against_central_differences():
+    """A and B against central differences (h = 1e-6) of the model's error through the model's retraction: truncation ~h^2,
+    rounding ~eps / h ~ 1e-10, both well inside 1e-7. Rotations up to 3 rad, w_D of either sign."""
+    poses, edges = _random_edges(200, 2)
+    lin = G.host_linearize(poses, edges)
+    Ta, Tb, Z = poses[edges["a"]], poses[edges["b"]], edges["a_T_b"]
+    wd = G.quat_mul(tuple(G.compose(G.inverse(Ta), Tb)[:, k] for k in range(4)), (-Z[:, 0], -Z[:, 1], -Z[:, 2], Z[:, 3]))[3]
+    assert (wd < -0.05).sum() > 20 and (wd > 0.05).sum() > 20
+    assert np.abs(2 * np.arccos(np.clip(np.abs(poses[:, 3]), 0, 1))).max() > 2.5
+    h = 1e-6
+    for k in range(6):
+        d = np.zeros((len(edges), 6))
+        d[:, k] = h
+        A_k = (G.error(G.retract(Ta, d), Tb, Z) - G.error(G.retract(Ta, -d), Tb, Z)) / (2 * h)
+        B_k = (G.error(Ta, G.retract(Tb, d), Z) - G.error(Ta, G.retract(Tb, -d), Z)) / (2 * h)
+        assert np.abs(lin["A"][:, :, k] - A_k).max() <= 1e-7, k
+        assert np.abs(lin["B"][:, :, k] - B_k).max() <= 1e-7, k
+    # the header's retraction is the model's
+    rng = np.random.default_rng(3)
+    for i in range(20):
+        d = rng.normal(size=6) * 10.0 ** rng.uniform(-8, 0)
+        assert _bytes_equal(G.host_retract(poses[i], d), G.retract(poses[i], d))
+
+
+def test_zero_noise_graph_costs_nothing_and_keeps_its_bytes():
+    rng = np.random.default_rng(4)
+    truth = np.stack([G.rand_pose(rng, 3.0) for _ in range(30)])
+    truth[5, :4] *= -1.0
+    pairs = [(i, i + 1) for i in range(29)] + [(29, 0), (17, 3), (4, 22)]
+    edges = G.make_edges(pairs, G.measured(truth, pairs, rng), G.rand_information(rng))
+    out, s = G.host_optimize(truth, edges)
+    assert s["initial_cost"] == 0.0 and s["final_cost"] == 0.0 and s["max_update"] == 0.0
+    assert s["termination"] == G.STEP_CONVERGED and s["iterations"] == 1 and s["accepted"] == 0 and s["pcg_iterations"] == 0
+    assert _bytes_equal(out, truth)
+
+
+GRAPHS = {
+    "ring40": lambda: G.chain_graph(40, 2, seed=10, closed=True)[:2] + (None,),
+    "full8": lambda: G.full_graph(8, seed=11)[:2] + (None,),
+    "chain300": lambda: G.chain_graph(300, 10, seed=12)[:2] + (None,),
+}
+
+
+@pytest.mark.parametrize("name", sorted(GRAPHS))
+def test_whole_solve_against_scipy(name):
+    """The host build's solve (tightened: 100 iterations, tolerances 1e-14 / 1e-12 / 1e-14) against scipy.optimize.least_squares on
+    the same residuals: final costs to COST_REL_BOUND relatively (measured: see the constant), poses up to the sign of q."""
+    poses, edges, fixed = GRAPHS[name]()
+    assert {"ring40": 42, "full8": 28, "chain300": 309}[name] == len(edges)
+    out, s = G.host_optimize(poses, edges, fixed, max_iterations=100, max_pcg_iterations=5000, pcg_tolerance=1e-12, cost_tolerance=1e-14,
+                             step_tolerance=1e-14)
+    ref, ref_cost = G.scipy_solve(poses, edges, fixed)
+    assert s["termination"] in (G.COST_CONVERGED, G.STEP_CONVERGED, G.LAMBDA_OVERFLOW)
+    assert abs(s["final_cost"] - G.graph_cost(out, edges)) <= 1e-12 * s["final_cost"]
+    rel = abs(s["final_cost"] - ref_cost) / ref_cost
+    print(f"{name}: cost {s['initial_cost']:.6g} -> {s['final_cost']:.17g}, scipy {ref_cost:.17g}, relative difference {rel:.3g}, "
+          f"{s['iterations']} LM / {s['pcg_iterations']} PCG iterations")
+    assert s["final_cost"] < 0.5 * s["initial_cost"]
+    assert rel <= COST_REL_BOUND
+    rot, trans = G.pose_distance(out, ref)
+    assert rot.max() < 1e-6 and trans.max() < 1e-5, (rot.max(), trans.max())
+
+
+def test_huber_contains_an_outlier():
+    poses, edges, _ = G.chain_graph(40, 3, seed=20, closed=True)
+    clean, _ = G.host_optimize(poses, edges)
+    bad = edges.copy()
+    bad["a_T_b"][-1, 4] += 5.0
+    plain, _ = G.host_optimize(poses, bad)
+    robust, sr = G.host_optimize(poses, bad, huber_delta=1.0)
+    err_plain, err_robust = G.pose_distance(plain, clean)[1].max(), G.pose_distance(robust, clean)[1].max()
+    assert err_robust < err_plain, (err_robust, err_plain)
+    assert G.host_linearize(robust, bad, huber_delta=1.0)["weight"][-1] < 1.0
+
+
+def test_every_termination_code():
+    poses, edges, _ = G.chain_graph(12, 1, seed=30, closed=True)
+    out, s = G.host_optimize(poses, edges)
+    assert s["termination"] == G.COST_CONVERGED and s["accepted"] >= 1 and s["final_cost"] < s["initial_cost"]
+    _, s1 = G.host_optimize(poses, edges, max_iterations=1, cost_tolerance=0.0)
+    assert s1["termination"] == G.MAX_ITERATIONS and s1["iterations"] == 1
+    # at the minimum no step lowers the cost any more: every one is rejected until lambda passes 1e12 ...
+    best, _ = G.host_optimize(poses, edges, max_iterations=100, cost_tolerance=0.0, step_tolerance=0.0, pcg_tolerance=1e-12)
+    _, s2 = G.host_optimize(best, edges, max_iterations=100, cost_tolerance=0.0, step_tolerance=0.0, initial_lambda=1e9)
+    assert s2["termination"] == G.LAMBDA_OVERFLOW and s2["lambda"] > 1e12
+    # ... unless the step is already below the step tolerance
+    out3, s3 = G.host_optimize(best, edges, step_tolerance=1e-3)
+    assert s3["termination"] == G.STEP_CONVERGED and s3["iterations"] == 1 and _bytes_equal(out3, best)
+    for p, e, f in ((poses, edges[:0], None), (poses, edges, np.ones(12, np.uint8)), (poses[:0], edges[:0], None)):
+        out4, s4 = G.host_optimize(p, e, f)
+        assert s4["termination"] == G.NOTHING_TO_DO and s4["iterations"] == 0 and _bytes_equal(out4, p)
+    bad = edges.copy()
+    bad["a"][3] = bad["b"][3]
+    bad["b"][7] = 12
+    out5, s5 = G.host_optimize(poses, bad)
+    assert s5["termination"] == G.BAD_INPUT and s5["n_bad_edges"] == 2 and _bytes_equal(out5, poses)
+
+
+def test_small_pieces():
+    rng = np.random.default_rng(40)
+    import ctypes as C
+    for n in (0, 1, 2, 3, 17, 300):
+        v = rng.permutation(n).astype(np.uint32) * 3
+        w = v.copy()
+        G.lib().hostcheck_pgo_sort(w.ctypes.data_as(C.c_void_p), C.c_uint32(n))
+        assert np.array_equal(w, np.sort(v))
+    M = G.rand_information(rng)
+    inv = np.zeros((6, 6))
+    assert G.lib().hostcheck_pgo_cholesky_inverse(M.ctypes.data_as(C.c_void_p), inv.ctypes.data_as(C.c_void_p)) == 0
+    assert np.abs(inv @ M - np.eye(6)).max() < 1e-9 and np.array_equal(inv, inv.T)
+    M[2, 2] = -1.0
+    assert G.lib().hostcheck_pgo_cholesky_inverse(M.ctypes.data_as(C.c_void_p), inv.ctypes.data_as(C.c_void_p)) == 1 and not inv.any()
+
+
+def test_sanitizer_program():
+    """the stand-alone ASan + UBSan build of the same file runs the solve over generated graphs"""
+    d = os.path.join(HERE, "hostcheck_posegraph")
+    subprocess.check_call(["make", "-s", "-C", d, "san"])
+    out = subprocess.run([os.path.join(d, "hostcheck_posegraph_san")], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "hostcheck_posegraph ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
