@@ -53,7 +53,9 @@ def motion_priors(poses, seed=5, yaw_sigma=np.radians(1.5), trans_sigma=0.1):
     return np.ascontiguousarray(out, dtype=np.float64)
 
 
-def main(scan_lines=32, points_per_line=512, huber_delta=0.0, threshold=THRESHOLD, min_age=MIN_AGE, verbose=True, ctx=None):
+def main(scan_lines=32, points_per_line=512, huber_delta=0.0, threshold=THRESHOLD, min_age=MIN_AGE, verbose=True, ctx=None, stage_hook=None):
+    """stage_hook(stage, ctx, d_scans, d_traj): called with "odometry" once the composed trajectory stands in d_traj and with
+    "corrected" right behind the solve, before anything synchronises (examples/global_map.py assembles its maps there)"""
     from loam_amd import capi
     c = ctx or capi.Context(0)
     H, W, n = scan_lines, points_per_line, N_SCANS
@@ -81,6 +83,8 @@ def main(scan_lines=32, points_per_line=512, huber_delta=0.0, threshold=THRESHOL
         c.pose_graph_edges_from_results_dev(d_results, d_info, n - 1, d_edges)
         c.synchronize()
         odometry = d_traj.download(np.float64, n * 7).reshape(n, 7)
+        if stage_hook:
+            stage_hook("odometry", c, d_xyz, d_traj)
 
         # the loop: the last scan against the stored scans at least min_age old
         descs = [db.descriptor(s) for s in scans]
@@ -102,6 +106,8 @@ def main(scan_lines=32, points_per_line=512, huber_delta=0.0, threshold=THRESHOL
 
         # one call corrects the trajectory in place (pose 0 stays where it is)
         c.pose_graph_optimize_dev(d_traj, n, d_edges, n, params=capi.PgoParams(huber_delta=huber_delta), d_summary=d_summary)
+        if stage_hook:
+            stage_hook("corrected", c, d_xyz, d_traj)
         c.synchronize()
         corrected = d_traj.download(np.float64, n * 7).reshape(n, 7)
         edges = d_edges.download(capi.PGO_EDGE_DTYPE, n)

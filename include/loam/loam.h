@@ -1,5 +1,6 @@
 /** @brief Convenience header including the whole loam API (MI355X back end). */
 #pragma once
+#include "cloudmap.h"
 #include "common.h"
 #include "features.h"
 #include "geometry.h"

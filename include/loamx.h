@@ -253,6 +253,7 @@ int loamx_ctx_last_assoc_census(loamx_ctx* ctx, int which_kind, loamx_assoc_cens
  *   host streaming: STREAM_CHUNK_PAIRS (a number: pairs per uploaded chunk of loamx_register_scan_pairs / _scan_sequence; 0 = default, 128)
  *   multi-GPU:     FORCE_RCCL (a one-rank communicator really enqueues the RCCL collectives)
  *   input checks:  CHECK_FINITE (see "Non-finite input" below)
+ *   cloud map:     NO_CLOUDMAP_COMBINE (one claim per point instead of one per run of a wavefront: the same bytes, see "cloud map")
  * Unknown name: LOAMX_ERR_BAD_PARAM.
  *
  * Non-finite input. The reference is undefined on NaN / Inf coordinates (loam/include/loam/features-inl.h:38 sorts on
@@ -899,6 +900,93 @@ int loamx_pose_graph_linearize(loamx_ctx* ctx, const double* poses, size_t n_pos
 int loamx_pose_graph_edges_from_results_dev(loamx_ctx* ctx, const loamx_reg_result* d_results, const loamx_reg_information* d_info,
                                             size_t n_pairs, uint32_t first_id, loamx_pgo_edge* d_edges);
 
+/* ---- cloud map (no reference counterpart). What a mapper exists to produce: all points of all scans at their poses, thinned on
+ * a voxel grid to ONE CENTROID PER VOXEL (PCL's VoxelGrid), held on the device, and rebuilt from corrected poses in one call
+ * after a pose-graph solve without the poses leaving the device. The sums are taken in integers, so every schedule, every split
+ * over workgroups and every partial combine gives the same bytes; a numpy model is compared by equality (tests/cloudmap_common.py).
+ * FP64 throughout, every product, quotient, sum and difference rounded on its own; float input is widened first.
+ *
+ * Per point p of cloud c (loam_amd/csrc/cloudmap_math.h):
+ *   validity   dropped and counted `invalid` if a coordinate or r2 = x x + y y + z z is not finite; dropped and counted `range`
+ *              if !(r2 >= min_range^2) || !(r2 <= max_range^2) (the squares are formed once on the host; min_range > 0 removes
+ *              the all-zero cells of an organised scan).
+ *   transform  p' = pose_c.act(p) (Pose3d::act; the quaternion is used as given), pose_c read from DEVICE memory: n_clouds x 7
+ *              doubles as loamx_compose_trajectory_dev and loamx_pose_graph_optimize_dev leave them. No pose array: p' = p.
+ *   voxel      per axis t = p'[a] / leaf (an IEEE division), v = floor(t); |v| < 2^20 as in "map upkeep", otherwise the point is
+ *              dropped and counted `outside`; key as there.
+ *   offset     frac = t - v (one rounded subtraction: t = -1e-20 gives exactly 1.0), u = min((uint64) floor(frac 2^32), 2^32 - 1).
+ *   voxel sums sum[a] += u[a] (uint64), count += 1 (uint32), first = min(first, g) with g the point's running index: the
+ *              points offered to the map before this call plus its index in the call's array counted from cloud_offsets[0].
+ *              Dropped points keep their index. At most 2^32 - 2 points may be offered between two clears, so neither a count
+ *              nor a sum can wrap.
+ *   centroid   c[a] = ((double) v + ((double) sum[a] / (double) count) / 4294967296.0) leaf.
+ * Voxel order. The voxels of a map are listed by ascending `first`: in order of first appearance across all calls since the
+ *   last clear. The order is kept as data (a list of table slots, appended to by every add); it is not obtained by sorting and
+ *   does not depend on which slot a voxel won.
+ * Storage. A table of 2^k >= 2 max_voxels slots (key, first, three sums and count: 40 B each), the list of max_voxels words, a
+ *   few counters and the scratch of one round of launches (21 MB), all allocated at create and never grown: add, emit and
+ *   clear never synchronise.
+ * Overflow. `overflow` counts the points whose probe gave up after 2^k slots (they went into no voxel) plus ONE per new voxel
+ *   that did not fit the list, for the point that opened it (such a voxel keeps taking sums, its points count as used, and it
+ *   is never emitted). No launch spins or writes out of bounds.
+ *   FROM THE FIRST OVERFLOW UNTIL THE NEXT CLEAR the map promises only that every call returns and that the stats say so:
+ *   which voxels it lists, and in which order, is then unspecified. */
+typedef struct {
+  double leaf;      /* 0.2 */
+  double min_range; /* 0.5 */
+  double max_range; /* 120.0 */
+} loamx_cloud_map_params;
+typedef struct {
+  uint64_t voxels;         /* voxels in the list */
+  uint64_t points_offered; /* since the last clear, dropped ones included */
+  uint64_t points_used;    /* points that went into a voxel's sums */
+  uint64_t invalid, range, outside;
+  uint64_t overflow;
+} loamx_cloud_map_stats;
+/* A map belongs to the context it was created on: every other entry point refuses it on another context (LOAMX_ERR_BAD_PARAM).
+ * The scratch of an add and of an emit lives in the map (so emit, which leaves the voxels alone, still writes to the handle's
+ * device memory), and the context's mutex and stream put its uses in order: calls from several threads are safe, and two emits
+ * or an add and an emit never overlap on the device. */
+typedef struct loamx_cloud_map loamx_cloud_map;
+void loamx_default_cloud_map_params(loamx_cloud_map_params* p);
+/* LOAMX_ERR_BAD_PARAM: a null argument, leaf not finite or <= 0, a negative or non-finite min_range, max_range < min_range (or
+ * NaN), max_voxels == 0; LOAMX_ERR_UNSUPPORTED: max_voxels > 2^30. */
+int loamx_cloud_map_create(loamx_ctx* ctx, const loamx_cloud_map_params* params, size_t max_voxels, loamx_cloud_map** out);
+void loamx_cloud_map_destroy(loamx_ctx* ctx, loamx_cloud_map* map);
+/* an empty map again, running index 0. Asynchronous on the context's stream. */
+int loamx_cloud_map_clear(loamx_ctx* ctx, loamx_cloud_map* map);
+/* n_clouds device-resident clouds back to back: cloud c holds the points cloud_offsets[c] .. cloud_offsets[c + 1] - 1 of d_points,
+ * point_stride scalars apart (the conventions of loamx_organize_clouds_dev: cloud_offsets is a HOST array of n_clouds + 1
+ * entries, an organised scan is a cloud of H W points, a cloud may be empty). d_poses: DEVICE, n_clouds x 7, or NULL = no
+ * transform. Asynchronous, no host round trip: it composes behind loamx_pose_graph_optimize_dev without a synchronise.
+ * LOAMX_ERR_BAD_PARAM: a null map, cloud_offsets or d_points (with points), point_stride < 3, descending offsets;
+ * LOAMX_ERR_UNSUPPORTED: more than 2^32 - 2 points offered since the last clear with this call's, a point_stride beyond 32 bits.
+ * A refused call changes nothing. n_clouds == 0: LOAMX_OK. */
+int loamx_cloud_map_add_clouds_dev(loamx_ctx* ctx, loamx_cloud_map* map, const double* d_points, size_t point_stride,
+                                   const size_t* cloud_offsets, size_t n_clouds, const double* d_poses);
+int loamx_cloud_map_add_clouds_dev_f32(loamx_ctx* ctx, loamx_cloud_map* map, const float* d_points, size_t point_stride,
+                                       const size_t* cloud_offsets, size_t n_clouds, const double* d_poses);
+/* The centroids of the voxels with count >= min_points, in list order, to DEVICE memory: d_xyz_out (capacity x 3), d_count_out and
+ * d_first_out (capacity each; either may be NULL). At most `capacity` are written; *d_n_out is the number that qualify even
+ * when it exceeds capacity. Every entry below min(n, capacity) of each non-null output is written and nothing beyond. The map
+ * is not changed. Asynchronous. LOAMX_ERR_BAD_PARAM: a null map or d_n_out, a null d_xyz_out with capacity > 0. */
+int loamx_cloud_map_emit_dev(loamx_ctx* ctx, const loamx_cloud_map* map, uint32_t min_points, double* d_xyz_out, uint32_t* d_count_out,
+                             uint32_t* d_first_out, size_t capacity, uint32_t* d_n_out);
+/* synchronises */
+int loamx_cloud_map_stats_read(loamx_ctx* ctx, const loamx_cloud_map* map, loamx_cloud_map_stats* out);
+/* Measurement read-out: the claims since the last clear, that is, how often the accumulate kernel began a probe (one 64-bit
+ * CAS, more when the probe walks) followed by its five atomics: once per used point in the plain form, once per run of a
+ * wavefront with run combining. Changes nothing; synchronises. */
+int loamx_cloud_map_claims_read(loamx_ctx* ctx, const loamx_cloud_map* map, uint64_t* claims);
+/* host forms, synchronous: one cloud in host memory with a HOST pose (NULL = no transform); the emit to host arrays, *n_out the
+ * number that qualify */
+int loamx_cloud_map_add_cloud(loamx_ctx* ctx, loamx_cloud_map* map, const double* points, size_t point_stride, size_t n_points,
+                              const double pose[7]);
+int loamx_cloud_map_add_cloud_f32(loamx_ctx* ctx, loamx_cloud_map* map, const float* points, size_t point_stride, size_t n_points,
+                                  const double pose[7]);
+int loamx_cloud_map_emit(loamx_ctx* ctx, const loamx_cloud_map* map, uint32_t min_points, double* xyz_out, uint32_t* count_out,
+                         uint32_t* first_out, size_t capacity, size_t* n_out);
+
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are
  * independent units). One process per GPU owns a contiguous block of pair ids and runs the single-GPU entry points
@@ -957,7 +1045,11 @@ enum {
                                 (12 with float input) + (4 + 24) B per feature written. LOAMX_K_CURVATURE / _SELECT count
                                 the separate kernels, which run when the parameters rule the fused one out */
   LOAMX_K_INFORMATION = 10, /* information_kernel + information_finish_kernel: 72 B per edge + 56 B per plane slot streamed */
-  LOAMX_K_COUNT = 11
+  LOAMX_K_CLOUD_ACCUMULATE = 11,       /* cloud map: the accumulate kernel with run combining: 24 B/point read (12 with float input) */
+  LOAMX_K_CLOUD_ACCUMULATE_PLAIN = 12, /* ... and its one-point-one-claim form (context option NO_CLOUDMAP_COMBINE) */
+  LOAMX_K_CLOUD_LIST = 13,             /* cloud map: new-voxel flags, compaction and append of an add */
+  LOAMX_K_CLOUD_EMIT = 14,             /* cloud map: flags, compaction and centroid scatter of an emit */
+  LOAMX_K_COUNT = 15
 };
 typedef struct {
   uint64_t launches;

@@ -13,7 +13,7 @@ from . import build as _build
 
 OK, ERR_SCAN_SIZE, ERR_BAD_PARAM, ERR_HIP, ERR_CAPACITY, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_COMM = range(8)
 CONVERGED, MAX_ITER, INSUFFICIENT_ASSOCIATIONS = 0, 1, 2
-K_CURVATURE, K_SELECT, K_COMPACT, K_GRID, K_ASSOC, K_SWEEP, K_LM, K_MOMENT, K_KNN_PLANE, K_EXTRACT_FUSED, K_INFORMATION, K_COUNT = range(12)
+K_CURVATURE, K_SELECT, K_COMPACT, K_GRID, K_ASSOC, K_SWEEP, K_LM, K_MOMENT, K_KNN_PLANE, K_EXTRACT_FUSED, K_INFORMATION, K_CLOUD_ACCUMULATE, K_CLOUD_ACCUMULATE_PLAIN, K_CLOUD_LIST, K_CLOUD_EMIT, K_COUNT = range(16)
 
 
 class LidarParams(C.Structure):
@@ -207,6 +207,30 @@ PLACE_MATCH_DTYPE = np.dtype([("id", np.uint32), ("shift", np.uint32), ("key_dis
 PLACE_NO_ID = 0xFFFFFFFF  # id of a record without an entry (fewer eligible entries than candidates asked for)
 
 
+class CloudMapParamsStruct(C.Structure):
+    """loamx_cloud_map_params (include/loamx.h)"""
+    _fields_ = [("leaf", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double)]
+
+
+class CloudMapParams:
+    """The rule of a cloud map (loamx_cloud_map_params): voxel edge, and the range band outside which a point is dropped.
+    Anything left out takes the C ABI's default."""
+
+    def __init__(self, leaf=None, min_range=None, max_range=None):
+        d = CloudMapParamsStruct()
+        load().loamx_default_cloud_map_params(C.byref(d))
+        self.leaf = d.leaf if leaf is None else float(leaf)
+        self.min_range = d.min_range if min_range is None else float(min_range)
+        self.max_range = d.max_range if max_range is None else float(max_range)
+
+    def struct(self):
+        return CloudMapParamsStruct(float(self.leaf), float(self.min_range), float(self.max_range))
+
+
+# loamx_cloud_map_stats
+CLOUD_MAP_STATS_DTYPE = np.dtype([(n, np.uint64) for n in ("voxels", "points_offered", "points_used", "invalid", "range", "outside", "overflow")])
+
+
 class PgoParamsStruct(C.Structure):
     """loamx_pgo_params (include/loamx.h)"""
     _fields_ = [("max_iterations", C.c_uint32), ("max_pcg_iterations", C.c_uint32), ("pcg_tolerance", C.c_double),
@@ -279,6 +303,9 @@ EXPORTS = [
     "loamx_place_search_dev", "loamx_place_descriptor", "loamx_place_descriptor_f32", "loamx_place_search",
     "loamx_pgo_default_params", "loamx_pose_graph_optimize_dev", "loamx_pose_graph_optimize", "loamx_pose_graph_linearize",
     "loamx_pose_graph_edges_from_results_dev",
+    "loamx_default_cloud_map_params", "loamx_cloud_map_create", "loamx_cloud_map_destroy", "loamx_cloud_map_clear",
+    "loamx_cloud_map_add_clouds_dev", "loamx_cloud_map_add_clouds_dev_f32", "loamx_cloud_map_emit_dev", "loamx_cloud_map_stats_read",
+    "loamx_cloud_map_add_cloud", "loamx_cloud_map_add_cloud_f32", "loamx_cloud_map_emit", "loamx_cloud_map_claims_read",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -517,6 +544,20 @@ def load(build_if_missing=True):
     lib.loamx_place_descriptor.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.loamx_place_descriptor_f32.argtypes = lib.loamx_place_descriptor.argtypes
     lib.loamx_place_search.argtypes = lib.loamx_place_search_dev.argtypes
+    lib.loamx_default_cloud_map_params.argtypes = [C.POINTER(CloudMapParamsStruct)]
+    lib.loamx_default_cloud_map_params.restype = None
+    lib.loamx_cloud_map_create.argtypes = [vp, C.POINTER(CloudMapParamsStruct), C.c_size_t, C.POINTER(vp)]
+    lib.loamx_cloud_map_destroy.argtypes = [vp, vp]
+    lib.loamx_cloud_map_destroy.restype = None
+    lib.loamx_cloud_map_clear.argtypes = [vp, vp]
+    lib.loamx_cloud_map_add_clouds_dev.argtypes = [vp, vp, vp, C.c_size_t, szp, C.c_size_t, vp]
+    lib.loamx_cloud_map_add_clouds_dev_f32.argtypes = lib.loamx_cloud_map_add_clouds_dev.argtypes
+    lib.loamx_cloud_map_emit_dev.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, C.c_size_t, vp]
+    lib.loamx_cloud_map_stats_read.argtypes = [vp, vp, vp]
+    lib.loamx_cloud_map_claims_read.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
+    lib.loamx_cloud_map_add_cloud.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
+    lib.loamx_cloud_map_add_cloud_f32.argtypes = lib.loamx_cloud_map_add_cloud.argtypes
+    lib.loamx_cloud_map_emit.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, C.c_size_t, szp]
     lib.loamx_pgo_default_params.argtypes = [C.POINTER(PgoParamsStruct)]
     lib.loamx_pgo_default_params.restype = None
     lib.loamx_pose_graph_optimize_dev.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(PgoParamsStruct), vp]
@@ -800,6 +841,104 @@ class PlaceDb:
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):
                 self.ctx.lib.loamx_place_db_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CloudMap:
+    """A cloud map (loamx_cloud_map; include/loamx.h, "cloud map"): posed clouds accumulated on a voxel grid as integer sums, one
+    centroid per voxel, the voxels in order of first appearance; on the context's device. close() frees it; the context must
+    still be open."""
+
+    def __init__(self, ctx, params=None, max_voxels=1 << 20):
+        self.ctx, self.params = ctx, params or CloudMapParams()
+        max_voxels = int(max_voxels)
+        if max_voxels < 0:
+            raise ValueError("cloud_map: max_voxels is negative")
+        st = self.params.struct()
+        h = C.c_void_p()
+        ctx._check(ctx.lib.loamx_cloud_map_create(ctx.h, C.byref(st), max_voxels, C.byref(h)))
+        self.h, self.max_voxels = h, max_voxels
+
+    def _handle(self):
+        if not getattr(self, "h", None):
+            raise ValueError("the cloud map is closed")
+        return self.h
+
+    def clear(self):
+        """an empty map again (loamx_cloud_map_clear). Asynchronous."""
+        self.ctx._check(self.ctx.lib.loamx_cloud_map_clear(self.ctx.h, self._handle()))
+
+    def add_clouds_dev(self, d_points, point_stride, cloud_offsets, d_poses=0, f32=False):
+        """len(cloud_offsets) - 1 device-resident clouds back to back, cloud c at the pose d_poses[c] (a device address of
+        n_clouds x 7 doubles, or 0 = no transform) (loamx_cloud_map_add_clouds_dev[_f32]). Asynchronous."""
+        off = _offsets(cloud_offsets, "add_clouds_dev")
+        if int(point_stride) < 0:
+            raise ValueError("add_clouds_dev: point_stride is negative")
+        fn = self.ctx.lib.loamx_cloud_map_add_clouds_dev_f32 if f32 else self.ctx.lib.loamx_cloud_map_add_clouds_dev
+        self.ctx._check(fn(self.ctx.h, self._handle(), d_points or None, int(point_stride), off.ctypes.data_as(C.POINTER(C.c_size_t)),
+                           off.size - 1, d_poses or None))
+
+    def add_cloud(self, points, pose=None):
+        """One cloud (or organised scan) in host memory, (n, k >= 3) float64 / float32, at a host pose7 or None (no transform)."""
+        pts = np.asarray(points)
+        if pts.dtype != np.float32:
+            pts = np.asarray(pts, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] < 3:
+            raise ValueError(f"add_cloud: points must be (n, 3) or (n, k >= 3), not {pts.shape}")
+        pts = np.ascontiguousarray(pts)
+        p = None
+        if pose is not None:
+            p = np.ascontiguousarray(pose, dtype=np.float64)
+            if p.shape != (7,):
+                raise ValueError(f"add_cloud: a pose is 7 numbers (qx qy qz qw tx ty tz), not {p.shape}")
+        fn = self.ctx.lib.loamx_cloud_map_add_cloud_f32 if pts.dtype == np.float32 else self.ctx.lib.loamx_cloud_map_add_cloud
+        self.ctx._check(fn(self.ctx.h, self._handle(), pts.ctypes.data, pts.shape[1], pts.shape[0], None if p is None else p.ctypes.data))
+
+    def emit_dev(self, d_xyz_out, capacity, d_n_out, min_points=1, d_count_out=0, d_first_out=0):
+        """the centroids of the voxels with count >= min_points in list order, at most `capacity`, to device addresses; the
+        number that qualify to d_n_out (loamx_cloud_map_emit_dev). Asynchronous."""
+        if int(capacity) < 0 or not 0 <= int(min_points) <= 0xFFFFFFFF:
+            raise ValueError("emit_dev: capacity is negative or min_points does not fit 32 bits")
+        self.ctx._check(self.ctx.lib.loamx_cloud_map_emit_dev(self.ctx.h, self._handle(), int(min_points), d_xyz_out or None, d_count_out or None,
+                                                              d_first_out or None, int(capacity), d_n_out or None))
+
+    def emit(self, min_points=1, capacity=None):
+        """(xyz (m, 3) float64, count (m,) uint32, first (m,) uint32, n): m = min(n, capacity) voxels in list order, n the
+        number that qualify; capacity None: room for every voxel the map can hold."""
+        capacity = self.max_voxels if capacity is None else int(capacity)
+        if capacity < 0 or not 0 <= int(min_points) <= 0xFFFFFFFF:
+            raise ValueError("emit: capacity is negative or min_points does not fit 32 bits")
+        room = min(capacity, self.max_voxels)
+        xyz, cnt, first = np.empty((room, 3)), np.empty(room, dtype=np.uint32), np.empty(room, dtype=np.uint32)
+        n = C.c_size_t(0)
+        self.ctx._check(self.ctx.lib.loamx_cloud_map_emit(self.ctx.h, self._handle(), int(min_points), xyz.ctypes.data, cnt.ctypes.data,
+                                                          first.ctypes.data, room, C.byref(n)))
+        m = min(n.value, room)
+        return xyz[:m], cnt[:m], first[:m], n.value
+
+    def stats(self):
+        """one CLOUD_MAP_STATS_DTYPE record (loamx_cloud_map_stats_read; synchronises)"""
+        st = np.zeros(1, dtype=CLOUD_MAP_STATS_DTYPE)
+        self.ctx._check(self.ctx.lib.loamx_cloud_map_stats_read(self.ctx.h, self._handle(), st.ctypes.data))
+        return st[0]
+
+    def claims(self):
+        """probes begun by the accumulate kernel since the last clear: one per used point in the plain form, one per run of a
+        wavefront with run combining (loamx_cloud_map_claims_read; synchronises)"""
+        n = C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.loamx_cloud_map_claims_read(self.ctx.h, self._handle(), C.byref(n)))
+        return n.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.ctx.lib.loamx_cloud_map_destroy(self.ctx.h, self.h)
             self.h = None
 
     def __del__(self):
@@ -1383,6 +1522,10 @@ class Context:
     # ---- place recognition (include/loamx.h, "place recognition") --------------------------------------------
     def place_db(self, params=None):
         return PlaceDb(self, params)
+
+    # ---- cloud map (include/loamx.h, "cloud map") ---------------------------------------------------------------
+    def cloud_map(self, params=None, max_voxels=1 << 20):
+        return CloudMap(self, params, max_voxels)
 
     @staticmethod
     def _pgo_params(params):

@@ -1,0 +1,295 @@
+// api_cloudmap.hip — the cloud map (loamx.h, "cloud map"): the map handle with its one device block (table, voxel list, counters,
+// the scratch of a round of launches), the add, emit, clear and stats entry points and their host forms.
+#include "api_host.h"
+#include "cloudmap_math.h"
+
+struct loamx_cloud_map {
+  loamx_ctx* owner = nullptr;  // the context it was created on: its mutex and stream order every use of the scratch below
+  int device = 0;
+  loamx_cloud_map_params params = {};
+  loamx::CloudRule rule = {};
+  loamx::CloudTable t = {};
+  void* block = nullptr;
+  size_t ones_bytes = 0;    // keys + first, at the block's start: 0xFF bytes in an empty map
+  size_t zeros_bytes = 0;   // sums, count, counters and lengths behind them: zero bytes in an empty map
+  uint32_t* d_slot = nullptr;   // scratch of a round of an add: [kCloudChunkPoints]
+  uint8_t* d_keep = nullptr;    // [max(kCloudChunkPoints, max_voxels)] (add and emit)
+  uint32_t* d_tiles = nullptr;  // the compaction's tiles for as many
+  uint64_t offered = 0;         // points offered since the last clear (the host's copy is the running index of the next call)
+};
+
+using namespace loamx;
+
+namespace {
+
+constexpr size_t kCloudMaxVoxels = (size_t)1 << 30;
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int map_check(loamx_ctx* ctx, const loamx_cloud_map* map) {
+  if (!map) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null cloud map");
+  if (map->owner != ctx) return fail(ctx, LOAMX_ERR_BAD_PARAM, "the cloud map was created on another context");
+  return LOAMX_OK;
+}
+
+int clear_locked(loamx_ctx* ctx, loamx_cloud_map* map) {
+  untimed(ctx);
+  HIP_TRY(ctx, hipMemsetAsync(map->block, 0xFF, map->ones_bytes, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(static_cast<char*>(map->block) + map->ones_bytes, 0, map->zeros_bytes, ctx->stream));
+  map->offered = 0;
+  return LOAMX_OK;
+}
+
+// the argument checks the device and the host forms of an add share; *total: the points of the call
+int add_check(loamx_ctx* ctx, const loamx_cloud_map* map, const void* points, size_t stride, const size_t* offsets, size_t n_clouds, size_t* total) {
+  int rc = map_check(ctx, map);
+  if (rc != LOAMX_OK) return rc;
+  *total = 0;
+  if (stride < 3) return fail(ctx, LOAMX_ERR_BAD_PARAM, "point_stride must be >= 3");
+  if (stride > 0xFFFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "point_stride does not fit 32 bits");
+  if (n_clouds == 0) return LOAMX_OK;
+  if (!offsets) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null cloud_offsets");
+  for (size_t c = 0; c < n_clouds; c++)
+    if (offsets[c + 1] < offsets[c]) return fail(ctx, LOAMX_ERR_BAD_PARAM, "cloud_offsets must ascend");
+  *total = offsets[n_clouds] - offsets[0];
+  if (*total && !points) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null points");
+  if (*total > kCloudMaxOffered || map->offered + *total > kCloudMaxOffered)
+    return fail(ctx, LOAMX_ERR_UNSUPPORTED, "a cloud map takes at most 2^32 - 2 points between two clears");
+  return LOAMX_OK;
+}
+
+// the clouds of the call, kOrgChunkClouds at a time (their offsets travel as a kernel argument), their points in rounds of
+// kCloudChunkPoints (the caller holds ctx->mu, has selected the device and checked the arguments)
+int add_locked(loamx_ctx* ctx, loamx_cloud_map* map, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
+               const double* d_poses) {
+  const bool combine = !(ctx->reg_flags & kRegFlagNoCloudmapCombine);
+  const double point_bytes = f32 ? 12.0 : 24.0;
+  for (size_t c0 = 0; c0 < n_clouds; c0 += kOrgChunkClouds) {
+    const uint32_t nc = (uint32_t)(n_clouds - c0 < kOrgChunkClouds ? n_clouds - c0 : kOrgChunkClouds);
+    OrgOffsets offs;
+    for (uint32_t c = 0; c <= kOrgChunkClouds; c++) offs.off[c] = offsets[c0 + (c < nc ? c : nc)];
+    for (unsigned long long p0 = offs.off[0]; p0 < offs.off[nc]; p0 += kCloudChunkPoints) {
+      const uint32_t n = (uint32_t)(offs.off[nc] - p0 < kCloudChunkPoints ? offs.off[nc] - p0 : kCloudChunkPoints);
+      const uint32_t g0 = (uint32_t)(map->offered + (p0 - offsets[0]));
+      {
+        TimedScope timed(ctx, combine ? LOAMX_K_CLOUD_ACCUMULATE : LOAMX_K_CLOUD_ACCUMULATE_PLAIN, point_bytes * n, true);
+        launch_cloud_accumulate(d_points, f32, (uint32_t)stride, offs, nc, p0, n, g0, d_poses ? d_poses + c0 * 7 : nullptr, map->rule, map->t, combine,
+                                map->d_slot, ctx->stream);
+      }
+      {
+        TimedScope timed(ctx, LOAMX_K_CLOUD_LIST, 5.0 * n, true);
+        launch_cloud_list(map->t, map->d_slot, n, g0, map->d_keep, map->d_tiles, ctx->stream);
+      }
+      CHECK_LAUNCH(ctx, "cloud map add kernels");
+    }
+  }
+  map->offered += offsets[n_clouds] - offsets[0];
+  return LOAMX_OK;
+}
+
+int add_dev(loamx_ctx* ctx, loamx_cloud_map* map, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
+            const double* d_poses) {
+  API_ENTER(ctx);
+  size_t total = 0;
+  int rc = add_check(ctx, map, d_points, stride, offsets, n_clouds, &total);
+  if (rc != LOAMX_OK || total == 0) return rc;
+  return add_locked(ctx, map, d_points, f32, stride, offsets, n_clouds, d_poses);
+}
+
+int add_host(loamx_ctx* ctx, loamx_cloud_map* map, const void* points, bool f32, size_t stride, size_t n, const double* pose) {
+  API_ENTER(ctx);
+  const size_t offsets[2] = {0, n};
+  size_t total = 0;
+  int rc = add_check(ctx, map, points, stride, offsets, 1, &total);
+  if (rc != LOAMX_OK || total == 0) return rc;
+  if (n > (~(size_t)0) / (stride * sizeof(double))) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "the cloud does not fit the address space");
+  const size_t in_bytes = n * stride * (f32 ? sizeof(float) : sizeof(double));
+  untimed(ctx);
+  ENSURE(ctx, WS_CLOUD_IN, in_bytes);
+  ENSURE(ctx, WS_CLOUD_POSE, 7 * sizeof(double));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_CLOUD_IN].p, points, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (pose) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_CLOUD_POSE].p, pose, 7 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  rc = add_locked(ctx, map, ctx->ws[WS_CLOUD_IN].p, f32, stride, offsets, 1, pose ? wsp<double>(ctx, WS_CLOUD_POSE) : nullptr);
+  if (rc != LOAMX_OK) {
+    (void)hipStreamSynchronize(ctx->stream);  // (the upload must not outlive the caller's array)
+    return rc;
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return LOAMX_OK;
+}
+
+int emit_check(loamx_ctx* ctx, const loamx_cloud_map* map, const void* xyz, size_t capacity, const void* n_out) {
+  int rc = map_check(ctx, map);
+  if (rc != LOAMX_OK) return rc;
+  if (!n_out || (capacity && !xyz)) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  return LOAMX_OK;
+}
+
+int emit_locked(loamx_ctx* ctx, const loamx_cloud_map* map, uint32_t min_points, double* d_xyz, uint32_t* d_count, uint32_t* d_first, size_t capacity,
+                uint32_t* d_n_out) {
+  TimedScope timed(ctx, LOAMX_K_CLOUD_EMIT, 0.0, true);
+  launch_cloud_emit(map->t, map->rule.leaf, min_points, map->d_keep, map->d_tiles, d_xyz, d_count, d_first, capacity, d_n_out, ctx->stream);
+  CHECK_LAUNCH(ctx, "cloud map emit kernels");
+  return LOAMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void loamx_default_cloud_map_params(loamx_cloud_map_params* p) {
+  if (!p) return;
+  p->leaf = 0.2, p->min_range = 0.5, p->max_range = 120.0;
+}
+
+int loamx_cloud_map_create(loamx_ctx* ctx, const loamx_cloud_map_params* params, size_t max_voxels, loamx_cloud_map** out) {
+  API_ENTER(ctx);
+  if (!params || !out) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  *out = nullptr;
+  if (!isfinite(params->leaf) || !(params->leaf > 0.0)) return fail(ctx, LOAMX_ERR_BAD_PARAM, "leaf must be finite and positive");
+  if (!isfinite(params->min_range) || params->min_range < 0.0) return fail(ctx, LOAMX_ERR_BAD_PARAM, "min_range must be finite and not negative");
+  if (!(params->max_range >= params->min_range)) return fail(ctx, LOAMX_ERR_BAD_PARAM, "max_range must be at least min_range");
+  if (max_voxels == 0) return fail(ctx, LOAMX_ERR_BAD_PARAM, "max_voxels must be >= 1");
+  if (max_voxels > kCloudMaxVoxels) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "max_voxels > 2^30 not supported");
+  loamx_cloud_map* map = new loamx_cloud_map;
+  map->owner = ctx, map->device = ctx->device;
+  map->params = *params;
+  map->rule.leaf = params->leaf;
+  map->rule.min_r2 = params->min_range * params->min_range, map->rule.max_r2 = params->max_range * params->max_range;
+  uint32_t log2_cap = 4;  // (voxel_hash takes 4 .. 32 bits)
+  while (((size_t)1 << log2_cap) < 2 * max_voxels) log2_cap++;
+  const size_t cap = (size_t)1 << log2_cap, scratch = max_voxels > kCloudChunkPoints ? max_voxels : kCloudChunkPoints;
+  const size_t o_keys = 0, o_first = o_keys + align256(cap * sizeof(unsigned long long));
+  const size_t o_sums = o_first + align256(cap * sizeof(uint32_t)), o_count = o_sums + align256(cap * 3 * sizeof(unsigned long long));
+  const size_t o_words = o_count + align256(cap * sizeof(uint32_t)), o_lens = o_words + align256(kCloudWords * sizeof(unsigned long long));
+  const size_t o_list = o_lens + align256(kCloudLens * sizeof(uint32_t)), o_slot = o_list + align256(max_voxels * sizeof(uint32_t));
+  const size_t o_keep = o_slot + align256((size_t)kCloudChunkPoints * sizeof(uint32_t)), o_tiles = o_keep + align256(scratch);
+  const size_t bytes = o_tiles + align256(map_compact_ws_bytes(scratch));
+  hipError_t e = hipMalloc(&map->block, bytes);
+  if (e != hipSuccess) {
+    delete map;
+    return fail(ctx, LOAMX_ERR_HIP, std::string("cloud map storage: ") + hipGetErrorString(e));
+  }
+  char* b = static_cast<char*>(map->block);
+  map->ones_bytes = o_sums, map->zeros_bytes = o_list - o_sums;
+  map->t.keys = reinterpret_cast<unsigned long long*>(b + o_keys), map->t.first = reinterpret_cast<uint32_t*>(b + o_first);
+  map->t.sums = reinterpret_cast<unsigned long long*>(b + o_sums), map->t.count = reinterpret_cast<uint32_t*>(b + o_count);
+  map->t.words = reinterpret_cast<unsigned long long*>(b + o_words), map->t.lens = reinterpret_cast<uint32_t*>(b + o_lens);
+  map->t.list = reinterpret_cast<uint32_t*>(b + o_list);
+  map->t.log2_cap = log2_cap, map->t.max_voxels = (uint32_t)max_voxels;
+  map->d_slot = reinterpret_cast<uint32_t*>(b + o_slot), map->d_keep = reinterpret_cast<uint8_t*>(b + o_keep);
+  map->d_tiles = reinterpret_cast<uint32_t*>(b + o_tiles);
+  int rc = clear_locked(ctx, map);
+  if (rc != LOAMX_OK) {
+    (void)hipFree(map->block);
+    delete map;
+    return rc;
+  }
+  *out = map;
+  return LOAMX_OK;
+}
+
+void loamx_cloud_map_destroy(loamx_ctx* ctx, loamx_cloud_map* map) {
+  if (!map) return;
+  if (ctx) {
+    std::lock_guard<std::mutex> guard(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);  // (kernels still working on the map)
+    if (map->block) (void)hipFree(map->block);
+    delete map;
+    return;
+  }
+  if (map->block) (void)hipFree(map->block);
+  delete map;
+}
+
+int loamx_cloud_map_clear(loamx_ctx* ctx, loamx_cloud_map* map) {
+  API_ENTER(ctx);
+  int rc = map_check(ctx, map);
+  if (rc != LOAMX_OK) return rc;
+  return clear_locked(ctx, map);
+}
+
+int loamx_cloud_map_add_clouds_dev(loamx_ctx* ctx, loamx_cloud_map* map, const double* d_points, size_t point_stride, const size_t* cloud_offsets,
+                                   size_t n_clouds, const double* d_poses) {
+  return add_dev(ctx, map, d_points, false, point_stride, cloud_offsets, n_clouds, d_poses);
+}
+int loamx_cloud_map_add_clouds_dev_f32(loamx_ctx* ctx, loamx_cloud_map* map, const float* d_points, size_t point_stride, const size_t* cloud_offsets,
+                                       size_t n_clouds, const double* d_poses) {
+  return add_dev(ctx, map, d_points, true, point_stride, cloud_offsets, n_clouds, d_poses);
+}
+int loamx_cloud_map_add_cloud(loamx_ctx* ctx, loamx_cloud_map* map, const double* points, size_t point_stride, size_t n_points, const double pose[7]) {
+  return add_host(ctx, map, points, false, point_stride, n_points, pose);
+}
+int loamx_cloud_map_add_cloud_f32(loamx_ctx* ctx, loamx_cloud_map* map, const float* points, size_t point_stride, size_t n_points,
+                                  const double pose[7]) {
+  return add_host(ctx, map, points, true, point_stride, n_points, pose);
+}
+
+int loamx_cloud_map_emit_dev(loamx_ctx* ctx, const loamx_cloud_map* map, uint32_t min_points, double* d_xyz_out, uint32_t* d_count_out,
+                             uint32_t* d_first_out, size_t capacity, uint32_t* d_n_out) {
+  API_ENTER(ctx);
+  int rc = emit_check(ctx, map, d_xyz_out, capacity, d_n_out);
+  if (rc != LOAMX_OK) return rc;
+  return emit_locked(ctx, map, min_points, d_xyz_out, d_count_out, d_first_out, capacity, d_n_out);
+}
+
+int loamx_cloud_map_emit(loamx_ctx* ctx, const loamx_cloud_map* map, uint32_t min_points, double* xyz_out, uint32_t* count_out, uint32_t* first_out,
+                         size_t capacity, size_t* n_out) {
+  API_ENTER(ctx);
+  int rc = emit_check(ctx, map, xyz_out, capacity, n_out);
+  if (rc != LOAMX_OK) return rc;
+  if (capacity > map->t.max_voxels) capacity = map->t.max_voxels;  // (no more can qualify)
+  const size_t o_count = align256(capacity * 3 * sizeof(double)), o_first = o_count + align256(capacity * sizeof(uint32_t));
+  const size_t o_n = o_first + align256(capacity * sizeof(uint32_t));
+  untimed(ctx);
+  ENSURE(ctx, WS_CLOUD_OUT, o_n + 256);
+  char* b = static_cast<char*>(ctx->ws[WS_CLOUD_OUT].p);
+  rc = emit_locked(ctx, map, min_points, reinterpret_cast<double*>(b), reinterpret_cast<uint32_t*>(b + o_count), reinterpret_cast<uint32_t*>(b + o_first),
+                   capacity, reinterpret_cast<uint32_t*>(b + o_n));
+  if (rc != LOAMX_OK) return rc;
+  untimed(ctx);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, b + o_n, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t n = ctx->h_pinned[0], m = n < capacity ? n : capacity;
+  if (m) {
+    HIP_TRY(ctx, hipMemcpyAsync(xyz_out, b, m * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (count_out) HIP_TRY(ctx, hipMemcpyAsync(count_out, b + o_count, m * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (first_out) HIP_TRY(ctx, hipMemcpyAsync(first_out, b + o_first, m * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  *n_out = n;
+  return LOAMX_OK;
+}
+
+int loamx_cloud_map_stats_read(loamx_ctx* ctx, const loamx_cloud_map* map, loamx_cloud_map_stats* out) {
+  API_ENTER(ctx);
+  int rc = map_check(ctx, map);
+  if (rc != LOAMX_OK) return rc;
+  if (!out) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  unsigned long long words[kCloudWords];
+  uint32_t lens[kCloudLens];
+  untimed(ctx);
+  HIP_TRY(ctx, hipMemcpyAsync(words, map->t.words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(lens, map->t.lens, sizeof(lens), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  out->voxels = lens[kCloudLenListed], out->points_offered = map->offered;
+  out->points_used = words[kCloudUsed], out->invalid = words[kCloudInvalid], out->range = words[kCloudRange];
+  out->outside = words[kCloudOutside], out->overflow = words[kCloudWordOverflow];
+  return LOAMX_OK;
+}
+
+int loamx_cloud_map_claims_read(loamx_ctx* ctx, const loamx_cloud_map* map, uint64_t* claims) {
+  API_ENTER(ctx);
+  int rc = map_check(ctx, map);
+  if (rc != LOAMX_OK) return rc;
+  if (!claims) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  unsigned long long word = 0;
+  untimed(ctx);
+  HIP_TRY(ctx, hipMemcpyAsync(&word, map->t.words + kCloudWordClaims, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *claims = word;
+  return LOAMX_OK;
+}
+
+}  // extern "C"

@@ -17,7 +17,8 @@ namespace {
 const char* kKernelNames[LOAMX_K_COUNT] = {"curvature_valid_kernel", "select_kernel", "compact_kernel",
                                            "grid_build_kernel",      "associate_kernel", "sweep_kernel",
                                            "lm_kernels",             "moment_kernel",    "knn_plane_kernel",
-                                           "extract_fused_kernel",   "information_kernel"};
+                                           "extract_fused_kernel",   "information_kernel", "cloud_accumulate_kernel",
+                                           "cloud_accumulate_plain_kernel", "cloud_list_kernels", "cloud_emit_kernels"};
 
 struct OptionName {
   const char* name;
@@ -35,7 +36,7 @@ const OptionName kOptionNames[] = {
     {"NO_COOP_LEFT", false, kRegFlagNoCoopLeft}, {"NO_REF_MOMENTS", false, kRegFlagNoRefMoments},
     {"NO_EXTRACT_BOXES", false, kRegFlagNoExtractBoxes}, {"CHECK_FINITE", false, kRegFlagCheckFinite},
     {"NO_SMALL_SETS", false, kRegFlagNoSmallSets}, {"FORCE_LATE_VERIFY", false, kRegFlagForceLate},
-    {"NO_LIVE_DEAL", false, kRegFlagNoLiveDeal}};
+    {"NO_LIVE_DEAL", false, kRegFlagNoLiveDeal}, {"NO_CLOUDMAP_COMBINE", false, kRegFlagNoCloudmapCombine}};
 
 }  // namespace
 

@@ -26,6 +26,7 @@ enum WsId {
   WS_ORG_WINNER, WS_ORG_RANGE, WS_ORG_CELL, WS_ORG_COUNTS, WS_ORG_IN, WS_ORG_RINGS, WS_ORG_OUT,
   WS_PLACE_TABLE, WS_PLACE_QKEYS, WS_PLACE_QNORMS, WS_PLACE_CAND_A, WS_PLACE_CAND_B, WS_PLACE_MATCH, WS_PLACE_IN, WS_PLACE_OUT,
   WS_PGO_WORK, WS_PGO_POSES, WS_PGO_FIXED, WS_PGO_EDGES, WS_PGO_OUT,
+  WS_CLOUD_IN, WS_CLOUD_POSE, WS_CLOUD_OUT,
   WS_COUNT
 };
 // the buffers that exist once per feature kind: loamx_ctx::wsk[id][kEdge | kPlane]

@@ -506,6 +506,36 @@ size_t map_compact_ws_bytes(size_t n);
 void launch_map_compact(const double* d_in, const uint8_t* d_keep, uint32_t n, uint32_t* d_tiles, double* d_out, uint32_t* d_src_idx,
                         uint32_t* d_total, const VoxelTable* fix, const uint32_t* d_slot, uint32_t owner_base, hipStream_t s);
 
+/* ---- cloud map (cloudmap_kernels.hip; the rule: cloudmap_math.h and loamx.h) ------------------------------------------------- */
+constexpr uint32_t kCloudChunkPoints = 1u << 22;  // points per round of launches of an add (its scratch is sized for them at create)
+constexpr uint32_t kRegFlagNoCloudmapCombine = 65536u;  // (loamx_ctx::reg_flags) one claim per point, no run combining
+// counter words of a map: [kCloudUsed .. kCloudOutside] of cloudmap_math.h, then the overflow and the claims (run heads: CAS
+// chains begun); the rest pads the array to 64 bytes
+enum { kCloudWordOverflow = 4, kCloudWordClaims = 5, kCloudWords = 8 };
+// length words: voxels in the list; new voxels of the chunk in flight (the compaction's total)
+enum { kCloudLenListed = 0, kCloudLenPending = 1, kCloudLens = 4 };
+struct CloudRule {
+  double leaf, min_r2, max_r2;
+};
+// Open-addressed table as VoxelTable: 2^log2_cap slots; keys and first start as 0xFF bytes, everything else as zero bytes.
+struct CloudTable {
+  unsigned long long* keys;   // [cap] voxel key (map_math.h) or all ones (empty)
+  uint32_t* first;            // [cap] lowest running index of a point of the voxel
+  unsigned long long* sums;   // [cap][3] sums of the points' 32-bit offsets inside the voxel
+  uint32_t* count;            // [cap]
+  uint32_t log2_cap;
+  uint32_t max_voxels;
+  uint32_t* list;             // [max_voxels] slots in order of first appearance
+  unsigned long long* words;  // [kCloudWords]
+  uint32_t* lens;             // [kCloudLens]
+};
+void launch_cloud_accumulate(const void* d_points, bool f32, uint32_t stride, const OrgOffsets& offs, uint32_t n_clouds, unsigned long long p0,
+                             uint32_t n, uint32_t g0, const double* d_poses, const CloudRule& rule, const CloudTable& t, bool combine, uint32_t* d_slot,
+                             hipStream_t s);
+void launch_cloud_list(const CloudTable& t, const uint32_t* d_slot, uint32_t n, uint32_t g0, uint8_t* d_keep, uint32_t* d_tiles, hipStream_t s);
+void launch_cloud_emit(const CloudTable& t, double leaf, uint32_t min_points, uint8_t* d_keep, uint32_t* d_tiles, double* d_xyz_out,
+                       uint32_t* d_count_out, uint32_t* d_first_out, size_t capacity, uint32_t* d_n_out, hipStream_t s);
+
 /* ---- synthetic generator (synth_kernels.hip) --------------------------------------------------- */
 void launch_synth_pairs(uint64_t seed, uint64_t first_pair, size_t n_pairs, uint32_t H, uint32_t W, double sigma,
                         double* d_xyz, hipStream_t s);

@@ -2,13 +2,13 @@
 // new points against an occupancy table (loamx_voxel_filter_dev, loamx_target_index_insert_filtered), the box test of the
 // crop (loamx_target_index_crop) and the stable compaction all three share. Per-point arithmetic: map_math.h.
 #include "loamx_internal.h"
+#include "map_compact.h"
 #include "map_math.h"
 
 namespace loamx {
 namespace {
 
 constexpr int kMapThreads = (int)kMapTile;  // one point per thread, one tile per workgroup
-static_assert(kMapThreads == 256, "block_rank and tile_scan_kernel are written for four wavefronts");
 
 struct Pose7 {
   double v[7];
@@ -99,22 +99,8 @@ __global__ __launch_bounds__(kMapThreads) void map_transform_kernel(const double
  * Three launches over tiles of kMapTile points, none of which waits for another workgroup: counts of the kept points per
  * tile; ONE workgroup turns the counts into the tiles' first output positions (it walks the tiles 256 at a time with a
  * running total, so any number of tiles takes the same code) and writes the total; every tile then ranks its kept points
- * again and moves them to base[tile] + rank. Kept points therefore leave in input order. */
-__device__ __forceinline__ uint32_t block_rank(bool flag, uint32_t* s_wave, uint32_t& total) {
-  const unsigned long long b = __ballot(flag);
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  if (lane == 0) s_wave[w] = (uint32_t)__popcll(b);
-  __syncthreads();
-  uint32_t before = 0;
-  total = 0;
-  for (uint32_t j = 0; j < 4; j++) {
-    const uint32_t c = s_wave[j];
-    before += j < w ? c : 0u;
-    total += c;
-  }
-  return before + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-}
-
+ * again and moves them to base[tile] + rank. Kept points therefore leave in input order. block_rank and the launcher of the
+ * first two launches stand in map_compact.h: the cloud map (cloudmap_kernels.hip) compacts with them too. */
 __global__ __launch_bounds__(kMapThreads) void tile_count_kernel(const uint8_t* __restrict__ keep, uint32_t n, uint32_t* __restrict__ tiles) {
   __shared__ uint32_t s_wave[4];
   const uint32_t i = blockIdx.x * kMapThreads + threadIdx.x;
@@ -206,16 +192,20 @@ void launch_map_transform(const double* d_pts, uint32_t n, const double* pose, d
                 d_flags);
 }
 
+void launch_tile_offsets(const uint8_t* d_keep, uint32_t n, uint32_t* d_tiles, uint32_t* d_total, hipStream_t s) {
+  const uint32_t n_tiles = (n + kMapTile - 1) / kMapTile;
+  if (n) launch_kernel(tile_count_kernel, dim3(n_tiles), dim3(kMapThreads), 0, s, d_keep, n, d_tiles);
+  launch_kernel(tile_scan_kernel, dim3(1), dim3(kMapThreads), 0, s, d_tiles, n_tiles, d_total);
+}
+
 size_t map_compact_ws_bytes(size_t n) { return ((n + kMapTile - 1) / kMapTile + 1) * sizeof(uint32_t); }
 
 // d_out: room for n points; d_tiles: map_compact_ws_bytes(n). Writes *d_total also for n == 0.
 void launch_map_compact(const double* d_in, const uint8_t* d_keep, uint32_t n, uint32_t* d_tiles, double* d_out, uint32_t* d_src_idx,
                         uint32_t* d_total, const VoxelTable* fix, const uint32_t* d_slot, uint32_t owner_base, hipStream_t s) {
-  const uint32_t n_tiles = (n + kMapTile - 1) / kMapTile;
-  if (n) launch_kernel(tile_count_kernel, dim3(n_tiles), dim3(kMapThreads), 0, s, d_keep, n, d_tiles);
-  launch_kernel(tile_scan_kernel, dim3(1), dim3(kMapThreads), 0, s, d_tiles, n_tiles, d_total);
+  launch_tile_offsets(d_keep, n, d_tiles, d_total, s);
   if (n)
-    launch_kernel(tile_scatter_kernel, dim3(n_tiles), dim3(kMapThreads), 0, s, d_in, d_keep, n, (const uint32_t*)d_tiles, d_out, d_src_idx,
+    launch_kernel(tile_scatter_kernel, tiles_of(n), dim3(kMapThreads), 0, s, d_in, d_keep, n, (const uint32_t*)d_tiles, d_out, d_src_idx,
                   fix ? fix->owner : (uint32_t*)nullptr, d_slot, owner_base);
 }
 

@@ -7,3 +7,4 @@ from .loam_python import (FeatureExtractionParams, LidarParams, LoamFeatures, Po
 from .loam_python import deskewScan, registerScanSequence  # noqa: F401  (extensions: scan sequences)
 from .loam_python import RegistrationInformation, registrationInformation  # noqa: F401  (extension: information matrix)
 from .loam_python import PoseGraph, PoseGraphParams, PoseGraphSummary  # noqa: F401  (extension: pose graph)
+from .loam_python import CloudMap, CloudMapParams  # noqa: F401  (extension: cloud map)

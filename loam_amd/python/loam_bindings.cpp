@@ -120,6 +120,23 @@ inline loam::PlaceDescriptor place_desc_arg(const loam::PlaceDatabase& db, const
   if ((size_t)desc.size() != db.cells()) throw std::runtime_error("descriptor: expected an (n_rings, n_sectors) uint16 array");
   return loam::PlaceDescriptor(desc.data(), desc.data() + desc.size());
 }
+// CloudMap: points as for organizeCloud; the pose is world_T_sensor or None (the points are in the map frame already)
+inline int c_cloud_map_add(loamx_ctx* c, loamx_cloud_map* m, const double* p, size_t stride, size_t n, const double* pose) {
+  return loamx_cloud_map_add_cloud(c, m, p, stride, n, pose);
+}
+inline int c_cloud_map_add(loamx_ctx* c, loamx_cloud_map* m, const float* p, size_t stride, size_t n, const double* pose) {
+  return loamx_cloud_map_add_cloud_f32(c, m, p, stride, n, pose);
+}
+template <typename T>
+void cloud_map_add(loam::CloudMap& map, const py::array_t<T, py::array::c_style>& points, const std::optional<loam::Pose3d>& world_T_sensor) {
+  if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
+  double pose[7];
+  if (world_T_sensor) world_T_sensor->toArray(pose);
+  loamx_ctx* ctx = loam::gpu::defaultContext();
+  py::gil_scoped_release release;
+  loam::gpu::check(ctx, c_cloud_map_add(ctx, map.handle(), points.data(), (size_t)points.shape(1), (size_t)points.shape(0),
+                                        world_T_sensor ? pose : nullptr));
+}
 template <typename T>
 py::tuple organize_cloud(const py::array_t<T, py::array::c_style>& points, const loam::ScanLayout& layout, const std::optional<ArrRings>& rings) {
   if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
@@ -541,6 +558,40 @@ PYBIND11_MODULE(loam_python, m) {
             return d.search(place_desc_arg(d, query), num_candidates, id_end.value_or(0xFFFFFFFFu));
           },
           py::arg("query"), py::arg("num_candidates"), py::arg("id_end") = py::none());
+  // cloud map (include/loamx.h: "cloud map"): an extension like TargetIndex
+  py::class_<loam::CloudMapParams>(m, "CloudMapParams")
+      .def(py::init<>())
+      .def_readwrite("leaf", &loam::CloudMapParams::leaf)
+      .def_readwrite("min_range", &loam::CloudMapParams::min_range)
+      .def_readwrite("max_range", &loam::CloudMapParams::max_range);
+  py::class_<loam::CloudMap>(m, "CloudMap")
+      .def(py::init<const loam::CloudMapParams&, size_t>(), py::arg("params") = loam::CloudMapParams(), py::arg("max_voxels") = (size_t)1 << 20)
+      .def_property_readonly("params", &loam::CloudMap::params)
+      .def_property_readonly("max_voxels", &loam::CloudMap::maxVoxels)
+      .def("add", &cloud_map_add<float>, py::arg("points"), py::arg("world_T_sensor") = py::none())
+      .def("add", &cloud_map_add<double>, py::arg("points"), py::arg("world_T_sensor") = py::none())
+      .def("clear", &loam::CloudMap::clear)
+      .def(
+          "points",
+          [](const loam::CloudMap& map, uint32_t min_points) {
+            const loam::CloudMapPoints p = map.points(min_points);
+            py::array_t<uint32_t> counts((py::ssize_t)p.size()), first((py::ssize_t)p.size());
+            if (p.size()) {
+              std::memcpy(counts.mutable_data(), p.counts.data(), p.size() * sizeof(uint32_t));
+              std::memcpy(first.mutable_data(), p.first.data(), p.size() * sizeof(uint32_t));
+            }
+            Arr xyz(std::vector<py::ssize_t>{(py::ssize_t)p.size(), 3});
+            if (p.size()) std::memcpy(xyz.mutable_data(), p.xyz.data(), p.xyz.size() * sizeof(double));
+            return py::make_tuple(xyz, counts, first);
+          },
+          py::arg("min_points") = 1)
+      .def("stats", [](const loam::CloudMap& map) {
+        const loam::CloudMapStats s = map.stats();
+        py::dict d;
+        d["voxels"] = s.voxels, d["points_offered"] = s.points_offered, d["points_used"] = s.points_used, d["invalid"] = s.invalid;
+        d["range"] = s.range, d["outside"] = s.outside, d["overflow"] = s.overflow;
+        return d;
+      });
   py::class_<loam::PoseGraphParams>(m, "PoseGraphParams")
       .def(py::init<>())
       .def_readwrite("max_iterations", &loam::PoseGraphParams::max_iterations)
