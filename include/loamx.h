@@ -238,6 +238,10 @@ typedef struct {
   size_t late_cap;             /*     (indices in the caller's source array, in the list's order) */
 } loamx_assoc_census;
 int loamx_ctx_last_assoc_census(loamx_ctx* ctx, int which_kind, loamx_assoc_census* out);
+/* Beside the census, from the same dump and with the same lifetime: how many listed entries the cooperative leftover kernel gave
+ * a row of 16 lanes (out[0]) and how many a whole wavefront (out[1]); counted by the kernel itself where it stores an entry's
+ * result, only during an association dump. Both 0 where that kernel was not launched. */
+int loamx_ctx_last_assoc_coop_forms(loamx_ctx* ctx, int which_kind, uint32_t out[2]);
 /* Debug / measurement switches of ONE context (no reference counterpart). loamx_ctx_create reads the environment
  * variables LOAMX_<NAME> once as the defaults (set = 1); no entry point looks at the environment afterwards, and a
  * switch only ever affects the context it was set on. None changes a result beyond the order in which a pair's residual
@@ -249,7 +253,7 @@ int loamx_ctx_last_assoc_census(loamx_ctx* ctx, int which_kind, loamx_assoc_cens
  *   extraction:    FORCE_TIE_REPLAY, FORCE_SCAN_GIVEUP, CURV_V1, NO_FUSED_COMPACT, NO_MIS_SELECT, NO_ROW_SELECT, FUSED_EXTRACT,
  *                  FUSED_ROWS, NO_SPLIT_CURV, STAGE_ALWAYS
  *   registration:  NO_MOMENTS, NO_REF_MOMENTS, NO_PACKED_GRID, NO_BIG_GRID, NO_GRID_SIDE, NO_EXTRACT_BOXES, NO_SMALL_SETS, DEBUG_POISON,
- *                  QUEUE_TWO_STAGE, QUEUE_ONE_STAGE, NO_COOP_LEFT, NO_MIXED_ASSOC, FORCE_LATE_VERIFY, NO_LIVE_DEAL, MAP_CELLS_LOG2 (a number: 0 = default)
+ *                  QUEUE_TWO_STAGE, QUEUE_ONE_STAGE, NO_COOP_LEFT, NO_COOP_ROWS, NO_MIXED_ASSOC, FORCE_LATE_VERIFY, NO_LIVE_DEAL, MAP_CELLS_LOG2 (a number: 0 = default)
  *   host streaming: STREAM_CHUNK_PAIRS (a number: pairs per uploaded chunk of loamx_register_scan_pairs / _scan_sequence; 0 = default, 128)
  *   multi-GPU:     FORCE_RCCL (a one-rank communicator really enqueues the RCCL collectives)
  *   input checks:  CHECK_FINITE (see "Non-finite input" below)

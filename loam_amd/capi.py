@@ -288,6 +288,7 @@ EXPORTS = [
     "loamx_comm_info", "loamx_gather_results_dev", "loamx_comm_barrier", "loamx_comm_stats", "loamx_ctx_extract_counters",
     "loamx_ctx_set_option", "loamx_ctx_get_option", "loamx_ctx_last_extract_route", "loamx_ctx_last_solve_census",
     "loamx_ctx_last_assoc_census",
+    "loamx_ctx_last_assoc_coop_forms",
     "loamx_fit_lines", "loamx_fit_planes", "loamx_knn_search", "loamx_associate", "loamx_target_index_stats",
     "loamx_register_scan_sequence_dev", "loamx_register_scan_sequence_dev_f32", "loamx_register_scan_sequence",
     "loamx_register_scan_sequence_f32", "loamx_compose_trajectory_dev", "loamx_deskew_scans_dev", "loamx_deskew_scans_dev_f32",
@@ -510,6 +511,7 @@ def load(build_if_missing=True):
     lib.loamx_ctx_last_extract_route.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.loamx_ctx_last_solve_census.argtypes = [vp, C.c_size_t, C.POINTER(SolveCensusStruct)]
     lib.loamx_ctx_last_assoc_census.argtypes = [vp, C.c_int, C.POINTER(AssocCensusStruct)]
+    lib.loamx_ctx_last_assoc_coop_forms.argtypes = [vp, C.c_int, u32p]
     lib.loamx_registration_information.argtypes = [vp, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp,
                                                    C.POINTER(RegistrationParams), C.POINTER(RegInformation)]
     lib.loamx_registration_information_indexed.argtypes = [vp, vp, dp, C.c_size_t, dp, C.c_size_t, dp, C.POINTER(RegistrationParams),
@@ -1041,6 +1043,14 @@ class Context:
         return SolveCensus(v.iterations, v.termination, v.use_moments, v.mom_ref_on, np.array(list(v.mom_ref)), v.tiles, v.live_tiles,
                            v.edge_stride, v.planar_stride, v.n_se, v.n_sp, v.walk, v.listed_total, v.s0max, v.v2max, v.sweep_chunk,
                            v.edge_cache, v.list_cache, v.flat_cache, counts[:v.live_tiles].copy())
+
+    def last_assoc_coop_forms(self, kind):
+        """(entries a row of lanes took, entries a whole wavefront took) in the cooperative leftover kernel of the last associate()
+        on this context, as the kernel counted them (include/loamx.h: loamx_ctx_last_assoc_coop_forms)"""
+        kind = {"edge": 0, "plane": 1}.get(kind, kind)
+        out = (C.c_uint32 * 2)()
+        self._check(self.lib.loamx_ctx_last_assoc_coop_forms(self.h, kind, out))
+        return int(out[0]), int(out[1])
 
     def last_assoc_census(self, kind):
         """the route census of the last associate() on this context for one feature kind (0 / "edge", 1 / "plane"; include/loamx.h:

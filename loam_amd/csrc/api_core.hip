@@ -33,7 +33,7 @@ const OptionName kOptionNames[] = {
     {"NO_GRID_SIDE", false, kRegFlagNoGridSide}, {"DEBUG_POISON", false, kRegFlagPoison},
     {"QUEUE_TWO_STAGE", false, kRegFlagQueueTwoStage}, {"QUEUE_ONE_STAGE", false, kRegFlagQueueOneStage},
     {"NO_MIXED_ASSOC", false, kRegFlagNoMixedAssoc}, {"FORCE_RCCL", false, kRegFlagForceRccl},
-    {"NO_COOP_LEFT", false, kRegFlagNoCoopLeft}, {"NO_REF_MOMENTS", false, kRegFlagNoRefMoments},
+    {"NO_COOP_LEFT", false, kRegFlagNoCoopLeft}, {"NO_COOP_ROWS", false, kRegFlagNoCoopRows}, {"NO_REF_MOMENTS", false, kRegFlagNoRefMoments},
     {"NO_EXTRACT_BOXES", false, kRegFlagNoExtractBoxes}, {"CHECK_FINITE", false, kRegFlagCheckFinite},
     {"NO_SMALL_SETS", false, kRegFlagNoSmallSets}, {"FORCE_LATE_VERIFY", false, kRegFlagForceLate},
     {"NO_LIVE_DEAL", false, kRegFlagNoLiveDeal}, {"NO_CLOUDMAP_COMBINE", false, kRegFlagNoCloudmapCombine}};

@@ -92,6 +92,7 @@ struct loamx_ctx {
     std::vector<uint32_t> entry;  // the queue's entries: query index | reason bits
     std::vector<int32_t> after_rest, before_fit;
     std::vector<uint32_t> late;   // the late list's queries
+    uint32_t coop_forms[2] = {0, 0};  // listed entries associate_knn_coop_kernel gave a row of lanes / a whole wavefront (loamx_ctx_last_assoc_coop_forms)
   } last_assoc_census[2];
   bool last_assoc_census_valid = false;
 

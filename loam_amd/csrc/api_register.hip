@@ -303,6 +303,7 @@ int reg_dump(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, const loamx_
     c.rest_blocks = F.rest_blocks, c.coop_blocks = F.coop_blocks;
     c.origin[0] = g.ox, c.origin[1] = g.oy, c.origin[2] = g.oz, c.h = g.h, c.nx = g.nx, c.ny = g.ny, c.nz = g.nz, c.n_points = g.n_points;
     c.verified = counts[0], c.unverified = counts[1], c.queued_words = counts[2];
+    keep.coop_forms[0] = counts[5], keep.coop_forms[1] = counts[6];  // (no census field: the kernel's own count of its two forms)
     c.queued = na[2 + kind], c.listed = na[4 + kind], c.exact = counts[4], c.leftover_finished = counts[3] - counts[4], c.late = na[6 + kind];
     const uint32_t q = c.queued < K.stride ? c.queued : (uint32_t)K.stride;
     keep.entry.assign(q, 0u), keep.after_rest.assign(q, 0), keep.before_fit.assign(q, 0);
@@ -639,6 +640,15 @@ int loamx_ctx_last_assoc_census(loamx_ctx* ctx, int which_kind, loamx_assoc_cens
     if (ar) ar[t] = keep.after_rest[t];
     if (bf) bf[t] = keep.before_fit[t];
   }
+  return LOAMX_OK;
+}
+
+int loamx_ctx_last_assoc_coop_forms(loamx_ctx* ctx, int which_kind, uint32_t out[2]) {
+  if (!out) return LOAMX_ERR_BAD_PARAM;
+  API_LOCK(ctx);
+  if (which_kind != 0 && which_kind != 1) return fail(ctx, LOAMX_ERR_BAD_PARAM, "which_kind: 0 = edges, 1 = planes");
+  if (!ctx->last_assoc_census_valid) return fail(ctx, LOAMX_ERR_BAD_PARAM, "no association dump on this context to read (or another call came after it)");
+  out[0] = ctx->last_assoc_census[which_kind].coop_forms[0], out[1] = ctx->last_assoc_census[which_kind].coop_forms[1];
   return LOAMX_OK;
 }
 

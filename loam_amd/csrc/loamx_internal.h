@@ -154,6 +154,7 @@ constexpr uint32_t kRegFlagQueueTwoStage = 32u;  // queue chain: always lean 5x5
 constexpr uint32_t kRegFlagQueueOneStage = 64u;  // queue chain: always the FP64 search over all rounds in one kernel
 constexpr uint32_t kRegFlagForceRccl = 256u;     // a one-rank communicator really enqueues ncclAllGather / ncclBroadcast / ncclAllReduce (host side only)
 constexpr uint32_t kRegFlagNoCoopLeft = 512u;    // listed queue leftovers one lane per query (associate_knn_left_kernel, round 3), not one wavefront per query
+constexpr uint32_t kRegFlagNoCoopRows = 131072u;  // plain leftovers of a lean set one wavefront per query too (associate_knn_coop_kernel until round 10), not one row of lanes
 constexpr uint32_t kRegFlagNoRefMoments = 1024u;  // first ICF iteration as in round 3: five sweeps of the records, no moments
 constexpr uint32_t kRegFlagNoSmallSets = 8192u;     // edge-sized sets through grid_build_kernel like every other set
 constexpr uint32_t kRegFlagCheckFinite = 4096u;     // the "_dev" entry points look for non-finite input coordinates first (host side only)
@@ -324,7 +325,8 @@ struct AssocCensusForm {
 };
 struct AssocCensusBuf {
   uint32_t* counts;     // [8] zeroed by the caller: [0..2] verified / unverified / queued count words behind round 1,
-                        // [3] negative counts behind associate_knn_rest_kernel, [4] in front of associate_fit_queued_kernel
+                        // [3] negative counts behind associate_knn_rest_kernel, [4] in front of associate_fit_queued_kernel,
+                        // [5] / [6] listed entries associate_knn_coop_kernel gave a row of lanes / a whole wavefront
   int32_t* after_rest;  // [stride] the counts by queue position behind associate_knn_rest_kernel ...
   int32_t* before_fit;  // ... and in front of associate_fit_queued_kernel
 };

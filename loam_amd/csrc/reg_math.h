@@ -974,6 +974,270 @@ LOAMX_HD int knn_search_keyed(const GridDesc& g, const uint32_t* __restrict__ ce
 }
 
 /* ------------------------------------------------------------------------------------------------
+ * Cooperative search (round 4; by rows of lanes since round 11): L lanes share ONE query, L = 64 (the wavefront) or a row of
+ * 16 / 32 lanes, 64 / L queries per wavefront. The listed leftovers of the queue are the searches one lane cannot do well:
+ * isolated queries (the whole radius cube: 81 rows at a quarter-radius cell, nearly all empty — ~100 dependent round trips for
+ * one lane) and, against a map-sized set, queries whose 3x3x3 block holds thousands of points. The pieces of a shell are dealt
+ * out over the L lanes (both table entries of up to L pieces in flight at once), and every piece's candidates are taken L at a
+ * time, one per lane, coalesced. Each lane keeps its own FP64 keyed collector (KnnKeys: one double per candidate, distance bits
+ * + position); the k + 1 smallest keys of the L lanes are then drawn from the lanes' lists by k + 1 minima over the L lanes.
+ * That is the collector's own contract — the k + 1 smallest keys of all the candidates examined — so knn_done / knn_keys_finish
+ * decide exactly as they do for one lane. Keys are a strict total order (distance bits + position) and every skip is against a
+ * rigorous upper bound of the k-th distance: the decided list is the one-lane search's (knn_search_keyed) for every query,
+ * whatever L is and whichever lane saw which candidate (what the keys cannot decide keeps its negative count, as there).
+ * The block grows shell by shell as in the one-lane search (knn_rounds): after shell w the exact k-th key of the L lanes is
+ * tested against the faces of the visited block (knn_done); the last shell is the cube whose faces lie beyond the radius.
+ * Pieces farther than the bound (the pooled k-th key; within a shell also any lane's own k-th key) or than the radius are
+ * skipped; inside a row of cells only the cells the bound reaches.
+ * Returns kept >= 0, -1 undecided, -2 not applicable (more than kCoopMaxShell shells could be needed): the caller falls back
+ * to the one-lane search.
+ *
+ * Written over NL lanes held by the caller: 1 on the device (its own, number `lane0` of the wavefront; the others are its
+ * row's), L on the host (a plain loop over virtual lanes, lane0 = 0: tests/hostcheck_coop_rows). Only the three exchanges
+ * between lanes differ between the two: the ballot, the read of one lane's word, the minimum. On the device every loop below
+ * runs on values that are the same on all lanes of a row: a row's lanes stay together (the DPP exchanges need them to), rows of
+ * one wavefront go their own ways under its control flow, and a row without a query is not in here.
+ * ---------------------------------------------------------------------------------------------- */
+constexpr int32_t kCoopMaxShell = 64;  // shells a cooperative search may walk (a radius of 62 cells; without a radius: grids up to that size)
+
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ uint32_t row32_xor16_b32(uint32_t v) {  // v of lane (l ^ 16): ds_swizzle, bit mode, and 0x1F / or 0 / xor 0x10
+  return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);
+}
+template <int J>
+__device__ __forceinline__ double row16_xor_key(double v) {
+  return knn_key_join(row16_xor_b32<J>(knn_key_hi(v)), row16_xor_b32<J>(knn_key_lo(v)));
+}
+#endif
+
+// the lanes of the row whose flag is set, bit b = lane b of the row
+template <int L, int NL>
+LOAMX_HD uint64_t knn_row_ballot(const bool (&flag)[NL], int lane0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  static_assert(NL == 1, "a device lane holds its own flag");
+  const uint64_t all = __ballot(flag[0]);
+  if constexpr (L == 64) return all;
+  else return (all >> (lane0 & ~(L - 1))) & ((1ull << L) - 1ull);
+#else
+  (void)lane0;
+  uint64_t m = 0;
+  for (int v = 0; v < NL; v++) m |= (uint64_t)flag[v] << v;
+  return m;
+#endif
+}
+// the word of lane b of the row, on every lane
+template <int L, int NL>
+LOAMX_HD uint32_t knn_row_read(const uint32_t (&word)[NL], int b, int lane0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  static_assert(NL == 1, "a device lane holds its own word");
+  if constexpr (L == 64) return (uint32_t)__builtin_amdgcn_readlane((int)word[0], b);  // (b is wave-uniform)
+  else return (uint32_t)__builtin_amdgcn_ds_bpermute(((lane0 & ~(L - 1)) + b) << 2, (int)word[0]);
+#else
+  (void)lane0;
+  return word[b];
+#endif
+}
+// the smallest key of the row's lanes, on every lane
+template <int L, int NL>
+LOAMX_HD double knn_row_key_min(const double (&key)[NL]) {
+  double m = key[0];
+#if defined(__HIP_DEVICE_COMPILE__)
+  static_assert(NL == 1, "a device lane holds its own key");
+  if constexpr (L == 64) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m = knn_key_min(m, __shfl_xor(m, off));
+  } else {
+    m = knn_key_min(m, row16_xor_key<1>(m)), m = knn_key_min(m, row16_xor_key<2>(m));
+    m = knn_key_min(m, row16_xor_key<4>(m)), m = knn_key_min(m, row16_xor_key<8>(m));
+    if constexpr (L == 32) m = knn_key_min(m, knn_key_join(row32_xor16_b32(knn_key_hi(m)), row32_xor16_b32(knn_key_lo(m))));
+  }
+#else
+  for (int v = 1; v < NL; v++) m = knn_key_min(m, key[v]);
+#endif
+  return m;
+}
+
+// Piece u of shell w around the cell (cx, cy, cz): the rows of cells at Chebyshev distance w over x in [cx - w, cx + w] (shell 1:
+// all nine rows of the block, centre first), then for w > 1 the two end cells cx -+ w of every row inside. If the bound reaches
+// the piece: its range [rb, re) of the sorted points and its smallest possible squared distance s2; else rb = re = 0.
+LOAMX_HD void knn_coop_piece(const GridDesc& g, const uint32_t* __restrict__ cell_start, const Vec3& q, int32_t cx, int32_t cy, int32_t cz,
+                             int32_t w, int u, int ring_rows, int pieces, double bound, uint32_t& rb, uint32_t& re, double& s2) {
+  rb = 0, re = 0, s2 = kDblMax;
+  int32_t dy = 0, dz = 0, xlo = cx - w, xhi = cx + w;
+  bool cap = false;
+  if (w == 1) {
+    constexpr int kOrder[9] = {4, 1, 3, 5, 7, 0, 2, 6, 8};
+    const int j = kOrder[u < 9 ? u : 0];
+    dy = j % 3 - 1, dz = j / 3 - 1;
+  } else if (u < ring_rows) {
+    const int side = 2 * w + 1, inner = 2 * w - 1;
+    if (u < side) dy = u - w, dz = -w;
+    else if (u < 2 * side) dy = u - side - w, dz = w;
+    else if (u < 2 * side + inner) dy = -w, dz = u - 2 * side - (w - 1);
+    else dy = w, dz = u - 2 * side - inner - (w - 1);
+  } else {
+    const int v = u - ring_rows, ri = v >> 1, inner = 2 * w - 1;
+    dy = ri % inner - (w - 1), dz = ri / inner - (w - 1);
+    xlo = xhi = (v & 1) ? cx + w : cx - w;
+    cap = true;
+  }
+  const int32_t iy = cy + dy, iz = cz + dz;
+  if (!(u < pieces && iy >= 0 && iy <= g.ny - 1 && iz >= 0 && iz <= g.nz - 1)) return;
+  const double sy = dy == 0 ? 0.0 : slab_dist(q.y, g.oy, g.h, iy), sz = dz == 0 ? 0.0 : slab_dist(q.z, g.oz, g.h, iz);
+  double pmin2 = sy * sy + sz * sz;
+  if (cap) {
+    const double sx = slab_dist(q.x, g.ox, g.h, xlo);
+    pmin2 += sx * sx;
+  }
+  if (!(pmin2 <= bound)) return;
+  if (!cap) {
+    if (xlo < 0) xlo = 0;
+    if (xhi > g.nx - 1) xhi = g.nx - 1;
+    if (bound < kDblMax) {  // cells whose x slab is farther than sqrt(bound - rowmin2) cannot contribute (as knn_general_round)
+      const double reach = sqrt(bound - pmin2) + 1e-9 * g.h;
+      const int32_t xl = grid_cell_coord(q.x - reach, g.ox, g.inv_h), xh = grid_cell_coord(q.x + reach, g.ox, g.inv_h);
+      if (xl > xlo) xlo = xl;
+      if (xh < xhi) xhi = xh;
+    }
+  }
+  if (xlo <= xhi && xlo >= 0 && xhi <= g.nx - 1) {
+    const uint32_t row = (uint32_t)((iz * g.ny + iy) * g.nx);
+    rb = cell_start_at(cell_start, row + (uint32_t)xlo);
+    re = cell_start_at(cell_start, row + (uint32_t)xhi + 1u);
+    s2 = pmin2;
+  }
+}
+
+// The next draw from the lanes' lists: the smallest key above `prev` held by any lane of the row, on every lane (empty: none is
+// left). Keys of different candidates differ in their position bits, so the draws prev = -1 (below every key, the value of the
+// sentinel slots), then the last draw, and so on, are the row's keys in ascending order — with no list copied or shifted.
+template <int KM, int L, int NL>
+LOAMX_HD double knn_row_draw(const KnnKeys<KM> (&c)[NL], double prev) {
+  double head[NL];
+#pragma unroll
+  for (int v = 0; v < NL; v++) {
+    head[v] = knn_key_empty();
+#pragma unroll
+    for (int j = KM; j >= 0; j--) head[v] = c[v].key[j] > prev ? c[v].key[j] : head[v];  // (ascending list: its first slot above prev, branch-free)
+  }
+  return knn_row_key_min<L, NL>(head);
+}
+
+template <int KM, int L, int NL>
+LOAMX_HD int knn_coop_search_rows(const GridDesc& g, const uint32_t* __restrict__ cell_start, const GridPoint* __restrict__ sp, Vec3 q,
+                                  int k, double max_dist, double pass_max, int lane0, uint32_t pos[KM]) {
+  static_assert(L == 16 || L == 32 || L == 64, "a row of 16 lanes, two of them, or the wavefront");
+  static_assert(NL == 1 || NL == L, "the caller holds one lane or the whole row");
+  const int in_row = lane0 & (L - 1);  // the number in its row of the first lane the caller holds
+#pragma unroll
+  for (int j = 0; j < KM; j++) pos[j] = 0;
+  if (g.n_points == 0 || k <= 0) return 0;
+  if (k > KM) k = KM;
+  const int32_t cx = grid_cell_coord(q.x, g.ox, g.inv_h), cy = grid_cell_coord(q.y, g.oy, g.inv_h), cz = grid_cell_coord(q.z, g.oz, g.inv_h);
+  const int32_t out = grid_outside_distance(g, cx, cy, cz);
+  if (max_dist > 0.0 && out >= 1 && (double)(out - 1) * g.h >= max_dist) return 0;
+  // Shells of growing half-width w, as the one-lane search visits them (knn_rounds): shell 1 = the 3x3x3 block, shell w > 1 =
+  // the cells at Chebyshev distance w. The last shell a radius can need: the cube whose faces lie strictly beyond it
+  // (+ 1: whatever the query's place in its cell; + out: a query outside the grid sits `out` cells off the nearest grid cell).
+  int32_t W = 0x7FFFFFFF;
+  if (max_dist > 0.0) {
+    const double wf = ceil(max_dist * g.inv_h) + 1.0 + (double)out;
+    if (wf < 1.0e6) W = (int32_t)wf;
+  }
+  if (W > kCoopMaxShell) {  // no radius (or a huge one in cells): only while the grid itself is that small
+    const int32_t span = (g.nx > g.ny ? (g.nx > g.nz ? g.nx : g.nz) : (g.ny > g.nz ? g.ny : g.nz)) + out;
+    if (span > kCoopMaxShell) return -2;
+    W = span;
+  }
+  const double r2 = knn_radius_bound(max_dist);
+  double bound = r2;  // the same on every lane of the row: nothing farther than this can be among the k kept
+  KnnKeys<KM> c[NL];
+#pragma unroll
+  for (int v = 0; v < NL; v++) knn_init(c[v], k, g.n_points);
+  bool done = false;
+  double kth = knn_key_empty();  // the k-th smallest key of the row after the last shell that offered a candidate
+  bool fresh = false;            // (the same on every lane of the row) candidates were offered since kth was drawn
+  for (int32_t w = 1; w <= W && !done; w++) {
+    const int ring_rows = w == 1 ? 9 : 8 * w;
+    const int inner_rows = w == 1 ? 0 : (2 * w - 1) * (2 * w - 1);
+    const int pieces = ring_rows + 2 * inner_rows;
+    for (int u0 = 0; u0 < pieces; u0 += L) {
+      // ---- every lane owns one piece: its distance and, if the bound reaches it, its range
+      uint32_t rb[NL], re[NL], s2hi[NL], s2lo[NL];
+      bool some[NL];
+#pragma unroll
+      for (int v = 0; v < NL; v++) {
+        double s2;
+        knn_coop_piece(g, cell_start, q, cx, cy, cz, w, u0 + in_row + v, ring_rows, pieces, bound, rb[v], re[v], s2);
+        s2hi[v] = knn_key_hi(s2), s2lo[v] = knn_key_lo(s2), some[v] = rb[v] < re[v];
+      }
+      // ---- the non-empty pieces of this turn, one after the other, L candidates at a time
+      uint64_t turn = knn_row_ballot<L, NL>(some, lane0);
+      while (turn) {
+        const int b = __builtin_ctzll(turn);
+        turn &= turn - 1;
+        const uint32_t begin = knn_row_read<L, NL>(rb, b, lane0), end = knn_row_read<L, NL>(re, b, lane0);
+        const double rs2 = knn_key_join(knn_row_read<L, NL>(s2hi, b, lane0), knn_row_read<L, NL>(s2lo, b, lane0));
+        if (rs2 > bound) continue;  // (the bound has moved since the piece was listed)
+        fresh = true;
+        for (uint32_t p0 = begin; p0 < end; p0 += (uint32_t)L) {
+#pragma unroll
+          for (int v = 0; v < NL; v++) {
+            const uint32_t p = p0 + (uint32_t)(in_row + v);
+            const bool real = p < end;
+            const GridPoint t = sp[real ? p : begin];
+            const double dx = q.x - t.x, dy = q.y - t.y, dz = q.z - t.z;
+            const double d2 = dx * dx + dy * dy + dz * dz;  // nanoflann L2_Simple, as knn_scan_batch
+            knn_key_insert(c[v], knn_key_pack(d2, p, c[v].mask, real));
+          }
+        }
+        if (end - begin >= 4u * (uint32_t)L) {  // a populous piece may have moved the bound (a lane with k keys bounds the true k-th distance)
+          double own[NL];
+#pragma unroll
+          for (int v = 0; v < NL; v++) own[v] = knn_bound(c[v], k);
+          const double wb = knn_row_key_min<L, NL>(own);
+          bound = wb < bound ? wb : bound;
+        }
+      }
+    }
+    // ---- is the search over after shell w? The k-th smallest key of the row, drawn from the lanes' lists as at the end,
+    // against the faces of the visited block: knn_done's test
+    // (an empty shell — an isolated query walks ceil(R / h) + 1 of them — leaves the k-th key where it was: the k
+    // minima are only drawn again after a shell that offered candidates)
+    if (fresh) {
+      fresh = false;
+      kth = -1.0;
+      for (int t = 0; t < k; t++) kth = knn_row_draw<KM, L, NL>(c, kth);
+    }
+    KnnKeys<KM> probe;  // (only slot KM - 1 and the mask are read by knn_bound)
+    probe.mask = c[0].mask;
+#pragma unroll
+    for (int j = 0; j <= KM; j++) probe.key[j] = kth;
+    if (kth < knn_key_empty()) {
+      const double ub = knn_bound(probe, k);
+      bound = ub < bound ? ub : bound;
+    }
+    done = knn_done(g, q, k, max_dist, cx, cy, cz, probe, w);  // (the same on every lane of the row)
+  }
+  if (!done) return -1;
+  // ---- the k + 1 smallest keys of the row: k + 1 times the smallest head of the lanes' lists
+  KnnKeys<KM> m;
+  knn_init(m, k, g.n_points);
+  double last = -1.0;
+#pragma unroll
+  for (int t = 0; t <= KM; t++)
+    if (t >= KM - k) m.key[t] = last = knn_row_draw<KM, L, NL>(c, last);  // (slots below hold the sentinel)
+  return knn_keys_finish(m, k, pass_max, pos);
+}
+
+// The deal of a pair's listed entries to the rows of its workgroups (associate_knn_coop_kernel; one wavefront of `rows` rows per
+// workgroup): in its turn number `turn` workgroup `chunk` of the pair's `blocks` holds the entries first .. first + rows - 1, row r
+// the entry first + r — entry t goes to row t mod (rows x blocks), in turn t / (rows x blocks). The kernel's loop and the host
+// model of the deal (tests/hostcheck_coop_rows) both step through a list with these two.
+LOAMX_HD uint32_t knn_coop_deal_first(uint32_t chunk, uint32_t rows) { return chunk * rows; }
+LOAMX_HD uint32_t knn_coop_deal_step(uint32_t blocks, uint32_t rows) { return blocks * rows; }
+
+/* ------------------------------------------------------------------------------------------------
  * FP32 pre-selection (round 1 of the fast kernel).
  *
  * The candidate loop of the keyed collector above is VALU-bound: 8 FP64 operations for the distance

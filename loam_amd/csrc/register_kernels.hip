@@ -1050,8 +1050,8 @@ __global__ __launch_bounds__(kAssocThreads, (KME <= 5 && KMP <= 5) ? LOAMX_ASSOC
 #define LOAMX_REST_THREADS 64
 #endif
 constexpr int kRestThreads = LOAMX_REST_THREADS;  // small workgroups: the queues are short and uneven
-// The listed leftovers of a queue: one WAVEFRONT per entry (associate_knn_coop_kernel) or one lane per entry
-// (associate_knn_left_kernel)? The cooperative search walks shells up to the one the radius closes; without a radius it falls
+// The listed leftovers of a queue: a wavefront or a row of its lanes per entry (associate_knn_coop_kernel) or one lane per
+// entry (associate_knn_left_kernel)? The cooperative search walks shells up to the one the radius closes; without a radius it falls
 // back to lane 0 alone, 63 lanes idle — such searches take the one-lane kernel's dense packing instead.
 __host__ __device__ inline bool queue_leftovers_coop(const RegConfig& C, int kind) {
   return !(C.flags & kRegFlagNoCoopLeft) && C.kind[kind].r > 0.0;
@@ -1176,212 +1176,89 @@ __global__ __launch_bounds__(kRestThreads, kLeftWaves) void associate_knn_left_k
   }
 }
 
-/* ------------------------------------------------------------------------------------------------
- * Wave-cooperative search (round 4): the 64 lanes of a wavefront share ONE query. The listed leftovers of the queue are
- * the searches one lane cannot do well: isolated queries (the whole radius cube: 81 rows at a quarter-radius cell, nearly
- * all empty — ~100 dependent round trips for one lane) and, against a map-sized set, queries whose 3x3x3 block holds
- * thousands of points (one lane walking a thousand batches: associate_knn_rest_kernel took 4 x 1 ms of BASELINE config 5).
- * Here the rows of the block are dealt out over the lanes (both table entries of up to 64 rows in flight at once), and
- * every row's candidates are taken 64 at a time, one per lane, coalesced. Each lane keeps its own FP64 keyed collector
- * (KnnKeys: one double per candidate, distance bits + position); the k + 1 smallest keys of the wavefront are then drawn
- * from the lanes' lists by k + 1 wave-wide minima. That is the collector's own contract — the k + 1 smallest keys of all
- * the candidates examined — so knn_done / knn_keys_finish decide exactly as they do for one lane, and the result is the
- * exact search's (what the keys cannot decide keeps its negative count for the exact collector, as before).
- * The block grows shell by shell as in the one-lane search (knn_rounds): after shell w the wavefront's exact k-th key is
- * tested against the faces of the visited block (knn_done); the last shell is the cube whose faces lie beyond the radius.
- * Pieces farther than the bound (the pooled k-th key; within a shell also any lane's own k-th key) or than the radius are
- * skipped; inside a row only the cells the bound reaches.
- * Returns kept >= 0, -1 undecided, -2 not applicable (more than kCoopMaxShell shells could be needed): the caller falls
- * back to the one-lane search.
- * ---------------------------------------------------------------------------------------------- */
-constexpr int32_t kCoopMaxShell = 64;  // shells a cooperative search may walk (a radius of 62 cells; without a radius: grids up to that size)
-
-__device__ __forceinline__ double wave_min_all(double v) {  // (every lane gets the minimum)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double o = __shfl_xor(v, off);
-    v = knn_key_min(v, o);
-  }
-  return v;
-}
-
+// Cooperative search (reg_math.h: knn_coop_search_rows): the 64 lanes of the wavefront share ONE query.
 template <int KM>
 __device__ __forceinline__ int knn_coop_search(const GridDesc& g, const uint32_t* __restrict__ cell_start, const GridPoint* __restrict__ sp,
                                                Vec3 q, int k, double max_dist, double pass_max, uint32_t pos[KM]) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int j = 0; j < KM; j++) pos[j] = 0;
-  if (g.n_points == 0 || k <= 0) return 0;
-  if (k > KM) k = KM;
-  const int32_t cx = grid_cell_coord(q.x, g.ox, g.inv_h), cy = grid_cell_coord(q.y, g.oy, g.inv_h), cz = grid_cell_coord(q.z, g.oz, g.inv_h);
-  const int32_t out = grid_outside_distance(g, cx, cy, cz);
-  if (max_dist > 0.0 && out >= 1 && (double)(out - 1) * g.h >= max_dist) return 0;
-  // Shells of growing half-width w, as the one-lane search visits them (knn_rounds): shell 1 = the 3x3x3 block, shell w > 1 =
-  // the cells at Chebyshev distance w. The last shell a radius can need: the cube whose faces lie strictly beyond it
-  // (+ 1: whatever the query's place in its cell; + out: a query outside the grid sits `out` cells off the nearest grid cell).
-  int32_t W = 0x7FFFFFFF;
-  if (max_dist > 0.0) {
-    const double wf = ceil(max_dist * g.inv_h) + 1.0 + (double)out;
-    if (wf < 1.0e6) W = (int32_t)wf;
-  }
-  if (W > kCoopMaxShell) {  // no radius (or a huge one in cells): only while the grid itself is that small
-    const int32_t span = (g.nx > g.ny ? (g.nx > g.nz ? g.nx : g.nz) : (g.ny > g.nz ? g.ny : g.nz)) + out;
-    if (span > kCoopMaxShell) return -2;
-    W = span;
-  }
-  const double r2 = knn_radius_bound(max_dist);
-  double bound = r2;  // wave-uniform: nothing farther than this can be among the k kept
-  KnnKeys<KM> c;
-  knn_init(c, k, g.n_points);
-  bool done = false;
-  double kth = knn_key_empty();  // the k-th smallest key of the wavefront after the last shell that offered a candidate
-  bool fresh = false;            // (wave-uniform) candidates were offered since kth was drawn
-  for (int32_t w = 1; w <= W && !done; w++) {
-    // pieces of shell w: the rows at Chebyshev distance w over x in [cx - w, cx + w] (shell 1: all nine rows of the block,
-    // centre first), then for w > 1 the two end cells cx -+ w of every row inside
-    const int ring_rows = w == 1 ? 9 : 8 * w;
-    const int inner_rows = w == 1 ? 0 : (2 * w - 1) * (2 * w - 1);
-    const int pieces = ring_rows + 2 * inner_rows;
-    for (int u0 = 0; u0 < pieces; u0 += 64) {
-      // ---- lane l owns one piece: its distance and, if the bound reaches it, its range
-      uint32_t rb = 0, re = 0;
-      double s2 = kDblMax;
-      {
-        const int u = u0 + lane;
-        int32_t dy = 0, dz = 0, xlo = cx - w, xhi = cx + w;
-        bool cap = false;
-        if (w == 1) {
-          constexpr int kOrder[9] = {4, 1, 3, 5, 7, 0, 2, 6, 8};
-          const int j = kOrder[u < 9 ? u : 0];
-          dy = j % 3 - 1, dz = j / 3 - 1;
-        } else if (u < ring_rows) {
-          const int side = 2 * w + 1, inner = 2 * w - 1;
-          if (u < side) dy = u - w, dz = -w;
-          else if (u < 2 * side) dy = u - side - w, dz = w;
-          else if (u < 2 * side + inner) dy = -w, dz = u - 2 * side - (w - 1);
-          else dy = w, dz = u - 2 * side - inner - (w - 1);
-        } else {
-          const int v = u - ring_rows, ri = v >> 1, inner = 2 * w - 1;
-          dy = ri % inner - (w - 1), dz = ri / inner - (w - 1);
-          xlo = xhi = (v & 1) ? cx + w : cx - w;
-          cap = true;
-        }
-        const int32_t iy = cy + dy, iz = cz + dz;
-        if (u < pieces && iy >= 0 && iy <= g.ny - 1 && iz >= 0 && iz <= g.nz - 1) {
-          const double sy = dy == 0 ? 0.0 : slab_dist(q.y, g.oy, g.h, iy), sz = dz == 0 ? 0.0 : slab_dist(q.z, g.oz, g.h, iz);
-          double pmin2 = sy * sy + sz * sz;
-          if (cap) {
-            const double sx = slab_dist(q.x, g.ox, g.h, xlo);
-            pmin2 += sx * sx;
-          }
-          if (pmin2 <= bound) {
-            if (!cap) {
-              if (xlo < 0) xlo = 0;
-              if (xhi > g.nx - 1) xhi = g.nx - 1;
-              if (bound < kDblMax) {  // cells whose x slab is farther than sqrt(bound - rowmin2) cannot contribute (as knn_general_round)
-                const double reach = sqrt(bound - pmin2) + 1e-9 * g.h;
-                const int32_t xl = grid_cell_coord(q.x - reach, g.ox, g.inv_h), xh = grid_cell_coord(q.x + reach, g.ox, g.inv_h);
-                if (xl > xlo) xlo = xl;
-                if (xh < xhi) xhi = xh;
-              }
-            }
-            if (xlo <= xhi && xlo >= 0 && xhi <= g.nx - 1) {
-              const uint32_t row = (uint32_t)((iz * g.ny + iy) * g.nx);
-              rb = cell_start_at(cell_start, row + (uint32_t)xlo);
-              re = cell_start_at(cell_start, row + (uint32_t)xhi + 1u);
-              s2 = pmin2;
-            }
-          }
-        }
-      }
-      // ---- the non-empty pieces of this turn, one after the other, 64 candidates at a time
-      unsigned long long rows = __ballot(rb < re);
-      while (rows) {
-        const int b = __ffsll(rows) - 1;
-        rows &= rows - 1;
-        const uint32_t begin = (uint32_t)__builtin_amdgcn_readlane((int)rb, b), end = (uint32_t)__builtin_amdgcn_readlane((int)re, b);
-        const double rs2 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(s2), b), __builtin_amdgcn_readlane(__double2loint(s2), b));
-        if (rs2 > bound) continue;  // (the bound has moved since the piece was listed)
-        fresh = true;
-        for (uint32_t p0 = begin; p0 < end; p0 += 64) {
-          const uint32_t p = p0 + (uint32_t)lane;
-          const bool real = p < end;
-          const GridPoint t = sp[real ? p : begin];
-          const double dx = q.x - t.x, dy = q.y - t.y, dz = q.z - t.z;
-          const double d2 = dx * dx + dy * dy + dz * dz;  // nanoflann L2_Simple, as knn_scan_batch
-          knn_key_insert(c, knn_key_pack(d2, p, c.mask, real));
-        }
-        if (end - begin >= 256u) {  // a populous piece may have moved the bound (a lane with k keys bounds the true k-th distance)
-          const double wb = wave_min_all(knn_bound(c, k));
-          bound = wb < bound ? wb : bound;
-        }
-      }
-    }
-    // ---- is the search over after shell w? The k-th smallest key of the wavefront, drawn from the lanes' lists as at the
-    // end (on a copy), against the faces of the visited block: knn_done's test
-    {
-      // (an empty shell — an isolated query walks ceil(R / h) + 1 of them — leaves the k-th key where it was: the k
-      // wave-wide minima are only drawn again after a shell that offered candidates)
-      if (fresh) {
-      fresh = false;
-      KnnKeys<KM> cc = c;
-      kth = knn_key_empty();
-      for (int t = 0; t < k; t++) {
-        double head = knn_key_empty();
-#pragma unroll
-        for (int j = KM; j >= 0; j--)
-          if (j >= KM - k) head = cc.key[j] < head ? cc.key[j] : head;
-        const double best = wave_min_all(head);
-        kth = best;
-        if (head == best && best < knn_key_empty()) {
-#pragma unroll
-          for (int j = 0; j < KM; j++)
-            if (j >= KM - k) cc.key[j] = cc.key[j + 1];
-          cc.key[KM] = knn_key_empty();
-        }
-      }
-      }
-      KnnKeys<KM> probe;  // (only slot KM - 1 and the mask are read by knn_bound)
-      probe.mask = c.mask;
-#pragma unroll
-      for (int j = 0; j <= KM; j++) probe.key[j] = kth;
-      if (kth < knn_key_empty()) {
-        const double ub = knn_bound(probe, k);
-        bound = ub < bound ? ub : bound;
-      }
-      done = knn_done(g, q, k, max_dist, cx, cy, cz, probe, w);  // (wave-uniform)
-    }
-  }
-  if (!done) return -1;
-  // ---- the k + 1 smallest keys of the wavefront: k + 1 times the smallest head of the lanes' lists
-  KnnKeys<KM> m;
-  knn_init(m, k, g.n_points);
-#pragma unroll
-  for (int t = 0; t <= KM; t++) {
-    if (t >= KM - k) {  // (slots below hold the sentinel)
-      double head = knn_key_empty();
-#pragma unroll
-      for (int j = KM; j >= 0; j--)
-        if (j >= KM - k) head = c.key[j] < head ? c.key[j] : head;  // the list is ascending: its first real slot — written branch-free
-      const double best = wave_min_all(head);
-      m.key[t] = best;
-      if (head == best && best < knn_key_empty()) {  // the owner drops it (keys of different candidates differ in their position bits)
-#pragma unroll
-        for (int j = 0; j < KM; j++)
-          if (j >= KM - k) c.key[j] = c.key[j + 1];
-        c.key[KM] = knn_key_empty();
-      }
-    }
-  }
-  return knn_keys_finish(m, k, pass_max, pos);
+  return knn_coop_search_rows<KM, 64, 1>(g, cell_start, sp, q, k, max_dist, pass_max, (int)(threadIdx.x & 63), pos);
 }
 
-// The listed leftovers, one WAVEFRONT per entry (see knn_coop_search); an entry the cooperative search does not apply to
-// (no radius limit) is searched by lane 0 alone, as associate_knn_left_kernel does it.
-// (one wavefront per workgroup: the entry loop steps by workgroups and s_rows is one lane's list — ADVICE r4)
+// The listed leftovers (see knn_coop_search_rows). Against a lean set (queue_lean_set: a scan-sized target) the listed entries
+// with plain reason bits are isolated queries: five shells of 9 - 202 pieces that hold zero to a few points each. One wavefront
+// per entry issued every turn's piece geometry, its 64-candidate batches with a handful of real candidates and the k wave-wide
+// minima for 64 lanes to serve one query (round 6: 5.7e7 vector instructions per launch, ~2 000 wave-instructions per entry),
+// beside the plane fit kernel, which those issue slots slow down. So (round 11) such an entry takes a ROW of kCoopRowLanes lanes,
+// 64 / kCoopRowLanes entries per wavefront and turn: entry t of the list goes to row t mod (rows per wavefront x workgroups of
+// the pair), as associate_fit_late_kernel deals its list. Wide and tied entries and every entry of a map-sized set hold thousands
+// of candidates per piece and keep the wavefront to themselves (BASELINE config 5 lives on them): in a turn the wavefront's
+// whole-wavefront entries come first, then its rows. The result does not depend on who searches (knn_coop_search_rows); the
+// context option NO_COOP_ROWS gives every entry the wavefront, as until round 10.
+// An entry the cooperative search does not apply to (no radius limit) is searched by the first lane of the wavefront or row
+// alone, as associate_knn_left_kernel does it.
+// took: null, or (an association dump's census buffer) two words that count the entries a row took and the entries a wavefront took.
+// (one wavefront per workgroup: the entry loop steps by workgroups and s_rows holds one list per row — ADVICE r4)
 static_assert(kRestThreads == 64, "associate_knn_coop_kernel is written for one wavefront per workgroup");
+constexpr int kCoopRowLanes = 16, kCoopRows = 64 / kCoopRowLanes;  // (32 was measured too: 2.4e7 instructions against 1.6e7, half the gain — EXPERIMENTS.md round 11)
+__host__ __device__ inline bool queue_coop_by_rows(const RegConfig& C, const GridDesc& g) {
+  return !(C.flags & kRegFlagNoCoopRows) && queue_lean_set(g);
+}
+// the listed entry at queue position qpos (query i of the pair; both wave-uniform) by the whole wavefront; lane 0 stores
 template <bool PLANE, int KM>
-__global__ __launch_bounds__(kRestThreads, LOAMX_COOP_WAVES) void associate_knn_coop_kernel(RegBatch B, RegConfig C, uint32_t blocks_per_pair) {
+__device__ __forceinline__ void coop_entry_wave(const RegBatch& B, const RegConfig& C, const PairState& S, size_t pair, const GridDesc& g,
+                                                uint32_t qpos, uint32_t i, uint32_t* s_rows, uint32_t* took) {
+  const RegKind& K = B.kind[PLANE];
+  const RegKindConfig& CK = C.kind[PLANE];
+  const size_t stride = K.stride, field = B.n_pairs * stride;
+  const GridSet &gs = K.grid, &src_gs = K.src_grid;
+  const uint32_t* __restrict__ cs = gs.cell_start + pair * (size_t)(kGridCellsCap + 1);
+  const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
+  uint32_t* __restrict__ rnn = K.rnn;
+  const size_t slot = pair * stride + qpos;
+  const GridPoint sq = src_gs.sorted[pair * src_gs.stride + i];
+  const Vec3 p = pose_act(S.est, v3(sq.x, sq.y, sq.z));
+  uint32_t pos[KM];
+  int kept = knn_coop_search<KM>(g, cs, sp, p, CK.k, CK.r, CK.pass, pos);
+  if (kept == -2) {  // uniform
+    if ((threadIdx.x & 63) == 0) kept = knn_search_keyed<KM>(g, cs, sp, p, CK.k, CK.r, CK.pass, pos, s_rows, kCoopRows);
+    kept = __builtin_amdgcn_readfirstlane(kept);
+#pragma unroll
+    for (int j = 0; j < KM; j++) pos[j] = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos[j]);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    rnn[slot] = (uint32_t)kept;
+#pragma unroll
+    for (int j = 0; j < KM; j++) rnn[(1 + j) * field + slot] = pos[j];
+    if (took) atomicAdd(&took[1], 1u);
+  }
+}
+// the listed entry at queue position qpos (query i; both the same on all lanes of the row) by the row of kCoopRowLanes lanes that
+// `lane` belongs to; the row's first lane stores. s_row: the row's list for the one-lane search, [word][kCoopRows]
+template <bool PLANE, int KM>
+__device__ __forceinline__ void coop_entry_row(const RegBatch& B, const RegConfig& C, const PairState& S, size_t pair, const GridDesc& g,
+                                               uint32_t qpos, uint32_t i, uint32_t* s_row, int lane, uint32_t* took) {
+  const RegKind& K = B.kind[PLANE];
+  const RegKindConfig& CK = C.kind[PLANE];
+  const size_t stride = K.stride, field = B.n_pairs * stride;
+  const GridSet &gs = K.grid, &src_gs = K.src_grid;
+  const uint32_t* __restrict__ cs = gs.cell_start + pair * (size_t)(kGridCellsCap + 1);
+  const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
+  uint32_t* __restrict__ rnn = K.rnn;
+  const size_t slot = pair * stride + qpos;
+  const GridPoint sq = src_gs.sorted[pair * src_gs.stride + i];
+  const Vec3 p = pose_act(S.est, v3(sq.x, sq.y, sq.z));
+  uint32_t pos[KM];
+  int kept = knn_coop_search_rows<KM, kCoopRowLanes, 1>(g, cs, sp, p, CK.k, CK.r, CK.pass, lane, pos);
+  if ((lane & (kCoopRowLanes - 1)) == 0) {
+    if (kept == -2) kept = knn_search_keyed<KM>(g, cs, sp, p, CK.k, CK.r, CK.pass, pos, s_row, kCoopRows);
+    rnn[slot] = (uint32_t)kept;
+#pragma unroll
+    for (int j = 0; j < KM; j++) rnn[(1 + j) * field + slot] = pos[j];
+    if (took) atomicAdd(&took[0], 1u);
+  }
+}
+template <bool PLANE, int KM>
+__global__ __launch_bounds__(kRestThreads, LOAMX_COOP_WAVES) void associate_knn_coop_kernel(RegBatch B, RegConfig C, uint32_t blocks_per_pair,
+                                                                                           uint32_t* took) {
   size_t pair;
   uint32_t chunk0;
   if (!assoc_map(B, blockIdx.x, blocks_per_pair, pair, chunk0)) return;
@@ -1389,38 +1266,33 @@ __global__ __launch_bounds__(kRestThreads, LOAMX_COOP_WAVES) void associate_knn_
   if (!S.active) return;                                              // uniform per workgroup
   const uint32_t listed = B.n_assoc[8 * pair + (PLANE ? 5 : 4)];
   if (listed == 0u) return;                                           // uniform per workgroup
-  __shared__ uint32_t s_rows[kLeanRowWords];
+  __shared__ uint32_t s_rows[kLeanRowWords * kCoopRows];  // ([word][row]: one list per row for the one-lane search)
   const RegKind& K = B.kind[PLANE];
-  const RegKindConfig& CK = C.kind[PLANE];
   const size_t stride = K.stride;
-  const size_t field = B.n_pairs * stride;
-  uint32_t* __restrict__ rnn = K.rnn;
   const uint32_t* __restrict__ rest = K.rest + pair * stride;
   const uint32_t* __restrict__ left = K.exact + pair * stride;
-  const GridSet &gs = K.grid, &src_gs = K.src_grid;
-  const GridDesc g = gs.desc[pair];
-  const uint32_t* __restrict__ cs = gs.cell_start + pair * (size_t)(kGridCellsCap + 1);
-  const GridPoint* __restrict__ sp = gs.sorted + pair * gs.stride;
-  const int kq = CK.k;
-  const double max_dist = CK.r, pass_max = CK.pass;
-  for (uint32_t t = chunk0; t < listed; t += blocks_per_pair) {  // (wave-uniform: one entry per wavefront and turn)
-    const uint32_t qpos = left[t], i = rest[qpos] & kQueueIndex;
-    const size_t slot = pair * stride + qpos;
-    const GridPoint sq = src_gs.sorted[pair * src_gs.stride + i];
-    const Vec3 p = pose_act(S.est, v3(sq.x, sq.y, sq.z));
-    uint32_t pos[KM];
-    int kept = knn_coop_search<KM>(g, cs, sp, p, kq, max_dist, pass_max, pos);
-    if (kept == -2) {  // uniform
-      if ((threadIdx.x & 63) == 0) kept = knn_search_keyed<KM>(g, cs, sp, p, kq, max_dist, pass_max, pos, s_rows, 1);
-      kept = __builtin_amdgcn_readfirstlane(kept);
-#pragma unroll
-      for (int j = 0; j < KM; j++) pos[j] = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos[j]);
+  const GridDesc g = K.grid.desc[pair];
+  if (!queue_coop_by_rows(C, g)) {                                    // uniform per workgroup
+    for (uint32_t t = chunk0; t < listed; t += blocks_per_pair) {  // (wave-uniform: one entry per wavefront and turn)
+      const uint32_t qpos = left[t];
+      coop_entry_wave<PLANE, KM>(B, C, S, pair, g, qpos, rest[qpos] & kQueueIndex, s_rows, took);
     }
-    if ((threadIdx.x & 63) == 0) {
-      rnn[slot] = (uint32_t)kept;
-#pragma unroll
-      for (int j = 0; j < KM; j++) rnn[(1 + j) * field + slot] = pos[j];
+    return;
+  }
+  const int lane = (int)(threadIdx.x & 63), row = lane / kCoopRowLanes;
+  // (wave-uniform: one entry per row and turn; the deal: reg_math.h)
+  for (uint32_t t0 = knn_coop_deal_first(chunk0, kCoopRows); t0 < listed; t0 += knn_coop_deal_step(blocks_per_pair, kCoopRows)) {
+    // ---- the turn's wide and tied entries, one after the other by the whole wavefront
+    for (uint32_t t = t0; t < t0 + kCoopRows && t < listed; t++) {
+      const uint32_t qpos = left[t], entry = rest[qpos];
+      if (entry & (kQueueWide | kQueueTied)) coop_entry_wave<PLANE, KM>(B, C, S, pair, g, qpos, entry & kQueueIndex, s_rows, took);
     }
+    // ---- its plain entries, each by its row (uniform per row; the rows are back together at the end of the block: the next turn's
+    // whole-wavefront entries need all 64 lanes)
+    const uint32_t t = t0 + (uint32_t)row;
+    uint32_t qpos = 0u, entry = kQueueWide;
+    if (t < listed) qpos = left[t], entry = rest[qpos];
+    if (!(entry & (kQueueWide | kQueueTied))) coop_entry_row<PLANE, KM>(B, C, S, pair, g, qpos, entry & kQueueIndex, s_rows + row, lane, took);
   }
 }
 
@@ -2751,7 +2623,8 @@ void launch_associate(const RegBatch& B, const RegConfig& C, hipStream_t s, hipS
         const uint32_t cblk_ = coop_blocks(B.n_pairs);                                                            \
         note[PL].leftover_kernel = LOAMX_ASSOC_LEFTOVER_COOP, note[PL].coop_blocks = cblk_;                       \
         launch_kernel((associate_knn_coop_kernel<PL, KMV>), dim3((unsigned)(pair_groups * 8 * cblk_)),       \
-                           dim3(kRestThreads), 0, (st), B, C, cblk_);                                             \
+                           dim3(kRestThreads), 0, (st), B, C, cblk_,                                              \
+                           (census && census->buf[PL].counts) ? census->buf[PL].counts + 5 : (uint32_t*)nullptr);        \
       }                                                                                                           \
     }                                                                                                             \
     census_at((PL), 2, (st));                                                                                     \
