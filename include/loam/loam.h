@@ -9,3 +9,4 @@
 #include "place.h"
 #include "posegraph.h"
 #include "registration.h"
+#include "segment.h"

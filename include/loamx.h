@@ -258,6 +258,7 @@ int loamx_ctx_last_assoc_coop_forms(loamx_ctx* ctx, int which_kind, uint32_t out
  *   multi-GPU:     FORCE_RCCL (a one-rank communicator really enqueues the RCCL collectives)
  *   input checks:  CHECK_FINITE (see "Non-finite input" below)
  *   cloud map:     NO_CLOUDMAP_COMBINE (one claim per point instead of one per run of a wavefront: the same bytes, see "cloud map")
+ *   segmentation:  NO_SEGMENT_TILES (every connected edge through the global union, no tile labelling in LDS: the same bytes, see "scan segmentation")
  * Unknown name: LOAMX_ERR_BAD_PARAM.
  *
  * Non-finite input. The reference is undefined on NaN / Inf coordinates (loam/include/loam/features-inl.h:38 sorts on
@@ -990,6 +991,90 @@ int loamx_cloud_map_add_cloud_f32(loamx_ctx* ctx, loamx_cloud_map* map, const fl
                                   const double pose[7]);
 int loamx_cloud_map_emit(loamx_ctx* ctx, const loamx_cloud_map* map, uint32_t min_points, double* xyz_out, uint32_t* count_out,
                          uint32_t* first_out, size_t capacity, size_t* n_out);
+
+/* ---- scan segmentation (no reference counterpart; the range-image pass LeGO-LOAM and LIO-SAM put in front of the extraction).
+ * Labels the ground of an organised scan, clusters the rest by connected components under an angle criterion, and tells the
+ * components too small to be a surface (leaves, wires, rain, the edges of moving objects) from the others. Everything is integer
+ * or individually rounded FP64, roots are minima and counts are integer sums: two runs give the same bytes, a scan alone or inside
+ * a batch gives the same bytes, and a numpy model is compared by equality on every cell (tests/segment_common.py).
+ *
+ * The rule (loam_amd/csrc/segment_math.h). Every product, sum and difference is one FP64 operation rounded on its own, in the
+ * order written; float input is widened first. A scan is scan_lines (H) x points_per_line (W) cells, row-major, i = l W + c.
+ *   valid      a cell is valid iff its three coordinates are finite and sqrt((x x + y y) + z z), the extraction's range, is not
+ *              < min_range and not > max_range (the extraction's own comparison). (0, 0, 0) and NaN cells are invalid; they are
+ *              never refused.
+ *   ground     G = ground_lines, or H when that is 0 or larger than H. For every column c and every l with l + 1 < G the cells
+ *              (l, c), (l + 1, c) are a ground pair iff both are valid and dz dz <= tg2 (dx dx + dy dy), d = p(l + 1, c) - p(l, c),
+ *              tg2 = tan(ground_angle)^2. A cell is ground iff it belongs to at least one ground pair.
+ *   nodes      the valid cells that are not ground. Candidate edges per cell: right, (l, c) - (l, (c + 1) mod W) (none when
+ *              W == 1; when W == 2 the same pair appears from both cells); up, (l, c) - (l + 1, c) (lines do not wrap).
+ *   connected  two nodes a, b joined by a candidate edge are connected iff t t < (c2 m) e2, where r2 = (x x + y y) + z z per point,
+ *              m = max(r2a, r2b), dot = (ax bx + ay by) + az bz, e = b - a, e2 = (ex ex + ey ey) + ez ez, t = m - dot and
+ *              c2 = cos(segment_angle)^2: the angle at the farther point between the ray to the sensor and the chord to the nearer
+ *              point exceeds segment_angle (LeGO-LOAM's test without atan2, sqrt or the sensor's angular resolution). The
+ *              expression is symmetric in a and b to the bit: the graph is undirected.
+ *   components the connected components of that graph. Label = the smallest linear index (the root); size = the number of cells;
+ *              line span = max line - min line + 1. Accepted iff size >= min_cluster_points, or size >= min_tall_cluster_points
+ *              and span >= min_tall_cluster_lines. Cells of accepted components are class cluster, the others class outlier.
+ * tg2 and c2 are formed once per call on the host (FP64, libm); loamx_segment_constants returns the same two numbers. */
+typedef struct {
+  uint64_t ground_lines;            /* 0 (all lines) */
+  double ground_angle;              /* 10 degrees, in radians */
+  double segment_angle;             /* 60 degrees, in radians */
+  uint64_t min_cluster_points;      /* 30 */
+  uint64_t min_tall_cluster_points; /* 5 */
+  uint64_t min_tall_cluster_lines;  /* 3 */
+  uint32_t drop_outliers;           /* 1 */
+  uint32_t drop_ground;             /* 0 */
+} loamx_segment_params;
+enum { LOAMX_SEGMENT_INVALID = 0, LOAMX_SEGMENT_GROUND = 1, LOAMX_SEGMENT_CLUSTER = 2, LOAMX_SEGMENT_OUTLIER = 3 };
+#define LOAMX_SEGMENT_NO_LABEL 0xFFFFFFFFu
+typedef struct {
+  uint32_t root, size, line_min, line_max;
+} loamx_segment_cluster;
+void loamx_default_segment_params(loamx_segment_params* p);
+/* out = {tg2, c2} exactly as the launcher computes them. Needs no context. LOAMX_ERR_BAD_PARAM as listed below for the angles. */
+int loamx_segment_constants(const loamx_segment_params* params, double out[2]);
+/* n_scans device-resident scans back to back (n_scans x H x W x 3 scalars). Outputs per scan, back to back over the batch, each
+ * pointer may be NULL:
+ *   d_classes   uint8 per cell: LOAMX_SEGMENT_INVALID / _GROUND / _CLUSTER / _OUTLIER
+ *   d_labels    uint32 per cell: the root for cluster and outlier cells, LOAMX_SEGMENT_NO_LABEL otherwise
+ *   d_sizes     uint32 per cell: the size of the cell's component for cluster and outlier cells, 0 otherwise
+ *   d_filtered  a scan of the input's scalar type: invalid cells, outlier cells under drop_outliers and ground cells under
+ *               drop_ground become (+0, +0, +0); every other cell's three scalars are copied bit for bit. May be exactly d_scans
+ *               (in place); any other overlap is the caller's error.
+ *   d_clusters  the accepted components in ascending root order, max_clusters records per scan of which the first
+ *               min(accepted, max_clusters) are written (an ordered compaction: never a sort, never arrival order)
+ *   d_stats     uint32[8] per scan: {invalid, ground, cluster cells, outlier cells, accepted components, rejected components,
+ *               largest component size, cluster records written}
+ * Asynchronous on the context's stream; synchronises only when the workspace has to grow. LOAMX_ERR_BAD_PARAM: a null params or
+ * lidar, scan_lines or points_per_line 0, a non-finite angle, ground_angle outside [0, pi/2), segment_angle outside (0, pi/2), a
+ * max_range whose fourth power is not finite, a null d_scans with n_scans > 0. LOAMX_ERR_UNSUPPORTED: points_per_line > 4096 or
+ * more than 2^30 - 1 cells (the extraction's limits), more than 65535 scans. A refused call writes nothing. n_scans == 0: LOAMX_OK.
+ *
+ * Kernels (loam_amd/csrc/segment_kernels.hip): classes and ground per cell; the components of each 16 x 256 tile by a union-find in
+ * LDS; the connected edges that cross a tile border (and the seam edges) through a union on global parents; a separate launch
+ * flattens. Context option NO_SEGMENT_TILES: every parent starts as its own index and ALL connected edges go through the global
+ * union — the same bytes. */
+int loamx_segment_scans_dev(loamx_ctx* ctx, const double* d_scans, size_t n_scans, const loamx_lidar_params* lidar,
+                            const loamx_segment_params* params, uint8_t* d_classes, uint32_t* d_labels, uint32_t* d_sizes,
+                            double* d_filtered, loamx_segment_cluster* d_clusters, size_t max_clusters, uint32_t* d_stats);
+int loamx_segment_scans_dev_f32(loamx_ctx* ctx, const float* d_scans, size_t n_scans, const loamx_lidar_params* lidar,
+                                const loamx_segment_params* params, uint8_t* d_classes, uint32_t* d_labels, uint32_t* d_sizes,
+                                float* d_filtered, loamx_segment_cluster* d_clusters, size_t max_clusters, uint32_t* d_stats);
+/* one scan, host memory in, host memory out, synchronous; further LOAMX_ERR_BAD_PARAM: a null scan */
+int loamx_segment_scan(loamx_ctx* ctx, const double* scan, const loamx_lidar_params* lidar, const loamx_segment_params* params,
+                       uint8_t* classes, uint32_t* labels, uint32_t* sizes, double* filtered, loamx_segment_cluster* clusters,
+                       size_t max_clusters, uint32_t* stats);
+int loamx_segment_scan_f32(loamx_ctx* ctx, const float* scan, const loamx_lidar_params* lidar, const loamx_segment_params* params,
+                           uint8_t* classes, uint32_t* labels, uint32_t* sizes, float* filtered, loamx_segment_cluster* clusters,
+                           size_t max_clusters, uint32_t* stats);
+/* The last segmentation call of the context: out = {tile lines, tile columns, tiles per scan, connected edges handed to the global
+ * union counted per cell and direction over the whole call, form: 1 tiles, 0 global-only}. An edge is handed over in the tile form
+ * iff it is an up edge from the last line of a tile, a right edge from the last column of a tile, or a right edge from column
+ * W - 1 (the seam, even where one tile holds both ends); in the global-only form always. Synchronises. LOAMX_ERR_BAD_PARAM before
+ * any segmentation call. Never part of a result. */
+int loamx_ctx_last_segment_census(loamx_ctx* ctx, uint64_t out[5]);
 
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are

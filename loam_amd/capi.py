@@ -231,6 +231,56 @@ class CloudMapParams:
 CLOUD_MAP_STATS_DTYPE = np.dtype([(n, np.uint64) for n in ("voxels", "points_offered", "points_used", "invalid", "range", "outside", "overflow")])
 
 
+class SegmentParamsStruct(C.Structure):
+    """loamx_segment_params (include/loamx.h)"""
+    _fields_ = [("ground_lines", C.c_uint64), ("ground_angle", C.c_double), ("segment_angle", C.c_double),
+                ("min_cluster_points", C.c_uint64), ("min_tall_cluster_points", C.c_uint64), ("min_tall_cluster_lines", C.c_uint64),
+                ("drop_outliers", C.c_uint32), ("drop_ground", C.c_uint32)]
+
+
+class SegmentParams:
+    """The rule of the scan segmentation (loamx_segment_params): the lines that can be ground and the ground angle, the
+    segmentation angle, the accept rule of a component and what the filtered scan drops. Anything left out takes the C ABI's
+    default."""
+    FIELDS = tuple(f[0] for f in SegmentParamsStruct._fields_)
+
+    def __init__(self, **kw):
+        d = SegmentParamsStruct()
+        load().loamx_default_segment_params(C.byref(d))
+        for name in self.FIELDS:
+            setattr(self, name, getattr(d, name))
+        for name, v in kw.items():
+            if name not in self.FIELDS:
+                raise TypeError(f"SegmentParams: no field {name}")
+            setattr(self, name, v)
+
+    def struct(self):
+        for name in ("ground_lines", "min_cluster_points", "min_tall_cluster_points", "min_tall_cluster_lines"):
+            if int(getattr(self, name)) < 0:
+                raise ValueError(f"SegmentParams: {name} must be >= 0")
+        return SegmentParamsStruct(int(self.ground_lines), float(self.ground_angle), float(self.segment_angle), int(self.min_cluster_points),
+                                   int(self.min_tall_cluster_points), int(self.min_tall_cluster_lines), 1 if self.drop_outliers else 0,
+                                   1 if self.drop_ground else 0)
+
+
+# classes of a cell, the label of a cell without a component, loamx_segment_cluster, the names of the stats words
+SEGMENT_INVALID, SEGMENT_GROUND, SEGMENT_CLUSTER, SEGMENT_OUTLIER = 0, 1, 2, 3
+SEGMENT_NO_LABEL = 0xFFFFFFFF
+SEGMENT_CLUSTER_DTYPE = np.dtype([("root", np.uint32), ("size", np.uint32), ("line_min", np.uint32), ("line_max", np.uint32)])
+SEGMENT_STATS = ("invalid", "ground", "cluster_cells", "outlier_cells", "accepted", "rejected", "largest", "records")
+SegmentCensus = collections.namedtuple("SegmentCensus", "tile_lines tile_cols tiles_per_scan merged_edges tiles")
+
+
+def segment_constants(params=None):
+    """(tg2, c2) = (tan(ground_angle)^2, cos(segment_angle)^2) exactly as the launcher computes them (loamx_segment_constants)"""
+    st = (params or SegmentParams()).struct()
+    out = (C.c_double * 2)()
+    rc = load().loamx_segment_constants(C.byref(st), out)
+    if rc != OK:
+        raise LoamxError(rc, "loamx_segment_constants: " + load().loamx_status_string(rc).decode())
+    return float(out[0]), float(out[1])
+
+
 class PgoParamsStruct(C.Structure):
     """loamx_pgo_params (include/loamx.h)"""
     _fields_ = [("max_iterations", C.c_uint32), ("max_pcg_iterations", C.c_uint32), ("pcg_tolerance", C.c_double),
@@ -307,6 +357,8 @@ EXPORTS = [
     "loamx_default_cloud_map_params", "loamx_cloud_map_create", "loamx_cloud_map_destroy", "loamx_cloud_map_clear",
     "loamx_cloud_map_add_clouds_dev", "loamx_cloud_map_add_clouds_dev_f32", "loamx_cloud_map_emit_dev", "loamx_cloud_map_stats_read",
     "loamx_cloud_map_add_cloud", "loamx_cloud_map_add_cloud_f32", "loamx_cloud_map_emit", "loamx_cloud_map_claims_read",
+    "loamx_default_segment_params", "loamx_segment_constants", "loamx_segment_scans_dev", "loamx_segment_scans_dev_f32",
+    "loamx_segment_scan", "loamx_segment_scan_f32", "loamx_ctx_last_segment_census",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -560,6 +612,15 @@ def load(build_if_missing=True):
     lib.loamx_cloud_map_add_cloud.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.loamx_cloud_map_add_cloud_f32.argtypes = lib.loamx_cloud_map_add_cloud.argtypes
     lib.loamx_cloud_map_emit.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, C.c_size_t, szp]
+    lib.loamx_default_segment_params.argtypes = [C.POINTER(SegmentParamsStruct)]
+    lib.loamx_default_segment_params.restype = None
+    lib.loamx_segment_constants.argtypes = [C.POINTER(SegmentParamsStruct), dp]
+    lib.loamx_segment_scans_dev.argtypes = [vp, vp, C.c_size_t, C.POINTER(LidarParams), C.POINTER(SegmentParamsStruct), vp, vp, vp, vp, vp,
+                                            C.c_size_t, vp]
+    lib.loamx_segment_scans_dev_f32.argtypes = lib.loamx_segment_scans_dev.argtypes
+    lib.loamx_segment_scan.argtypes = [vp, vp, C.POINTER(LidarParams), C.POINTER(SegmentParamsStruct), vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.loamx_segment_scan_f32.argtypes = lib.loamx_segment_scan.argtypes
+    lib.loamx_ctx_last_segment_census.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.loamx_pgo_default_params.argtypes = [C.POINTER(PgoParamsStruct)]
     lib.loamx_pgo_default_params.restype = None
     lib.loamx_pose_graph_optimize_dev.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(PgoParamsStruct), vp]
@@ -1528,6 +1589,45 @@ class Context:
         self._check(fn(self.h, layout._handle(), pts.ctypes.data, stride, r.ctypes.data if r is not None else None, n, scan.ctypes.data,
                        src.ctypes.data, stats.ctypes.data))
         return scan, src, stats
+
+    # ---- scan segmentation (include/loamx.h, "scan segmentation") ----------------------------------------------
+    def segment_scans_dev(self, d_scans, n_scans, lidar, params=None, d_classes=0, d_labels=0, d_sizes=0, d_filtered=0, d_clusters=0,
+                          max_clusters=0, d_stats=0, f32=False):
+        """n_scans device-resident scans -> classes, labels, sizes, the filtered scans, the cluster tables (max_clusters records
+        per scan) and the stats (loamx_segment_scans_dev[_f32]); every output is a device address or 0. d_filtered may equal
+        d_scans. Asynchronous on the context's stream."""
+        if int(n_scans) < 0 or int(max_clusters) < 0:
+            raise ValueError("segment_scans_dev: n_scans and max_clusters must be >= 0")
+        st = (params or SegmentParams()).struct()
+        fn = self.lib.loamx_segment_scans_dev_f32 if f32 else self.lib.loamx_segment_scans_dev
+        self._check(fn(self.h, d_scans or None, int(n_scans), C.byref(lidar), C.byref(st), d_classes or None, d_labels or None, d_sizes or None,
+                       d_filtered or None, d_clusters or None, int(max_clusters), d_stats or None))
+
+    def segment_scan(self, scan, lidar, params=None):
+        """One organised scan in host memory, float64 or float32 -> (classes (H W,) uint8, labels (H W,) uint32 with
+        SEGMENT_NO_LABEL outside the components, sizes (H W,) uint32, filtered (H W, 3) in the scan's dtype, clusters = the accepted
+        components as SEGMENT_CLUSTER_DTYPE records in ascending root order, stats = uint32[8], see SEGMENT_STATS)."""
+        a = np.asarray(scan)
+        if a.dtype != np.float32:
+            a = np.asarray(a, dtype=np.float64)
+        cells = int(lidar.scan_lines) * int(lidar.points_per_line)
+        if a.size != cells * 3:
+            raise ValueError(f"segment_scan: the scan holds {a.size} scalars, the lidar parameters ask for {cells} x 3")
+        a = np.ascontiguousarray(a.reshape(-1, 3))
+        st = (params or SegmentParams()).struct()
+        classes, labels, sizes = np.empty(cells, np.uint8), np.empty(cells, np.uint32), np.empty(cells, np.uint32)
+        filtered, clusters, stats = np.empty_like(a), np.empty(cells, SEGMENT_CLUSTER_DTYPE), np.zeros(8, np.uint32)
+        fn = self.lib.loamx_segment_scan_f32 if a.dtype == np.float32 else self.lib.loamx_segment_scan
+        self._check(fn(self.h, a.ctypes.data, C.byref(lidar), C.byref(st), classes.ctypes.data, labels.ctypes.data, sizes.ctypes.data,
+                       filtered.ctypes.data, clusters.ctypes.data, cells, stats.ctypes.data))
+        return classes, labels, sizes, filtered, clusters[:int(stats[7])].copy(), stats
+
+    def last_segment_census(self):
+        """The last segmentation call of this context (loamx_ctx_last_segment_census): tile shape, tiles per scan, the connected
+        edges that went through the global union, and whether the tile form ran."""
+        v = (C.c_uint64 * 5)()
+        self._check(self.lib.loamx_ctx_last_segment_census(self.h, v))
+        return SegmentCensus(int(v[0]), int(v[1]), int(v[2]), int(v[3]), bool(v[4]))
 
     # ---- place recognition (include/loamx.h, "place recognition") --------------------------------------------
     def place_db(self, params=None):

@@ -36,7 +36,8 @@ const OptionName kOptionNames[] = {
     {"NO_COOP_LEFT", false, kRegFlagNoCoopLeft}, {"NO_COOP_ROWS", false, kRegFlagNoCoopRows}, {"NO_REF_MOMENTS", false, kRegFlagNoRefMoments},
     {"NO_EXTRACT_BOXES", false, kRegFlagNoExtractBoxes}, {"CHECK_FINITE", false, kRegFlagCheckFinite},
     {"NO_SMALL_SETS", false, kRegFlagNoSmallSets}, {"FORCE_LATE_VERIFY", false, kRegFlagForceLate},
-    {"NO_LIVE_DEAL", false, kRegFlagNoLiveDeal}, {"NO_CLOUDMAP_COMBINE", false, kRegFlagNoCloudmapCombine}};
+    {"NO_LIVE_DEAL", false, kRegFlagNoLiveDeal}, {"NO_CLOUDMAP_COMBINE", false, kRegFlagNoCloudmapCombine},
+    {"NO_SEGMENT_TILES", false, kRegFlagNoSegmentTiles}};
 
 }  // namespace
 

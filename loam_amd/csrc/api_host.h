@@ -27,6 +27,7 @@ enum WsId {
   WS_PLACE_TABLE, WS_PLACE_QKEYS, WS_PLACE_QNORMS, WS_PLACE_CAND_A, WS_PLACE_CAND_B, WS_PLACE_MATCH, WS_PLACE_IN, WS_PLACE_OUT,
   WS_PGO_WORK, WS_PGO_POSES, WS_PGO_FIXED, WS_PGO_EDGES, WS_PGO_OUT,
   WS_CLOUD_IN, WS_CLOUD_POSE, WS_CLOUD_OUT,
+  WS_SEG_BYTES, WS_SEG_WORDS, WS_SEG_COUNTS, WS_SEG_IN, WS_SEG_OUT,
   WS_COUNT
 };
 // the buffers that exist once per feature kind: loamx_ctx::wsk[id][kEdge | kPlane]
@@ -95,6 +96,12 @@ struct loamx_ctx {
     uint32_t coop_forms[2] = {0, 0};  // listed entries associate_knn_coop_kernel gave a row of lanes / a whole wavefront (loamx_ctx_last_assoc_coop_forms)
   } last_assoc_census[2];
   bool last_assoc_census_valid = false;
+
+  // the last segmentation call (loamx_ctx_last_segment_census): its edge counts are n_scans words of WS_SEG_COUNTS
+  struct {
+    bool valid = false, tiles = false;
+    uint32_t H = 0, W = 0, n_scans = 0;
+  } last_segment;
 
   unsigned long long sweep_slots_base[2] = {0, 0};
   unsigned long long features_base = 0;  // events[2] at the last loamx_ctx_reset_kernel_stats

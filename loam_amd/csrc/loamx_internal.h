@@ -10,6 +10,7 @@
 #include "reg_math.h"
 #include "organize_math.h"
 #include "place_math.h"
+#include "segment_math.h"
 #include "xcd_map.h"
 
 namespace loamx {
@@ -537,6 +538,35 @@ void launch_cloud_accumulate(const void* d_points, bool f32, uint32_t stride, co
 void launch_cloud_list(const CloudTable& t, const uint32_t* d_slot, uint32_t n, uint32_t g0, uint8_t* d_keep, uint32_t* d_tiles, hipStream_t s);
 void launch_cloud_emit(const CloudTable& t, double leaf, uint32_t min_points, uint8_t* d_keep, uint32_t* d_tiles, double* d_xyz_out,
                        uint32_t* d_count_out, uint32_t* d_first_out, size_t capacity, uint32_t* d_n_out, hipStream_t s);
+
+/* ---- scan segmentation (segment_kernels.hip; the rule: segment_math.h and loamx.h) ------------------------------------------- */
+constexpr uint32_t kSegTileLines = 16, kSegTileCols = 256;  // the tile a workgroup labels in LDS (loamx_ctx_last_segment_census)
+constexpr uint32_t kSegMaxScans = 65535;                    // scans per call: the scan is the launch grid's y
+constexpr uint32_t kSegStatWords = 8;
+constexpr uint32_t kRegFlagNoSegmentTiles = 262144u;      // (loamx_ctx::reg_flags) every connected edge through the global union
+constexpr uint32_t kSegBlock = 256;                         // cells per workgroup of the per-cell kernels (and per compaction block)
+// scratch of one call, all per scan back to back (HW = H W cells, nb = ceil(HW / kSegBlock))
+struct SegScratch {
+  uint8_t* cls;         // [HW] kSegInvalid / kSegGround / kSegNode
+  uint8_t* ebits;       // [HW] connected edges handed to the global merge: bit 0 right, bit 1 up
+  uint32_t* parent;     // [HW] nodes only
+  uint32_t* root;       // [HW] kSegNoLabel for the others
+  uint32_t* size;       // [HW] at the roots
+  uint32_t* line_max;   // [HW] at the roots
+  uint32_t* block_cnt;  // [nb] accepted roots per block, then their exclusive prefix sum
+  uint32_t* stats;      // [kSegStatWords], zeroed before the launch
+  uint32_t* edges;      // [1] per scan: edges handed to the global merge, zeroed before the launch
+};
+struct SegOutputs {
+  uint8_t* classes;
+  uint32_t *labels, *sizes;
+  void* filtered;  // the input's scalar type; may be the input itself
+  loamx_segment_cluster* clusters;
+  size_t max_clusters;
+  uint32_t* stats;
+};
+void launch_segment(const void* d_scans, bool f32, uint32_t n_scans, const SegParams& P, bool tiles, const SegScratch& ws, const SegOutputs& out,
+                    hipStream_t s);
 
 /* ---- synthetic generator (synth_kernels.hip) --------------------------------------------------- */
 void launch_synth_pairs(uint64_t seed, uint64_t first_pair, size_t n_pairs, uint32_t H, uint32_t W, double sigma,

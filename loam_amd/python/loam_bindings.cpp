@@ -6,7 +6,8 @@
 // and deskewScan (include/loamx.h: "scan sequences"), and the class TargetIndex with a registerFeatures overload that
 // takes it (scan-to-map: "persistent target index" and "map upkeep"), and OrganizeParams / ScanLayout / organizeCloud, the way
 // in for clouds that are not organised scans yet ("unordered clouds into scans"), and PlaceParams / PlaceMatch / PlaceDatabase
-// ("place recognition"), and PoseGraphParams / PoseGraphSummary / PoseGraph ("pose graph"). Point clouds are contiguous (N,3) float64
+// ("place recognition"), and PoseGraphParams / PoseGraphSummary / PoseGraph ("pose graph"), and SegmentationParams / segmentScan
+// ("scan segmentation"). Point clouds are contiguous (N,3) float64
 // arrays handed to the C ABI without per-point objects (a list of 3-vectors is converted once).
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -152,6 +153,38 @@ py::tuple organize_cloud(const py::array_t<T, py::array::c_style>& points, const
                                      src.mutable_data(), stats));
   }
   return py::make_tuple(scan, src);
+}
+
+// segmentScan: an organised (H W, 3) scan as it lies in the array -> (classes, labels, sizes, filtered, clusters (n, 4), stats (8,))
+inline int c_segment(loamx_ctx* c, const double* s, const loamx_lidar_params* l, const loamx_segment_params* p, uint8_t* cl, uint32_t* la, uint32_t* sz,
+                     double* f, loamx_segment_cluster* k, size_t cap, uint32_t* st) {
+  return loamx_segment_scan(c, s, l, p, cl, la, sz, f, k, cap, st);
+}
+inline int c_segment(loamx_ctx* c, const float* s, const loamx_lidar_params* l, const loamx_segment_params* p, uint8_t* cl, uint32_t* la, uint32_t* sz,
+                     float* f, loamx_segment_cluster* k, size_t cap, uint32_t* st) {
+  return loamx_segment_scan_f32(c, s, l, p, cl, la, sz, f, k, cap, st);
+}
+template <typename T>
+py::tuple segment_scan(const py::array_t<T, py::array::c_style>& scan, const loam::LidarParams& lidar, const loam::SegmentationParams& params) {
+  const size_t n = lidar.scan_lines * lidar.points_per_line;
+  if (scan.ndim() != 2 || scan.shape(1) != 3) throw std::runtime_error("scan: expected an (N, 3) array");
+  if ((size_t)scan.shape(0) != n) throw std::runtime_error("LOAM: provided lidar scan size does not match provided lidar parameters");
+  py::array_t<uint8_t> classes((py::ssize_t)n);
+  py::array_t<uint32_t> labels((py::ssize_t)n), sizes((py::ssize_t)n), stats((py::ssize_t)8);
+  py::array_t<T> filtered(std::vector<py::ssize_t>{(py::ssize_t)n, 3});
+  std::vector<loamx_segment_cluster> recs(n);
+  const loamx_lidar_params lp = loam::gpu::toC(lidar);
+  const loamx_segment_params sp = loam::gpu::toC(params);
+  loamx_ctx* ctx = loam::gpu::defaultContext();
+  {
+    py::gil_scoped_release release;
+    loam::gpu::check(ctx, c_segment(ctx, scan.data(), &lp, &sp, classes.mutable_data(), labels.mutable_data(), sizes.mutable_data(),
+                                    filtered.mutable_data(), recs.data(), n, stats.mutable_data()));
+  }
+  const size_t written = stats.data()[7];
+  py::array_t<uint32_t> clusters(std::vector<py::ssize_t>{(py::ssize_t)written, 4});
+  if (written) std::memcpy(clusters.mutable_data(), recs.data(), written * sizeof(loamx_segment_cluster));
+  return py::make_tuple(classes, labels, sizes, filtered, clusters, stats);
 }
 
 loam::Vector3d vec_from(const Arr& a) {
@@ -527,6 +560,19 @@ PYBIND11_MODULE(loam_python, m) {
       .def("lineTangents", [](const loam::ScanLayout& l) { return matrix_to_array(l.lineTangents().data(), l.scanLines() + 1, 1); });
   m.def("organizeCloud", &organize_cloud<float>, py::arg("points"), py::arg("layout"), py::arg("rings") = py::none());
   m.def("organizeCloud", &organize_cloud<double>, py::arg("points"), py::arg("layout"), py::arg("rings") = py::none());
+  // scan segmentation (include/loamx.h: "scan segmentation"): an extension of the reference's surface like organizeCloud
+  py::class_<loam::SegmentationParams>(m, "SegmentationParams")
+      .def(py::init<>())
+      .def_readwrite("ground_lines", &loam::SegmentationParams::ground_lines)
+      .def_readwrite("ground_angle", &loam::SegmentationParams::ground_angle)
+      .def_readwrite("segment_angle", &loam::SegmentationParams::segment_angle)
+      .def_readwrite("min_cluster_points", &loam::SegmentationParams::min_cluster_points)
+      .def_readwrite("min_tall_cluster_points", &loam::SegmentationParams::min_tall_cluster_points)
+      .def_readwrite("min_tall_cluster_lines", &loam::SegmentationParams::min_tall_cluster_lines)
+      .def_readwrite("drop_outliers", &loam::SegmentationParams::drop_outliers)
+      .def_readwrite("drop_ground", &loam::SegmentationParams::drop_ground);
+  m.def("segmentScan", &segment_scan<float>, py::arg("scan"), py::arg("lidar_params"), py::arg("params") = loam::SegmentationParams());
+  m.def("segmentScan", &segment_scan<double>, py::arg("scan"), py::arg("lidar_params"), py::arg("params") = loam::SegmentationParams());
   // place recognition (include/loamx.h: "place recognition"): an extension like TargetIndex
   py::class_<loam::PlaceParams>(m, "PlaceParams")
       .def(py::init<>())
