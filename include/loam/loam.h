@@ -10,3 +10,4 @@
 #include "posegraph.h"
 #include "registration.h"
 #include "segment.h"
+#include "visibility.h"

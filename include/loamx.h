@@ -259,6 +259,7 @@ int loamx_ctx_last_assoc_coop_forms(loamx_ctx* ctx, int which_kind, uint32_t out
  *   input checks:  CHECK_FINITE (see "Non-finite input" below)
  *   cloud map:     NO_CLOUDMAP_COMBINE (one claim per point instead of one per run of a wavefront: the same bytes, see "cloud map")
  *   segmentation:  NO_SEGMENT_TILES (every connected edge through the global union, no tile labelling in LDS: the same bytes, see "scan segmentation")
+ *   map cleaning:  NO_VISIBILITY_RANGES (the votes kernel reads the scans' points, no first launch that writes every cell's squared range: the same bytes, see "map cleaning")
  * Unknown name: LOAMX_ERR_BAD_PARAM.
  *
  * Non-finite input. The reference is undefined on NaN / Inf coordinates (loam/include/loam/features-inl.h:38 sorts on
@@ -1075,6 +1076,103 @@ int loamx_segment_scan_f32(loamx_ctx* ctx, const float* scan, const loamx_lidar_
  * W - 1 (the seam, even where one tile holds both ends); in the global-only form always. Synchronises. LOAMX_ERR_BAD_PARAM before
  * any segmentation call. Never part of a result. */
 int loamx_ctx_last_segment_census(loamx_ctx* ctx, uint64_t out[5]);
+
+/* ---- map cleaning (no reference counterpart; the visibility check of Removert and of OctoMap-style free-space carving). A cloud
+ * map keeps everything the sensor ever hit, a passing car included. For every pair of a map point and a scan this asks: did the
+ * beam that looked towards the point stop at it, stop before it, or pass through it? A point that many scans saw through and few
+ * confirmed belonged to a moving object. The votes are integer counts, so every schedule and both forms of the kernel give the
+ * same bytes, and a numpy model is compared by equality (tests/visibility_common.py).
+ *
+ * The rule (loam_amd/csrc/visibility_math.h). FP64 throughout, float scans are widened first; every product, sum and difference
+ * is one operation rounded on its own, in the order written; the only libm call is sqrt. The host forms
+ * min2 = min_range min_range and max2 = max_range max_range once per call.
+ * Per map point m (world frame) and scan s with pose world_T_s = (q, t) read from DEVICE memory (n_scans x 7 doubles):
+ *   1 sensor frame  d = m - t component-wise; p = quat_rotate(conj(q), d) with conj(q) = (-qx, -qy, -qz, qw), quat_rotate the
+ *                   rotation of Pose3d::act (v + qw (2 u x v) + u x (2 u x v)); the quaternion is used as given.
+ *   2 has a place   the validity test of "unordered clouds into scans" must hold for p (finite, rho2 = x x + y y >= 1e-100),
+ *                   with r2 = rho2 + z z; otherwise the verdict is NONE. If !(r2 >= min2) || !(r2 <= max2): NONE.
+ *   3 cell          the organiser's cell of p WITHOUT ring numbers: the column by the layout's column boundaries, the line by the
+ *                   elevation; the layout's ring map and keep rule are ignored. Outside the elevation fan: NONE. Otherwise
+ *                   l = cell / W, c = cell % W.
+ *   4 bounds        dist = sqrt(r2); tol = margin + margin_rel dist; lo = dist - tol, taken as 0 when negative; hi = dist + tol;
+ *                   lo2 = lo lo; hi2 = hi hi.
+ *   5 window        the cells (l + dl, (c + dc) mod W) for |dl| <= window_lines with 0 <= l + dl < H and |dc| <= window_cols: lines
+ *                   do not wrap, columns do. (A cell met twice when 2 window_cols + 1 > W changes nothing: the reductions below
+ *                   are `any` and `all`.) A cell is USABLE iff its three coordinates are finite and r2c = (x x + y y) + z z
+ *                   satisfies r2c >= min2: NaN cells never are, (0, 0, 0) cells are not while min_range > 0. A usable cell AGREES iff r2c >= lo2 && r2c <= hi2
+ *                   and is BEYOND iff r2c > hi2.
+ *   6 verdict       EMPTY: no usable cell. AGREE: some usable cell agrees. THROUGH: otherwise, if every usable cell is beyond.
+ *                   OCCLUDED: otherwise.
+ *   7 votes         each field of the point's loamx_visibility_tally counts the scans with that verdict; NONE counts nowhere.
+ * A point is DYNAMIC iff through >= min_through && (double) through >= through_ratio (double) agree (one rounded product).
+ * The default window of one line and one column each way is what makes the test usable on ground seen at a grazing angle: the
+ * beam through the point's own cell hits the ground metres further on, but the line below returns from in front of the point,
+ * THROUGH needs every usable cell beyond, and the verdict is OCCLUDED. */
+typedef struct {
+  double min_range;      /* 1.0 */
+  double max_range;      /* 80.0 */
+  double margin;         /* 0.3 */
+  double margin_rel;     /* 0.01 */
+  uint32_t window_lines; /* 1; at most 3 */
+  uint32_t window_cols;  /* 1; at most 3 */
+  uint32_t min_through;  /* 2 */
+  double through_ratio;  /* 1.0 */
+} loamx_visibility_params;
+typedef struct {
+  uint32_t through, agree, occluded, empty;
+} loamx_visibility_tally;
+typedef struct {
+  uint32_t form;           /* 1: the window reads squared ranges a first launch wrote; 0: it reads the scans' points (NO_VISIBILITY_RANGES) */
+  uint32_t scan_chunks;    /* workgroup rows the scans were dealt over */
+  uint64_t in_range_pairs; /* (point, scan) pairs that passed step 2 */
+  uint64_t projected_pairs; /* ... and step 3: the sum of all four fields over all points that this call added */
+} loamx_visibility_census;
+void loamx_default_visibility_params(loamx_visibility_params* p);
+/* Parameter refusals of every entry point below. LOAMX_ERR_BAD_PARAM: a non-finite double, min_range < 0, max_range < min_range,
+ * margin < 0, margin_rel < 0, through_ratio < 0. LOAMX_ERR_UNSUPPORTED: window_lines > 3 or window_cols > 3. */
+/* The votes of n_points device-resident map points (double, world frame, point_stride scalars apart: what loamx_cloud_map_emit_dev
+ * writes) over n_scans device-resident organised scans of the layout's shape (n_scans x H W x 3 scalars, double or _f32 float) at
+ * d_poses (DEVICE, n_scans x 7: what loamx_compose_trajectory_dev and loamx_pose_graph_optimize_dev leave). accumulate == 0: every
+ * entry of d_votes is written; 1: the counts are added to what d_votes holds (a drive in several calls). Asynchronous on the
+ * context's stream; synchronises only when the workspace has to grow. LOAMX_ERR_BAD_PARAM: a null layout, params, d_votes, d_points
+ * or d_scans, point_stride < 3, a layout of another device, a null d_poses with scans; LOAMX_ERR_UNSUPPORTED: 2^32 points or more,
+ * 2^31 scans or more, a point_stride beyond 32 bits. A refused call writes nothing. n_points == 0 or n_scans == 0: LOAMX_OK, and
+ * with accumulate == 0 the votes are zeroed (the pointers of what is absent may then be NULL).
+ *
+ * Kernels (loam_amd/csrc/visibility_kernels.hip): one map point per thread, the scans dealt over workgroup rows of 32 (more when
+ * there are more than 65535 x 32 scans); the layout's two tables are staged in LDS when they fit 48 KB; the range test comes
+ * first; the counts stay in registers and leave as one store per point (one row, no accumulation) or one integer atomic per
+ * non-zero field. A first launch writes every cell's squared range (negative: not usable) into grow-on-demand workspace (8 bytes
+ * per cell of the call's scans) and the window reads 8 bytes per cell. Context option NO_VISIBILITY_RANGES: no first launch, the
+ * window reads the scans' points and squares them itself — the same bytes, no workspace, 1.27 times the time on the drive of
+ * tools/bench_visibility.py. */
+int loamx_visibility_votes_dev(loamx_ctx* ctx, const loamx_scan_layout* layout, const double* d_points, size_t point_stride, size_t n_points,
+                               const double* d_scans, size_t n_scans, const double* d_poses, const loamx_visibility_params* params,
+                               int accumulate, loamx_visibility_tally* d_votes);
+int loamx_visibility_votes_dev_f32(loamx_ctx* ctx, const loamx_scan_layout* layout, const double* d_points, size_t point_stride, size_t n_points,
+                                   const float* d_scans, size_t n_scans, const double* d_poses, const loamx_visibility_params* params,
+                                   int accumulate, loamx_visibility_tally* d_votes);
+/* The decision per point and the ordered compaction of the points that stay (never a sort: kept points keep their input order).
+ * Outputs, each may be NULL: d_dynamic_out (uint8 per point, n_points entries, 1 = dynamic); d_static_xyz_out (capacity x 3: the
+ * kept points' coordinates, read from d_points; ignored when d_points is NULL); d_static_index_out (capacity: their indices).
+ * *d_n_static_out is the number of kept points even when it exceeds capacity; every entry below min(n, capacity) of the two
+ * compacted outputs is written and nothing beyond it. Asynchronous; synchronises only when the workspace has to grow.
+ * LOAMX_ERR_BAD_PARAM: a null params or d_n_static_out, a null d_votes with points, point_stride < 3 with a non-null d_points, a
+ * null d_static_xyz_out with a non-null d_points and capacity > 0; LOAMX_ERR_UNSUPPORTED: 2^32 points or more. A refused call
+ * writes nothing. */
+int loamx_visibility_filter_dev(loamx_ctx* ctx, const loamx_visibility_tally* d_votes, size_t n_points, const loamx_visibility_params* params,
+                                const double* d_points, size_t point_stride, uint8_t* d_dynamic_out, double* d_static_xyz_out,
+                                uint32_t* d_static_index_out, size_t capacity, uint32_t* d_n_static_out);
+/* host memory in and out, synchronous: votes has n_points entries, all written */
+int loamx_visibility_votes(loamx_ctx* ctx, const loamx_scan_layout* layout, const double* points, size_t point_stride, size_t n_points,
+                           const double* scans, size_t n_scans, const double* poses, const loamx_visibility_params* params,
+                           loamx_visibility_tally* votes);
+int loamx_visibility_votes_f32(loamx_ctx* ctx, const loamx_scan_layout* layout, const double* points, size_t point_stride, size_t n_points,
+                               const float* scans, size_t n_scans, const double* poses, const loamx_visibility_params* params,
+                               loamx_visibility_tally* votes);
+/* The last votes call of the context (device or host form). Synchronises. LOAMX_ERR_BAD_PARAM before any votes call. Never part of
+ * a result. */
+int loamx_ctx_last_visibility_census(loamx_ctx* ctx, loamx_visibility_census* out);
 
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are

@@ -281,6 +281,47 @@ def segment_constants(params=None):
     return float(out[0]), float(out[1])
 
 
+class VisibilityParamsStruct(C.Structure):
+    """loamx_visibility_params (include/loamx.h)"""
+    _fields_ = [("min_range", C.c_double), ("max_range", C.c_double), ("margin", C.c_double), ("margin_rel", C.c_double),
+                ("window_lines", C.c_uint32), ("window_cols", C.c_uint32), ("min_through", C.c_uint32), ("through_ratio", C.c_double)]
+
+
+class VisibilityParams:
+    """The rule of the map cleaning (loamx_visibility_params): the range band in which a scan can vote on a point, the margin around
+    the point's range, the window of cells looked at, and the decision over the votes. Anything left out takes the C ABI's default."""
+    FIELDS = tuple(f[0] for f in VisibilityParamsStruct._fields_)
+    INTEGERS = ("window_lines", "window_cols", "min_through")
+
+    def __init__(self, **kw):
+        d = VisibilityParamsStruct()
+        load().loamx_default_visibility_params(C.byref(d))
+        for name in self.FIELDS:
+            setattr(self, name, getattr(d, name))
+        for name, v in kw.items():
+            if name not in self.FIELDS:
+                raise TypeError(f"VisibilityParams: no field {name}")
+            setattr(self, name, v)
+
+    def struct(self):
+        for name in self.INTEGERS:
+            if not 0 <= int(getattr(self, name)) <= 0xFFFFFFFF:
+                raise ValueError(f"VisibilityParams: {name} does not fit 32 bits")
+        return VisibilityParamsStruct(*(int(getattr(self, n)) if n in self.INTEGERS else float(getattr(self, n)) for n in self.FIELDS))
+
+
+# loamx_visibility_tally: the votes of one map point; loamx_visibility_census
+VISIBILITY_VOTES_DTYPE = np.dtype([("through", np.uint32), ("agree", np.uint32), ("occluded", np.uint32), ("empty", np.uint32)])
+VISIBILITY_SCAN_CHUNK = 32  # scans per workgroup row of the votes kernel
+
+
+class VisibilityCensusStruct(C.Structure):
+    _fields_ = [("form", C.c_uint32), ("scan_chunks", C.c_uint32), ("in_range_pairs", C.c_uint64), ("projected_pairs", C.c_uint64)]
+
+
+VisibilityCensus = collections.namedtuple("VisibilityCensus", "form scan_chunks in_range_pairs projected_pairs")
+
+
 class PgoParamsStruct(C.Structure):
     """loamx_pgo_params (include/loamx.h)"""
     _fields_ = [("max_iterations", C.c_uint32), ("max_pcg_iterations", C.c_uint32), ("pcg_tolerance", C.c_double),
@@ -359,6 +400,8 @@ EXPORTS = [
     "loamx_cloud_map_add_cloud", "loamx_cloud_map_add_cloud_f32", "loamx_cloud_map_emit", "loamx_cloud_map_claims_read",
     "loamx_default_segment_params", "loamx_segment_constants", "loamx_segment_scans_dev", "loamx_segment_scans_dev_f32",
     "loamx_segment_scan", "loamx_segment_scan_f32", "loamx_ctx_last_segment_census",
+    "loamx_default_visibility_params", "loamx_visibility_votes_dev", "loamx_visibility_votes_dev_f32", "loamx_visibility_filter_dev",
+    "loamx_visibility_votes", "loamx_visibility_votes_f32", "loamx_ctx_last_visibility_census",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -621,6 +664,14 @@ def load(build_if_missing=True):
     lib.loamx_segment_scan.argtypes = [vp, vp, C.POINTER(LidarParams), C.POINTER(SegmentParamsStruct), vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.loamx_segment_scan_f32.argtypes = lib.loamx_segment_scan.argtypes
     lib.loamx_ctx_last_segment_census.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.loamx_default_visibility_params.argtypes = [C.POINTER(VisibilityParamsStruct)]
+    lib.loamx_default_visibility_params.restype = None
+    lib.loamx_visibility_votes_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, C.POINTER(VisibilityParamsStruct), C.c_int, vp]
+    lib.loamx_visibility_votes_dev_f32.argtypes = lib.loamx_visibility_votes_dev.argtypes
+    lib.loamx_visibility_filter_dev.argtypes = [vp, vp, C.c_size_t, C.POINTER(VisibilityParamsStruct), vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp]
+    lib.loamx_visibility_votes.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, C.POINTER(VisibilityParamsStruct), vp]
+    lib.loamx_visibility_votes_f32.argtypes = lib.loamx_visibility_votes.argtypes
+    lib.loamx_ctx_last_visibility_census.argtypes = [vp, C.POINTER(VisibilityCensusStruct)]
     lib.loamx_pgo_default_params.argtypes = [C.POINTER(PgoParamsStruct)]
     lib.loamx_pgo_default_params.restype = None
     lib.loamx_pose_graph_optimize_dev.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(PgoParamsStruct), vp]
@@ -1628,6 +1679,60 @@ class Context:
         v = (C.c_uint64 * 5)()
         self._check(self.lib.loamx_ctx_last_segment_census(self.h, v))
         return SegmentCensus(int(v[0]), int(v[1]), int(v[2]), int(v[3]), bool(v[4]))
+
+    # ---- map cleaning (include/loamx.h, "map cleaning") ---------------------------------------------------------
+    def visibility_votes_dev(self, layout, d_points, point_stride, n_points, d_scans, n_scans, d_poses, d_votes, params=None, accumulate=False,
+                             f32=False):
+        """The votes of n_points device-resident map points (double, world frame) over n_scans device-resident scans of the
+        layout's shape at d_poses (device, n_scans x 7) into d_votes (n_points VISIBILITY_VOTES_DTYPE records), written or, with
+        accumulate, added to (loamx_visibility_votes_dev[_f32]; f32 is the scans' type). Asynchronous on the context's stream."""
+        if int(n_points) < 0 or int(n_scans) < 0:
+            raise ValueError("visibility_votes_dev: n_points and n_scans must be >= 0")
+        st = (params or VisibilityParams()).struct()
+        fn = self.lib.loamx_visibility_votes_dev_f32 if f32 else self.lib.loamx_visibility_votes_dev
+        self._check(fn(self.h, layout._handle(), d_points or None, int(point_stride), int(n_points), d_scans or None, int(n_scans), d_poses or None,
+                       C.byref(st), 1 if accumulate else 0, d_votes or None))
+
+    def visibility_votes(self, points, scans, poses, layout, params=None):
+        """Host form: points (n, k >= 3) float64 world, scans (n_scans, H W, 3) float64 or float32, poses (n_scans, 7) -> (n,)
+        VISIBILITY_VOTES_DTYPE (loamx_visibility_votes[_f32]; synchronous)."""
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] < 3:
+            raise ValueError(f"visibility_votes: points must be (n, k >= 3), not {pts.shape}")
+        sc = np.asarray(scans)
+        if sc.dtype != np.float32:
+            sc = np.asarray(sc, dtype=np.float64)
+        sc = np.ascontiguousarray(sc)
+        if sc.size % (layout.cells * 3):
+            raise ValueError(f"visibility_votes: the scans hold {sc.size} scalars, no multiple of {layout.cells} x 3")
+        n_scans = sc.size // (layout.cells * 3)
+        po = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        if len(po) != n_scans:
+            raise ValueError(f"visibility_votes: {len(po)} poses for {n_scans} scans")
+        st = (params or VisibilityParams()).struct()
+        votes = np.zeros(len(pts), dtype=VISIBILITY_VOTES_DTYPE)
+        fn = self.lib.loamx_visibility_votes_f32 if sc.dtype == np.float32 else self.lib.loamx_visibility_votes
+        self._check(fn(self.h, layout._handle(), pts.ctypes.data if len(pts) else None, pts.shape[1], len(pts), sc.ctypes.data if n_scans else None,
+                       n_scans, po.ctypes.data if n_scans else None, C.byref(st), votes.ctypes.data if len(pts) else None))
+        return votes
+
+    def visibility_filter_dev(self, d_votes, n_points, d_n_static_out, params=None, d_points=0, point_stride=3, d_dynamic_out=0, d_static_xyz_out=0,
+                              d_static_index_out=0, capacity=0):
+        """The decision per point and the ordered compaction of the points that stay (loamx_visibility_filter_dev); every output
+        but d_n_static_out is a device address or 0. Asynchronous on the context's stream."""
+        if int(n_points) < 0 or int(capacity) < 0:
+            raise ValueError("visibility_filter_dev: n_points and capacity must be >= 0")
+        st = (params or VisibilityParams()).struct()
+        self._check(self.lib.loamx_visibility_filter_dev(self.h, d_votes or None, int(n_points), C.byref(st), d_points or None, int(point_stride),
+                                                         d_dynamic_out or None, d_static_xyz_out or None, d_static_index_out or None, int(capacity),
+                                                         d_n_static_out or None))
+
+    def last_visibility_census(self):
+        """The last votes call of this context (loamx_ctx_last_visibility_census): the form (1 ranges, 0 scans), the workgroup rows
+        the scans were dealt over, the pairs in range and the pairs that had a cell. Synchronises."""
+        v = VisibilityCensusStruct()
+        self._check(self.lib.loamx_ctx_last_visibility_census(self.h, C.byref(v)))
+        return VisibilityCensus(int(v.form), int(v.scan_chunks), int(v.in_range_pairs), int(v.projected_pairs))
 
     # ---- place recognition (include/loamx.h, "place recognition") --------------------------------------------
     def place_db(self, params=None):

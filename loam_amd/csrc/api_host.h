@@ -28,6 +28,7 @@ enum WsId {
   WS_PGO_WORK, WS_PGO_POSES, WS_PGO_FIXED, WS_PGO_EDGES, WS_PGO_OUT,
   WS_CLOUD_IN, WS_CLOUD_POSE, WS_CLOUD_OUT,
   WS_SEG_BYTES, WS_SEG_WORDS, WS_SEG_COUNTS, WS_SEG_IN, WS_SEG_OUT,
+  WS_VIS_RANGES, WS_VIS_CENSUS, WS_VIS_KEEP, WS_VIS_TILES, WS_VIS_IN, WS_VIS_SCANS, WS_VIS_POSES, WS_VIS_OUT,
   WS_COUNT
 };
 // the buffers that exist once per feature kind: loamx_ctx::wsk[id][kEdge | kPlane]
@@ -102,6 +103,11 @@ struct loamx_ctx {
     bool valid = false, tiles = false;
     uint32_t H = 0, W = 0, n_scans = 0;
   } last_segment;
+  // the last visibility votes call (loamx_ctx_last_visibility_census): its pair counts are two words of WS_VIS_CENSUS
+  struct {
+    bool valid = false, counted = false;  // counted: kernels ran and left the words (otherwise both counts are 0)
+    uint32_t form = 0, scan_chunks = 0;
+  } last_visibility;
 
   unsigned long long sweep_slots_base[2] = {0, 0};
   unsigned long long features_base = 0;  // events[2] at the last loamx_ctx_reset_kernel_stats

@@ -2,16 +2,6 @@
 // two host-computed tables, the device-resident batch entry points and the one-cloud host forms.
 #include "api_host.h"
 
-struct loamx_scan_layout {
-  int device = 0;
-  uint32_t H = 0, W = 0, clockwise = 0, keep = 0;
-  std::vector<double> col_dirs, line_tans;  // the uploaded bytes (loamx_scan_layout_tables)
-  std::vector<uint16_t> ring_map;
-  double* d_col_dirs = nullptr;
-  double* d_line_tans = nullptr;
-  uint16_t* d_ring_map = nullptr;
-};
-
 using namespace loamx;
 
 namespace {

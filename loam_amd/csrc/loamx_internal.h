@@ -5,12 +5,15 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <vector>
+
 #include "../../include/loamx.h"
 #include "extract_math.h"
 #include "reg_math.h"
 #include "organize_math.h"
 #include "place_math.h"
 #include "segment_math.h"
+#include "visibility_math.h"
 #include "xcd_map.h"
 
 namespace loamx {
@@ -423,6 +426,19 @@ void launch_organize(const void* d_points, bool f32, uint32_t stride, const uint
                      unsigned long long max_points, const OrgTables& L, bool nearest, uint32_t* winner, unsigned long long* range,
                      uint32_t* cell, uint32_t* counters, void* d_scans, uint32_t* d_src_idx, uint32_t* d_stats, hipStream_t s);
 
+}  // namespace loamx
+// a scan layout (api_organize.hip creates and frees it; api_visibility.hip reads its shape and device tables)
+struct loamx_scan_layout {
+  int device = 0;
+  uint32_t H = 0, W = 0, clockwise = 0, keep = 0;
+  std::vector<double> col_dirs, line_tans;  // the uploaded bytes (loamx_scan_layout_tables)
+  std::vector<uint16_t> ring_map;
+  double* d_col_dirs = nullptr;
+  double* d_line_tans = nullptr;
+  uint16_t* d_ring_map = nullptr;
+};
+namespace loamx {
+
 /* ---- place recognition (place_kernels.hip; the rule: place_math.h and loamx.h) ---------------------------------------------- */
 constexpr uint32_t kPlaceSelectChunk = 1024;  // records a workgroup of the selection ranks at once
 // one candidate of the key stage: squared key distance and entry id (kPlaceNoKeyDist / kPlaceNoId: none)
@@ -567,6 +583,31 @@ struct SegOutputs {
 };
 void launch_segment(const void* d_scans, bool f32, uint32_t n_scans, const SegParams& P, bool tiles, const SegScratch& ws, const SegOutputs& out,
                     hipStream_t s);
+
+/* ---- map cleaning (visibility_kernels.hip; the rule: visibility_math.h and loamx.h) ------------------------------------------------ */
+constexpr uint32_t kVisScanChunk = 32;            // scans per workgroup row of the votes kernel (more when n_scans > 65535 x 32)
+constexpr size_t kVisLdsTableBytes = 48u << 10;   // layout tables up to this size are staged in LDS
+constexpr uint32_t kRegFlagNoVisibilityRanges = 524288u;  // (loamx_ctx::reg_flags) the window reads the scans' points, no first launch that writes every cell's squared range
+inline size_t vis_table_bytes(uint32_t H, uint32_t W) { return (2 * (size_t)W + (size_t)H + 1) * sizeof(double); }
+struct VisVotesCall {
+  const double* d_points;
+  uint32_t stride, n_points;
+  const void* d_scans;
+  bool f32;
+  const double* d_ranges;  // n_scans x H W squared ranges (launch_visibility_ranges); nullptr: the window reads the scans
+  uint32_t n_scans, chunk;
+  const double* d_poses;
+  OrgTables tab;
+  VisRule rule;
+  bool atomic;  // the counts are added to the votes (zeroed or kept by the caller); false: stored
+  loamx_visibility_tally* d_votes;
+  unsigned long long* d_census;  // [2] in-range pairs, projected pairs: added to
+};
+void launch_visibility_ranges(const void* d_scans, bool f32, unsigned long long n_cells, double min2, double* d_ranges, hipStream_t s);
+void launch_visibility_votes(const VisVotesCall& c, hipStream_t s);
+void launch_visibility_filter(const loamx_visibility_tally* d_votes, uint32_t n, uint32_t min_through, double through_ratio, const double* d_points,
+                              uint32_t stride, uint8_t* d_keep, uint32_t* d_tiles, uint8_t* d_dynamic_out, double* d_xyz_out, uint32_t* d_index_out,
+                              size_t capacity, uint32_t* d_n_out, hipStream_t s);
 
 /* ---- synthetic generator (synth_kernels.hip) --------------------------------------------------- */
 void launch_synth_pairs(uint64_t seed, uint64_t first_pair, size_t n_pairs, uint32_t H, uint32_t W, double sigma,

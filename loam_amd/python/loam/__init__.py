@@ -8,3 +8,4 @@ from .loam_python import deskewScan, registerScanSequence  # noqa: F401  (extens
 from .loam_python import RegistrationInformation, registrationInformation  # noqa: F401  (extension: information matrix)
 from .loam_python import PoseGraph, PoseGraphParams, PoseGraphSummary  # noqa: F401  (extension: pose graph)
 from .loam_python import CloudMap, CloudMapParams  # noqa: F401  (extension: cloud map)
+from .loam_python import VisibilityParams, removeDynamicPoints, visibilityVotes  # noqa: F401  (extension: map cleaning)

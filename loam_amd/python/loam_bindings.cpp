@@ -7,8 +7,8 @@
 // takes it (scan-to-map: "persistent target index" and "map upkeep"), and OrganizeParams / ScanLayout / organizeCloud, the way
 // in for clouds that are not organised scans yet ("unordered clouds into scans"), and PlaceParams / PlaceMatch / PlaceDatabase
 // ("place recognition"), and PoseGraphParams / PoseGraphSummary / PoseGraph ("pose graph"), and SegmentationParams / segmentScan
-// ("scan segmentation"). Point clouds are contiguous (N,3) float64
-// arrays handed to the C ABI without per-point objects (a list of 3-vectors is converted once).
+// ("scan segmentation"), and VisibilityParams / visibilityVotes / removeDynamicPoints ("map cleaning"). Point clouds are
+// contiguous (N,3) float64 arrays handed to the C ABI without per-point objects (a list of 3-vectors is converted once).
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -153,6 +153,60 @@ py::tuple organize_cloud(const py::array_t<T, py::array::c_style>& points, const
                                      src.mutable_data(), stats));
   }
   return py::make_tuple(scan, src);
+}
+
+// visibilityVotes: map points (N, 3) or (N, k) float64, scans (n_scans, H W, 3) as they lie in the array, one pose per scan
+// -> votes (N, 4) uint32 [through, agree, occluded, empty]
+inline int c_visibility_votes(loamx_ctx* c, const loamx_scan_layout* l, const double* m, size_t stride, size_t n, const double* s, size_t ns,
+                              const double* poses, const loamx_visibility_params* p, loamx_visibility_tally* v) {
+  return loamx_visibility_votes(c, l, m, stride, n, s, ns, poses, p, v);
+}
+inline int c_visibility_votes(loamx_ctx* c, const loamx_scan_layout* l, const double* m, size_t stride, size_t n, const float* s, size_t ns,
+                              const double* poses, const loamx_visibility_params* p, loamx_visibility_tally* v) {
+  return loamx_visibility_votes_f32(c, l, m, stride, n, s, ns, poses, p, v);
+}
+template <typename T>
+py::array_t<uint32_t> visibility_votes(const py::array_t<double, py::array::c_style>& map_points, const py::array_t<T, py::array::c_style>& scans,
+                                       const std::vector<loam::Pose3d>& world_T_scan, const loam::ScanLayout& layout,
+                                       const loam::VisibilityParams& params) {
+  if (map_points.ndim() != 2 || map_points.shape(1) < 3) throw std::runtime_error("map_points: expected an (N, 3) or (N, k) float64 array");
+  const size_t n = (size_t)map_points.shape(0), n_scans = world_T_scan.size();
+  if ((size_t)scans.size() != n_scans * layout.cells() * 3) throw std::runtime_error("scans: expected (n_scans, H W, 3) with one pose per scan");
+  std::vector<double> poses(7 * n_scans);
+  for (size_t i = 0; i < n_scans; i++) world_T_scan[i].toArray(poses.data() + 7 * i);
+  py::array_t<uint32_t> votes(std::vector<py::ssize_t>{(py::ssize_t)n, 4});
+  static_assert(sizeof(loamx_visibility_tally) == 4 * sizeof(uint32_t), "votes travel as rows of four words");
+  const loamx_visibility_params vp = loam::gpu::toC(params);
+  loamx_ctx* ctx = loam::gpu::defaultContext();
+  {
+    py::gil_scoped_release release;
+    loam::gpu::check(ctx, c_visibility_votes(ctx, layout.handle(), map_points.data(), (size_t)map_points.shape(1), n, scans.data(), n_scans, poses.data(),
+                                             &vp, reinterpret_cast<loamx_visibility_tally*>(votes.mutable_data())));
+  }
+  return votes;
+}
+// removeDynamicPoints: -> (dynamic (N,) uint8, static_index (K,) uint32, static_points (K, 3) float64)
+py::tuple remove_dynamic_points(const py::array_t<double, py::array::c_style>& map_points,
+                                const py::array_t<uint32_t, py::array::c_style | py::array::forcecast>& votes, const loam::VisibilityParams& params) {
+  if (map_points.ndim() != 2 || map_points.shape(1) < 3) throw std::runtime_error("map_points: expected an (N, 3) or (N, k) float64 array");
+  const size_t n = (size_t)map_points.shape(0), stride = (size_t)map_points.shape(1);
+  if (votes.ndim() != 2 || (size_t)votes.shape(0) != n || votes.shape(1) != 4) throw std::runtime_error("votes: expected an (N, 4) uint32 array");
+  struct P3 {
+    double x, y, z;
+  };
+  std::vector<P3> pts(n);
+  for (size_t i = 0; i < n; i++) pts[i] = P3{map_points.data()[i * stride], map_points.data()[i * stride + 1], map_points.data()[i * stride + 2]};
+  std::vector<loam::VisibilityVotes> v(n);
+  if (n) std::memcpy(v.data(), votes.data(), n * sizeof(loam::VisibilityVotes));
+  const auto cleaned = loam::removeDynamicPoints(pts, v, params);
+  const size_t k = cleaned.static_index.size();
+  py::array_t<uint8_t> dynamic((py::ssize_t)n);
+  py::array_t<uint32_t> index((py::ssize_t)k);
+  py::array_t<double> kept(std::vector<py::ssize_t>{(py::ssize_t)k, 3});
+  if (n) std::memcpy(dynamic.mutable_data(), cleaned.dynamic.data(), n);
+  if (k) std::memcpy(index.mutable_data(), cleaned.static_index.data(), k * sizeof(uint32_t));
+  if (k) std::memcpy(kept.mutable_data(), cleaned.static_points.data(), k * sizeof(P3));
+  return py::make_tuple(dynamic, index, kept);
 }
 
 // segmentScan: an organised (H W, 3) scan as it lies in the array -> (classes, labels, sizes, filtered, clusters (n, 4), stats (8,))
@@ -573,6 +627,23 @@ PYBIND11_MODULE(loam_python, m) {
       .def_readwrite("drop_ground", &loam::SegmentationParams::drop_ground);
   m.def("segmentScan", &segment_scan<float>, py::arg("scan"), py::arg("lidar_params"), py::arg("params") = loam::SegmentationParams());
   m.def("segmentScan", &segment_scan<double>, py::arg("scan"), py::arg("lidar_params"), py::arg("params") = loam::SegmentationParams());
+
+  // map cleaning (include/loamx.h: "map cleaning"): an extension of the reference's surface like segmentScan
+  py::class_<loam::VisibilityParams>(m, "VisibilityParams")
+      .def(py::init<>())
+      .def_readwrite("min_range", &loam::VisibilityParams::min_range)
+      .def_readwrite("max_range", &loam::VisibilityParams::max_range)
+      .def_readwrite("margin", &loam::VisibilityParams::margin)
+      .def_readwrite("margin_rel", &loam::VisibilityParams::margin_rel)
+      .def_readwrite("window_lines", &loam::VisibilityParams::window_lines)
+      .def_readwrite("window_cols", &loam::VisibilityParams::window_cols)
+      .def_readwrite("min_through", &loam::VisibilityParams::min_through)
+      .def_readwrite("through_ratio", &loam::VisibilityParams::through_ratio);
+  m.def("visibilityVotes", &visibility_votes<float>, py::arg("map_points"), py::arg("scans"), py::arg("world_T_scan"), py::arg("layout"),
+        py::arg("params") = loam::VisibilityParams());
+  m.def("visibilityVotes", &visibility_votes<double>, py::arg("map_points"), py::arg("scans"), py::arg("world_T_scan"), py::arg("layout"),
+        py::arg("params") = loam::VisibilityParams());
+  m.def("removeDynamicPoints", &remove_dynamic_points, py::arg("map_points"), py::arg("votes"), py::arg("params") = loam::VisibilityParams());
   // place recognition (include/loamx.h: "place recognition"): an extension like TargetIndex
   py::class_<loam::PlaceParams>(m, "PlaceParams")
       .def(py::init<>())
