@@ -5,6 +5,7 @@
 #include "features.h"
 #include "geometry.h"
 #include "kdtree.h"
+#include "occupancy.h"
 #include "organize.h"
 #include "place.h"
 #include "posegraph.h"

@@ -1,0 +1,136 @@
+/** @brief Extension (not in the reference): the occupancy map on the device, free space by ray traversal.
+ *
+ * An OccupancyMap takes scans (or any clouds) at their poses and walks every beam from the sensor to its return through a voxel
+ * grid: the voxel of the return counts a hit, every voxel in front of it a pass. A voxel is then occupied, free or unknown
+ * (never seen), the distinction OctoMap provides. The counts are integers, so the map does not depend on how the device
+ * schedules its threads or on how a drive is split into calls. It is read per point, as a dense box of voxels, or as the 2-D
+ * grid a planner takes. The rule is written out in loamx.h ("occupancy map").
+ */
+#pragma once
+#include <array>
+#include <cstdint>
+#include <memory>
+#include <stdexcept>
+#include <vector>
+
+#include "common.h"
+#include "geometry.h"
+
+namespace loam {
+
+/// LOAMX_OCC_*: the state of a voxel
+enum class Occupancy : uint8_t { UNKNOWN = 0, FREE = 1, OCCUPIED = 2 };
+
+/// loamx_occupancy_params; the defaults are loamx_default_occupancy_params'
+struct OccupancyParams {
+  double leaf = 0.2;        ///< voxel edge
+  double min_range = 0.5;   ///< returns nearer to the sensor are dropped (the all-zero cells of an organised scan among them)
+  double max_range = 80.0;  ///< returns farther away make no hit; with clip_long their beam is walked up to this range
+  double end_margin = 0.2;  ///< a walk stops this far in front of its return
+  bool clip_long = true;
+  uint32_t min_hits = 1;    ///< occupied: hits >= min_hits and hits >= occ_ratio x passes
+  double occ_ratio = 0.0;   ///< 0: a hit always wins; raise it to let passes erase hits
+  uint32_t min_passes = 1;  ///< free: not occupied and passes >= min_passes
+};
+
+/// loamx_occupancy_stats
+struct OccupancyStats {
+  uint64_t rays_offered = 0, rays_hit = 0, invalid = 0, range_short = 0, range_long = 0, outside = 0, visits = 0, voxels = 0, overflow = 0;
+};
+
+/// What OccupancyMap::query and ::box return: counts[2 i] hits and counts[2 i + 1] passes of entry i, states[i] its state
+struct OccupancyCells {
+  std::vector<uint32_t> counts;
+  std::vector<uint8_t> states;
+  size_t size() const { return states.size(); }
+  Occupancy state(size_t i) const { return static_cast<Occupancy>(states[i]); }
+};
+
+/// The map (loamx_occupancy_map): table and counters on the device. Cheap to copy (shared handle).
+class OccupancyMap {
+ public:
+  explicit OccupancyMap(const OccupancyParams& params = OccupancyParams(), size_t max_voxels = (size_t)1 << 20)
+      : params_(params), max_voxels_(max_voxels) {
+    loamx_ctx* ctx = gpu::defaultContext();
+    loamx_occupancy_params p;
+    loamx_default_occupancy_params(&p);
+    p.leaf = params.leaf, p.min_range = params.min_range, p.max_range = params.max_range, p.end_margin = params.end_margin;
+    p.clip_long = params.clip_long ? 1u : 0u, p.min_hits = params.min_hits, p.occ_ratio = params.occ_ratio, p.min_passes = params.min_passes;
+    loamx_occupancy_map* h = nullptr;
+    gpu::check(ctx, loamx_occupancy_create(ctx, &p, max_voxels, &h));
+    handle_ = std::shared_ptr<loamx_occupancy_map>(h, [](loamx_occupancy_map* m) { loamx_occupancy_destroy(gpu::defaultContext(), m); });
+  }
+  const OccupancyParams& params() const { return params_; }
+  size_t maxVoxels() const { return max_voxels_; }
+  /// One cloud in the sensor frame at world_T_sensor: its beams start at the pose's translation. Float fields read through
+  /// FieldAccessor travel as floats, like the scans of extractFeatures.
+  template <template <typename> class Accessor = FieldAccessor, typename PointType, typename Alloc>
+  void add(const std::vector<PointType, Alloc>& points, const Pose3d& world_T_sensor) {
+    double pose[7];
+    world_T_sensor.toArray(pose);
+    addPacked<Accessor>(points, pose);
+  }
+  /// One cloud whose sensor stands at the map's origin (no transform)
+  template <template <typename> class Accessor = FieldAccessor, typename PointType, typename Alloc>
+  void add(const std::vector<PointType, Alloc>& points) {
+    addPacked<Accessor>(points, nullptr);
+  }
+  void clear() {
+    loamx_ctx* ctx = gpu::defaultContext();
+    gpu::check(ctx, loamx_occupancy_clear(ctx, handle_.get()));
+  }
+  /// Counts and state of the voxel of each point (map frame, packed x y z)
+  OccupancyCells query(const std::vector<double>& xyz) const {
+    loamx_ctx* ctx = gpu::defaultContext();
+    const size_t n = xyz.size() / 3;
+    OccupancyCells out;
+    out.counts.resize(2 * n), out.states.resize(n);
+    gpu::check(ctx, loamx_occupancy_query(ctx, handle_.get(), xyz.data(), 3, n, out.counts.data(), out.states.data()));
+    return out;
+  }
+  /// The voxels vmin .. vmin + dims - 1, x fastest: entry (z dims[1] + y) dims[0] + x
+  OccupancyCells box(const std::array<int32_t, 3>& vmin, const std::array<uint32_t, 3>& dims) const {
+    loamx_ctx* ctx = gpu::defaultContext();
+    const size_t n = (size_t)dims[0] * dims[1] * dims[2];
+    OccupancyCells out;
+    out.counts.resize(2 * n), out.states.resize(n);
+    gpu::check(ctx, loamx_occupancy_box(ctx, handle_.get(), vmin.data(), dims.data(), out.counts.data(), out.states.data()));
+    return out;
+  }
+  /// The 2-D grid of the box's columns, entry y dims[0] + x: occupied if any level of the column is, otherwise free if any is
+  std::vector<uint8_t> slice(const std::array<int32_t, 3>& vmin, const std::array<uint32_t, 3>& dims) const {
+    loamx_ctx* ctx = gpu::defaultContext();
+    std::vector<uint8_t> grid((size_t)dims[0] * dims[1]);
+    gpu::check(ctx, loamx_occupancy_slice(ctx, handle_.get(), vmin.data(), dims.data(), grid.data()));
+    return grid;
+  }
+  OccupancyStats stats() const {
+    loamx_ctx* ctx = gpu::defaultContext();
+    loamx_occupancy_stats s;
+    gpu::check(ctx, loamx_occupancy_stats_read(ctx, handle_.get(), &s));
+    OccupancyStats out;
+    out.rays_offered = s.rays_offered, out.rays_hit = s.rays_hit, out.invalid = s.invalid, out.range_short = s.range_short;
+    out.range_long = s.range_long, out.outside = s.outside, out.visits = s.visits, out.voxels = s.voxels, out.overflow = s.overflow;
+    return out;
+  }
+  loamx_occupancy_map* handle() const { return handle_.get(); }
+
+ private:
+  template <template <typename> class Accessor, typename PointType, typename Alloc>
+  void addPacked(const std::vector<PointType, Alloc>& points, const double* pose) {
+    loamx_ctx* ctx = gpu::defaultContext();
+    if constexpr (gpu::float_scan_v<Accessor, PointType>) {
+      const std::vector<float> xyz = gpu::packFloat(points);
+      gpu::check(ctx, loamx_occupancy_add_cloud_f32(ctx, handle_.get(), xyz.data(), 3, points.size(), pose));
+    } else {
+      const std::vector<double> xyz = gpu::pack<Accessor>(points);
+      gpu::check(ctx, loamx_occupancy_add_cloud(ctx, handle_.get(), xyz.data(), 3, points.size(), pose));
+    }
+  }
+
+  OccupancyParams params_;
+  size_t max_voxels_;
+  std::shared_ptr<loamx_occupancy_map> handle_;
+};
+
+}  // namespace loam

@@ -260,6 +260,7 @@ int loamx_ctx_last_assoc_coop_forms(loamx_ctx* ctx, int which_kind, uint32_t out
  *   cloud map:     NO_CLOUDMAP_COMBINE (one claim per point instead of one per run of a wavefront: the same bytes, see "cloud map")
  *   segmentation:  NO_SEGMENT_TILES (every connected edge through the global union, no tile labelling in LDS: the same bytes, see "scan segmentation")
  *   map cleaning:  NO_VISIBILITY_RANGES (the votes kernel reads the scans' points, no first launch that writes every cell's squared range: the same bytes, see "map cleaning")
+ *   occupancy map: NO_OCCUPANCY_COMBINE (one claim per visit instead of one per run of a wavefront: the same bytes, see "occupancy map")
  * Unknown name: LOAMX_ERR_BAD_PARAM.
  *
  * Non-finite input. The reference is undefined on NaN / Inf coordinates (loam/include/loam/features-inl.h:38 sorts on
@@ -1173,6 +1174,119 @@ int loamx_visibility_votes_f32(loamx_ctx* ctx, const loamx_scan_layout* layout, 
 /* The last votes call of the context (device or host form). Synchronises. LOAMX_ERR_BAD_PARAM before any votes call. Never part of
  * a result. */
 int loamx_ctx_last_visibility_census(loamx_ctx* ctx, loamx_visibility_census* out);
+
+/* ---- occupancy map (no reference counterpart; the free / occupied / unknown distinction of OctoMap). The cloud map and the
+ * visibility votes say where the sensor hit something; this map also says where it saw nothing. A device-resident hash table
+ * voxel -> (hits, passes), two integer counts per voxel, filled by walking every beam from the sensor's position to its return.
+ * Counts are integer sums and the walk of a ray depends on that ray alone, so every schedule, every split over workgroups and every
+ * split of a drive into calls gives the same bytes; a numpy model is compared by equality (tests/occupancy_common.py). It is read
+ * back through three forms whose order is dense or given by the caller (points, a 3-D box, a 2-D slice): nothing is ever sorted.
+ *
+ * The rule (loam_amd/csrc/occupancy_math.h). FP64 throughout, float input widened first; every product, quotient, sum and
+ * difference is one operation rounded on its own, in the order written; the only libm call is sqrt; min2 = min_range^2 and
+ * max2 = max_range^2 are formed once by the host. Per ray, for point p of cloud c whose pose (q, t) is read from DEVICE memory
+ * (no pose array: p' = p, o = 0):
+ *   1 validity   the cloud map's tests on p and r2 = x x + y y + z z. Not finite: counted `invalid`, dropped. !(r2 >= min2): counted
+ *                `range_short`, dropped (this removes the (0, 0, 0) cells). !(r2 <= max2): counted `range_long`; with clip_long
+ *                the ray is LONG: it is walked up to max_range and makes no hit; without, it is dropped.
+ *   2 end points p' = pose.act(p) (the cloud map's function), o = t, d = p' - o per axis, dist = sqrt(r2);
+ *                s = (dist - end_margin) / dist for a normal ray, s = max_range / dist for a long one. !(s > 0): the ray has its
+ *                hit and no walk. Walk end e = o + s d per axis: one product, one sum.
+ *   3 hit        a normal ray's hit voxel is the voxel of p' by the cloud map's rule (floor(p' / leaf), |v| < 2^20, the same
+ *                key: at equal leaf an occupancy key is a cloud-map key). p' outside that range: the ray is counted `outside`
+ *                and dropped whole. Otherwise hits[key] += 1 and the ray counts in `rays_hit`.
+ *   4 walk       per axis a: to = o[a] / leaf, te = e[a] / leaf, v = floor(to), ve = floor(te). Either outside |v| < 2^20 on any
+ *                axis: counted `outside`, no walk (the hit stays). rem[a] = |ve - v|, dir[a] = +-1. Where rem[a] > 0:
+ *                ad = |te - to|, tDelta[a] = 1.0 / ad, tMax[a] = (dir > 0 ? (v + 1.0) - to : to - v) / ad. The start voxel is
+ *                visited, then exactly rem[0] + rem[1] + rem[2] steps follow; in each, among the axes with rem[a] > 0 the one with
+ *                the smallest tMax is taken (ties: the lowest axis), v[a] += dir[a], tMax[a] = tMax[a] + tDelta[a], rem[a] -= 1,
+ *                and v is visited. The walk ends in ve and its length is known before it starts. Every visited voxel whose key
+ *                differs from the ray's own hit key takes passes += 1 and counts in `visits`.
+ *                THIS is the definition of the visited set, not "the voxels the segment meets" (they differ by roundings at faces).
+ *   5 state      OCCUPIED iff hits >= min_hits && (double) hits >= occ_ratio * (double) passes; otherwise FREE iff
+ *                passes >= min_passes; otherwise UNKNOWN, which includes a voxel without a slot. With occ_ratio 0 a hit always
+ *                wins; raise it to let passes erase hits. A hit of one scan is not shielded from the passes of the same scan
+ *                (OctoMap's per-scan priority would make the result depend on how a drive is split into calls): occ_ratio and
+ *                end_margin are the knobs instead.
+ * Storage. One device block per map, allocated at create and never grown: 2^k >= 2 max_voxels slots of a 64-bit key (all ones:
+ *   empty) and one 64-bit count word hits << 32 | passes, and the counters. A visit is one 64-bit compare-and-swap probe whose
+ *   returned value decides plus ONE 64-bit atomic add. At most 2^32 - 2 rays may be offered between two clears, so neither half
+ *   of a word can wrap (a ray visits no voxel twice).
+ * Overflow. `overflow` counts the visits and hits whose probe gave up after 2^k slots (they were added nowhere). FROM THE FIRST
+ *   OVERFLOW UNTIL THE NEXT CLEAR the map promises only that every call returns and that the stats say so.
+ * Kernels (loam_amd/csrc/occupancy_kernels.hip). One ray per lane; the lanes of a wavefront are neighbouring beams, and in every
+ *   step of the walk runs of neighbouring lanes that stand in the same voxel are combined into one claim that adds the run's
+ *   length (the hit goes the same way). Context option NO_OCCUPANCY_COMBINE: one claim per visit; the same bytes.
+ *   loamx_occupancy_claims_read tells the two apart. */
+enum { LOAMX_OCC_UNKNOWN = 0, LOAMX_OCC_FREE = 1, LOAMX_OCC_OCCUPIED = 2 };
+typedef struct {
+  double leaf;         /* 0.2 */
+  double min_range;    /* 0.5 */
+  double max_range;    /* 80.0 */
+  double end_margin;   /* 0.2 */
+  uint32_t clip_long;  /* 1 */
+  uint32_t min_hits;   /* 1 */
+  double occ_ratio;    /* 0.0 */
+  uint32_t min_passes; /* 1 */
+} loamx_occupancy_params;
+typedef struct {
+  uint64_t rays_offered; /* since the last clear, dropped ones included */
+  uint64_t rays_hit;     /* rays that made a hit */
+  uint64_t invalid, range_short, range_long, outside;
+  uint64_t visits;       /* passes made */
+  uint64_t voxels;       /* empty slots won: the voxels of the table */
+  uint64_t overflow;
+} loamx_occupancy_stats;
+/* A map belongs to the context it was created on: every other entry point refuses it on another context (LOAMX_ERR_BAD_PARAM).
+ * The context's mutex and stream put its uses in order. */
+typedef struct loamx_occupancy_map loamx_occupancy_map;
+void loamx_default_occupancy_params(loamx_occupancy_params* p);
+/* LOAMX_ERR_BAD_PARAM: a null argument, leaf not finite or <= 0, a negative or non-finite min_range, max_range, end_margin or
+ * occ_ratio, max_range < min_range, max_voxels == 0; LOAMX_ERR_UNSUPPORTED: max_range / leaf > 4096 (with a unit quaternion this
+ * keeps a walk under 3 x 4098 steps), max_voxels > 2^30. */
+int loamx_occupancy_create(loamx_ctx* ctx, const loamx_occupancy_params* params, size_t max_voxels, loamx_occupancy_map** out);
+void loamx_occupancy_destroy(loamx_ctx* ctx, loamx_occupancy_map* map);
+/* an empty map again. Asynchronous on the context's stream. */
+int loamx_occupancy_clear(loamx_ctx* ctx, loamx_occupancy_map* map);
+/* The arguments, conventions and refusals of loamx_cloud_map_add_clouds_dev, so that the two are called side by side on the same
+ * buffers: n_clouds device-resident clouds back to back, cloud_offsets a HOST array of n_clouds + 1 entries, d_poses DEVICE
+ * n_clouds x 7 or NULL. Asynchronous, no host round trip. LOAMX_ERR_UNSUPPORTED: more than 2^32 - 2 rays offered since the last
+ * clear with this call's. A refused call changes nothing. */
+int loamx_occupancy_add_clouds_dev(loamx_ctx* ctx, loamx_occupancy_map* map, const double* d_points, size_t point_stride,
+                                   const size_t* cloud_offsets, size_t n_clouds, const double* d_poses);
+int loamx_occupancy_add_clouds_dev_f32(loamx_ctx* ctx, loamx_occupancy_map* map, const float* d_points, size_t point_stride,
+                                       const size_t* cloud_offsets, size_t n_clouds, const double* d_poses);
+/* The counts and the state of the voxel of each of n device-resident points (double, map frame, point_stride scalars apart), the
+ * voxel found by the cloud map's rule: d_counts_out[i] = (hits, passes), d_state_out[i] = LOAMX_OCC_*; either may be NULL. No
+ * voxel or no slot: (0, 0) and UNKNOWN. Fed with what loamx_cloud_map_emit_dev wrote, it labels that map's centroids in its own
+ * order. The map is not changed. Asynchronous. LOAMX_ERR_BAD_PARAM: a null map, null points with n > 0, point_stride < 3;
+ * LOAMX_ERR_UNSUPPORTED: n > 2^31, a point_stride beyond 32 bits. */
+int loamx_occupancy_query_dev(loamx_ctx* ctx, const loamx_occupancy_map* map, const double* d_points, size_t point_stride, size_t n,
+                              uint32_t* d_counts_out /* [n][2] */, uint8_t* d_state_out /* [n] */);
+/* A dense box of voxels vmin .. vmin + dims - 1, x fastest: entry (z dims[1] + y) dims[0] + x. Voxels outside |v| < 2^20 read as
+ * without a slot. Either output may be NULL. Asynchronous. LOAMX_ERR_BAD_PARAM: a null map, vmin or dims; LOAMX_ERR_UNSUPPORTED:
+ * more than 2^31 voxels. A box with a dimension of 0 writes nothing. */
+int loamx_occupancy_box_dev(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3],
+                            uint32_t* d_counts_out, uint8_t* d_state_out);
+/* The 2-D grid a planner takes, d_grid_out[y dims[0] + x]: column (x, y) of the same box is OCCUPIED if any voxel of its dims[2]
+ * levels is, otherwise FREE if any is, otherwise UNKNOWN. Asynchronous. Refusals as the box's, and a null d_grid_out with columns. */
+int loamx_occupancy_slice_dev(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3],
+                              uint8_t* d_grid_out /* [dims[1]][dims[0]] */);
+/* synchronises */
+int loamx_occupancy_stats_read(loamx_ctx* ctx, const loamx_occupancy_map* map, loamx_occupancy_stats* out);
+/* Measurement read-out: the claims since the last clear, that is, how often the walk kernel began a probe: once per hit and per
+ * pass without combining, once per run of a wavefront with it. Changes nothing; synchronises. */
+int loamx_occupancy_claims_read(loamx_ctx* ctx, const loamx_occupancy_map* map, uint64_t* claims);
+/* host forms, synchronous: one cloud in host memory with a HOST pose (NULL = no transform); the read-outs from and to host arrays */
+int loamx_occupancy_add_cloud(loamx_ctx* ctx, loamx_occupancy_map* map, const double* points, size_t point_stride, size_t n_points,
+                              const double pose[7]);
+int loamx_occupancy_add_cloud_f32(loamx_ctx* ctx, loamx_occupancy_map* map, const float* points, size_t point_stride, size_t n_points,
+                                  const double pose[7]);
+int loamx_occupancy_query(loamx_ctx* ctx, const loamx_occupancy_map* map, const double* points, size_t point_stride, size_t n,
+                          uint32_t* counts_out, uint8_t* state_out);
+int loamx_occupancy_box(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3], uint32_t* counts_out,
+                        uint8_t* state_out);
+int loamx_occupancy_slice(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3], uint8_t* grid_out);
 
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are

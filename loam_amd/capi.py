@@ -231,6 +231,40 @@ class CloudMapParams:
 CLOUD_MAP_STATS_DTYPE = np.dtype([(n, np.uint64) for n in ("voxels", "points_offered", "points_used", "invalid", "range", "outside", "overflow")])
 
 
+class OccupancyParamsStruct(C.Structure):
+    """loamx_occupancy_params (include/loamx.h)"""
+    _fields_ = [("leaf", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double), ("end_margin", C.c_double),
+                ("clip_long", C.c_uint32), ("min_hits", C.c_uint32), ("occ_ratio", C.c_double), ("min_passes", C.c_uint32)]
+
+
+class OccupancyParams:
+    """The rule of an occupancy map (loamx_occupancy_params): voxel edge, range band, how far in front of a return a walk stops,
+    whether rays beyond max_range are walked up to it, and the three thresholds of a voxel's state. Anything left out takes
+    the C ABI's default."""
+    NAMES = ("leaf", "min_range", "max_range", "end_margin", "clip_long", "min_hits", "occ_ratio", "min_passes")
+
+    def __init__(self, leaf=None, min_range=None, max_range=None, end_margin=None, clip_long=None, min_hits=None, occ_ratio=None, min_passes=None):
+        d = OccupancyParamsStruct()
+        load().loamx_default_occupancy_params(C.byref(d))
+        given = dict(leaf=leaf, min_range=min_range, max_range=max_range, end_margin=end_margin, clip_long=clip_long, min_hits=min_hits,
+                     occ_ratio=occ_ratio, min_passes=min_passes)
+        for name in self.NAMES:
+            setattr(self, name, getattr(d, name) if given[name] is None else given[name])
+
+    def struct(self):
+        for name in ("clip_long", "min_hits", "min_passes"):
+            if not 0 <= int(getattr(self, name)) <= 0xFFFFFFFF:
+                raise ValueError(f"OccupancyParams: {name} does not fit 32 bits")
+        return OccupancyParamsStruct(float(self.leaf), float(self.min_range), float(self.max_range), float(self.end_margin), int(self.clip_long),
+                                     int(self.min_hits), float(self.occ_ratio), int(self.min_passes))
+
+
+# loamx_occupancy_stats
+OCCUPANCY_STATS_DTYPE = np.dtype([(n, np.uint64) for n in ("rays_offered", "rays_hit", "invalid", "range_short", "range_long", "outside", "visits",
+                                                          "voxels", "overflow")])
+OCC_UNKNOWN, OCC_FREE, OCC_OCCUPIED = 0, 1, 2  # LOAMX_OCC_*: the state of a voxel
+
+
 class SegmentParamsStruct(C.Structure):
     """loamx_segment_params (include/loamx.h)"""
     _fields_ = [("ground_lines", C.c_uint64), ("ground_angle", C.c_double), ("segment_angle", C.c_double),
@@ -402,6 +436,10 @@ EXPORTS = [
     "loamx_segment_scan", "loamx_segment_scan_f32", "loamx_ctx_last_segment_census",
     "loamx_default_visibility_params", "loamx_visibility_votes_dev", "loamx_visibility_votes_dev_f32", "loamx_visibility_filter_dev",
     "loamx_visibility_votes", "loamx_visibility_votes_f32", "loamx_ctx_last_visibility_census",
+    "loamx_default_occupancy_params", "loamx_occupancy_create", "loamx_occupancy_destroy", "loamx_occupancy_clear",
+    "loamx_occupancy_add_clouds_dev", "loamx_occupancy_add_clouds_dev_f32", "loamx_occupancy_query_dev", "loamx_occupancy_box_dev",
+    "loamx_occupancy_slice_dev", "loamx_occupancy_stats_read", "loamx_occupancy_claims_read", "loamx_occupancy_add_cloud",
+    "loamx_occupancy_add_cloud_f32", "loamx_occupancy_query", "loamx_occupancy_box", "loamx_occupancy_slice",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -655,6 +693,24 @@ def load(build_if_missing=True):
     lib.loamx_cloud_map_add_cloud.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.loamx_cloud_map_add_cloud_f32.argtypes = lib.loamx_cloud_map_add_cloud.argtypes
     lib.loamx_cloud_map_emit.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, C.c_size_t, szp]
+    lib.loamx_default_occupancy_params.argtypes = [C.POINTER(OccupancyParamsStruct)]
+    lib.loamx_default_occupancy_params.restype = None
+    lib.loamx_occupancy_create.argtypes = [vp, C.POINTER(OccupancyParamsStruct), C.c_size_t, C.POINTER(vp)]
+    lib.loamx_occupancy_destroy.argtypes = [vp, vp]
+    lib.loamx_occupancy_destroy.restype = None
+    lib.loamx_occupancy_clear.argtypes = [vp, vp]
+    lib.loamx_occupancy_add_clouds_dev.argtypes = [vp, vp, vp, C.c_size_t, szp, C.c_size_t, vp]
+    lib.loamx_occupancy_add_clouds_dev_f32.argtypes = lib.loamx_occupancy_add_clouds_dev.argtypes
+    lib.loamx_occupancy_query_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp]
+    lib.loamx_occupancy_query.argtypes = lib.loamx_occupancy_query_dev.argtypes
+    lib.loamx_occupancy_box_dev.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), vp, vp]
+    lib.loamx_occupancy_box.argtypes = lib.loamx_occupancy_box_dev.argtypes
+    lib.loamx_occupancy_slice_dev.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), vp]
+    lib.loamx_occupancy_slice.argtypes = lib.loamx_occupancy_slice_dev.argtypes
+    lib.loamx_occupancy_stats_read.argtypes = [vp, vp, vp]
+    lib.loamx_occupancy_claims_read.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
+    lib.loamx_occupancy_add_cloud.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
+    lib.loamx_occupancy_add_cloud_f32.argtypes = lib.loamx_occupancy_add_cloud.argtypes
     lib.loamx_default_segment_params.argtypes = [C.POINTER(SegmentParamsStruct)]
     lib.loamx_default_segment_params.restype = None
     lib.loamx_segment_constants.argtypes = [C.POINTER(SegmentParamsStruct), dp]
@@ -1053,6 +1109,139 @@ class CloudMap:
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):
                 self.ctx.lib.loamx_cloud_map_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _box_args(vmin, dims, what):
+    """(int32[3], uint32[3]) of a voxel box"""
+    v, d = np.asarray(vmin), np.asarray(dims)
+    if v.shape != (3,) or d.shape != (3,) or v.dtype.kind not in "iu" or d.dtype.kind not in "iu":
+        raise ValueError(f"{what}: vmin and dims are three integers each")
+    if (np.abs(v.astype(np.int64)) > 0x7FFFFFFF).any() or (d.astype(np.int64) < 0).any() or (d.astype(np.int64) > 0xFFFFFFFF).any():
+        raise ValueError(f"{what}: vmin does not fit int32 or dims does not fit uint32")
+    return np.ascontiguousarray(v, dtype=np.int32), np.ascontiguousarray(d, dtype=np.uint32)
+
+
+class OccupancyMap:
+    """An occupancy map (loamx_occupancy_map; include/loamx.h, "occupancy map"): every beam of posed clouds walked through a voxel
+    grid, two integer counts per voxel (hits, passes), read back as free / occupied / unknown per point, per voxel of a dense
+    box or per column of a 2-D slice; on the context's device. close() frees it; the context must still be open."""
+
+    def __init__(self, ctx, params=None, max_voxels=1 << 20):
+        self.ctx, self.params = ctx, params or OccupancyParams()
+        max_voxels = int(max_voxels)
+        if max_voxels < 0:
+            raise ValueError("occupancy_map: max_voxels is negative")
+        st = self.params.struct()
+        h = C.c_void_p()
+        ctx._check(ctx.lib.loamx_occupancy_create(ctx.h, C.byref(st), max_voxels, C.byref(h)))
+        self.h, self.max_voxels = h, max_voxels
+
+    def _handle(self):
+        if not getattr(self, "h", None):
+            raise ValueError("the occupancy map is closed")
+        return self.h
+
+    def clear(self):
+        """an empty map again (loamx_occupancy_clear). Asynchronous."""
+        self.ctx._check(self.ctx.lib.loamx_occupancy_clear(self.ctx.h, self._handle()))
+
+    def add_clouds_dev(self, d_points, point_stride, cloud_offsets, d_poses=0, f32=False):
+        """the arguments of CloudMap.add_clouds_dev (loamx_occupancy_add_clouds_dev[_f32]). Asynchronous."""
+        off = _offsets(cloud_offsets, "add_clouds_dev")
+        if int(point_stride) < 0:
+            raise ValueError("add_clouds_dev: point_stride is negative")
+        fn = self.ctx.lib.loamx_occupancy_add_clouds_dev_f32 if f32 else self.ctx.lib.loamx_occupancy_add_clouds_dev
+        self.ctx._check(fn(self.ctx.h, self._handle(), d_points or None, int(point_stride), off.ctypes.data_as(C.POINTER(C.c_size_t)),
+                           off.size - 1, d_poses or None))
+
+    def add_cloud(self, points, pose=None):
+        """One cloud (or organised scan) in host memory, (n, k >= 3) float64 / float32, at a host pose7 or None (no transform)."""
+        pts = np.asarray(points)
+        if pts.dtype != np.float32:
+            pts = np.asarray(pts, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] < 3:
+            raise ValueError(f"add_cloud: points must be (n, 3) or (n, k >= 3), not {pts.shape}")
+        pts = np.ascontiguousarray(pts)
+        p = None
+        if pose is not None:
+            p = np.ascontiguousarray(pose, dtype=np.float64)
+            if p.shape != (7,):
+                raise ValueError(f"add_cloud: a pose is 7 numbers (qx qy qz qw tx ty tz), not {p.shape}")
+        fn = self.ctx.lib.loamx_occupancy_add_cloud_f32 if pts.dtype == np.float32 else self.ctx.lib.loamx_occupancy_add_cloud
+        self.ctx._check(fn(self.ctx.h, self._handle(), pts.ctypes.data, pts.shape[1], pts.shape[0], None if p is None else p.ctypes.data))
+
+    def query_dev(self, d_points, point_stride, n, d_counts_out=0, d_state_out=0):
+        """counts (uint32 [n][2]: hits, passes) and state (uint8 [n]) of the voxels of n device-resident points (double), to
+        device addresses, either 0 = not wanted (loamx_occupancy_query_dev). Asynchronous."""
+        if int(point_stride) < 0 or int(n) < 0:
+            raise ValueError("query_dev: point_stride or n is negative")
+        self.ctx._check(self.ctx.lib.loamx_occupancy_query_dev(self.ctx.h, self._handle(), d_points or None, int(point_stride), int(n),
+                                                               d_counts_out or None, d_state_out or None))
+
+    def query(self, points):
+        """host points (n, k >= 3) -> (counts (n, 2) uint32, state (n,) uint8)"""
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] < 3:
+            raise ValueError(f"query: points must be (n, 3) or (n, k >= 3), not {pts.shape}")
+        counts, state = np.zeros((len(pts), 2), dtype=np.uint32), np.zeros(len(pts), dtype=np.uint8)
+        self.ctx._check(self.ctx.lib.loamx_occupancy_query(self.ctx.h, self._handle(), pts.ctypes.data, pts.shape[1], len(pts), counts.ctypes.data,
+                                                           state.ctypes.data))
+        return counts, state
+
+    def box_dev(self, vmin, dims, d_counts_out=0, d_state_out=0):
+        """the voxels vmin .. vmin + dims - 1, x fastest, to device addresses, either 0 = not wanted (loamx_occupancy_box_dev).
+        Asynchronous."""
+        v, d = _box_args(vmin, dims, "box_dev")
+        self.ctx._check(self.ctx.lib.loamx_occupancy_box_dev(self.ctx.h, self._handle(), v.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                             d.ctypes.data_as(C.POINTER(C.c_uint32)), d_counts_out or None, d_state_out or None))
+
+    def box(self, vmin, dims):
+        """(counts (dz, dy, dx, 2) uint32, state (dz, dy, dx) uint8) of the box"""
+        v, d = _box_args(vmin, dims, "box")
+        shape = (int(d[2]), int(d[1]), int(d[0]))
+        counts, state = np.zeros(shape + (2,), dtype=np.uint32), np.zeros(shape, dtype=np.uint8)
+        self.ctx._check(self.ctx.lib.loamx_occupancy_box(self.ctx.h, self._handle(), v.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         d.ctypes.data_as(C.POINTER(C.c_uint32)), counts.ctypes.data, state.ctypes.data))
+        return counts, state
+
+    def slice_dev(self, vmin, dims, d_grid_out):
+        """the 2-D grid (uint8 [dims[1]][dims[0]]) of the box's columns to a device address (loamx_occupancy_slice_dev). Asynchronous."""
+        v, d = _box_args(vmin, dims, "slice_dev")
+        self.ctx._check(self.ctx.lib.loamx_occupancy_slice_dev(self.ctx.h, self._handle(), v.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                               d.ctypes.data_as(C.POINTER(C.c_uint32)), d_grid_out or None))
+
+    def slice(self, vmin, dims):
+        """(dy, dx) uint8: OCC_OCCUPIED where any level of the column is occupied, otherwise OCC_FREE where any is free"""
+        v, d = _box_args(vmin, dims, "slice")
+        grid = np.zeros((int(d[1]), int(d[0])), dtype=np.uint8)
+        self.ctx._check(self.ctx.lib.loamx_occupancy_slice(self.ctx.h, self._handle(), v.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           d.ctypes.data_as(C.POINTER(C.c_uint32)), grid.ctypes.data))
+        return grid
+
+    def stats(self):
+        """one OCCUPANCY_STATS_DTYPE record (loamx_occupancy_stats_read; synchronises)"""
+        st = np.zeros(1, dtype=OCCUPANCY_STATS_DTYPE)
+        self.ctx._check(self.ctx.lib.loamx_occupancy_stats_read(self.ctx.h, self._handle(), st.ctypes.data))
+        return st[0]
+
+    def claims(self):
+        """probes begun by the walk kernel since the last clear: one per hit and per pass in the plain form, one per run of a
+        wavefront with run combining (loamx_occupancy_claims_read; synchronises)"""
+        n = C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.loamx_occupancy_claims_read(self.ctx.h, self._handle(), C.byref(n)))
+        return n.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.ctx.lib.loamx_occupancy_destroy(self.ctx.h, self.h)
             self.h = None
 
     def __del__(self):
@@ -1741,6 +1930,9 @@ class Context:
     # ---- cloud map (include/loamx.h, "cloud map") ---------------------------------------------------------------
     def cloud_map(self, params=None, max_voxels=1 << 20):
         return CloudMap(self, params, max_voxels)
+
+    def occupancy_map(self, params=None, max_voxels=1 << 20):
+        return OccupancyMap(self, params, max_voxels)
 
     @staticmethod
     def _pgo_params(params):

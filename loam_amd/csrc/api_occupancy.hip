@@ -1,0 +1,361 @@
+// api_occupancy.hip — the occupancy map (loamx.h, "occupancy map"): the map handle with its one device block (table and counters),
+// the add, clear, query, box, slice and stats entry points and their host forms.
+#include "api_host.h"
+
+struct loamx_occupancy_map {
+  loamx_ctx* owner = nullptr;  // the context it was created on: its mutex and stream order every use
+  int device = 0;
+  loamx_occupancy_params params = {};
+  loamx::OccRule rule = {};
+  loamx::OccStateRule state_rule = {};
+  loamx::OccTable t = {};
+  void* block = nullptr;
+  size_t ones_bytes = 0;   // keys, at the block's start: 0xFF bytes in an empty map
+  size_t zeros_bytes = 0;  // counts and counters behind them: zero bytes in an empty map
+  uint64_t offered = 0;    // rays offered since the last clear
+};
+
+using namespace loamx;
+
+namespace {
+
+constexpr size_t kOccMaxVoxels = (size_t)1 << 30;
+constexpr unsigned long long kOccMaxRead = 1ull << 31;  // points of a query, voxels of a box
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int map_check(loamx_ctx* ctx, const loamx_occupancy_map* map) {
+  if (!map) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null occupancy map");
+  if (map->owner != ctx) return fail(ctx, LOAMX_ERR_BAD_PARAM, "the occupancy map was created on another context");
+  return LOAMX_OK;
+}
+
+int clear_locked(loamx_ctx* ctx, loamx_occupancy_map* map) {
+  untimed(ctx);
+  HIP_TRY(ctx, hipMemsetAsync(map->block, 0xFF, map->ones_bytes, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(static_cast<char*>(map->block) + map->ones_bytes, 0, map->zeros_bytes, ctx->stream));
+  map->offered = 0;
+  return LOAMX_OK;
+}
+
+// the argument checks the device and the host forms of an add share; *total: the rays of the call
+int add_check(loamx_ctx* ctx, const loamx_occupancy_map* map, const void* points, size_t stride, const size_t* offsets, size_t n_clouds, size_t* total) {
+  int rc = map_check(ctx, map);
+  if (rc != LOAMX_OK) return rc;
+  *total = 0;
+  if (stride < 3) return fail(ctx, LOAMX_ERR_BAD_PARAM, "point_stride must be >= 3");
+  if (stride > 0xFFFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "point_stride does not fit 32 bits");
+  if (n_clouds == 0) return LOAMX_OK;
+  if (!offsets) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null cloud_offsets");
+  for (size_t c = 0; c < n_clouds; c++)
+    if (offsets[c + 1] < offsets[c]) return fail(ctx, LOAMX_ERR_BAD_PARAM, "cloud_offsets must ascend");
+  *total = offsets[n_clouds] - offsets[0];
+  if (*total && !points) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null points");
+  if (*total > kOccMaxOffered || map->offered + *total > kOccMaxOffered)
+    return fail(ctx, LOAMX_ERR_UNSUPPORTED, "an occupancy map takes at most 2^32 - 2 rays between two clears");
+  return LOAMX_OK;
+}
+
+// the clouds of the call, kOrgChunkClouds at a time (their offsets travel as a kernel argument), their rays in launches of
+// kOccChunkRays (the caller holds ctx->mu, has selected the device and checked the arguments)
+int add_locked(loamx_ctx* ctx, loamx_occupancy_map* map, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
+               const double* d_poses) {
+  const bool combine = !(ctx->reg_flags & kRegFlagNoOccupancyCombine);
+  untimed(ctx);
+  for (size_t c0 = 0; c0 < n_clouds; c0 += kOrgChunkClouds) {
+    const uint32_t nc = (uint32_t)(n_clouds - c0 < kOrgChunkClouds ? n_clouds - c0 : kOrgChunkClouds);
+    OrgOffsets offs;
+    for (uint32_t c = 0; c <= kOrgChunkClouds; c++) offs.off[c] = offsets[c0 + (c < nc ? c : nc)];
+    for (unsigned long long p0 = offs.off[0]; p0 < offs.off[nc]; p0 += kOccChunkRays) {
+      const uint32_t n = (uint32_t)(offs.off[nc] - p0 < kOccChunkRays ? offs.off[nc] - p0 : kOccChunkRays);
+      launch_occupancy_walk(d_points, f32, (uint32_t)stride, offs, nc, p0, n, d_poses ? d_poses + c0 * 7 : nullptr, map->rule, map->t, combine,
+                            ctx->stream);
+      CHECK_LAUNCH(ctx, "occupancy walk kernel");
+    }
+  }
+  map->offered += offsets[n_clouds] - offsets[0];
+  return LOAMX_OK;
+}
+
+int add_dev(loamx_ctx* ctx, loamx_occupancy_map* map, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
+            const double* d_poses) {
+  API_ENTER(ctx);
+  size_t total = 0;
+  int rc = add_check(ctx, map, d_points, stride, offsets, n_clouds, &total);
+  if (rc != LOAMX_OK || total == 0) return rc;
+  return add_locked(ctx, map, d_points, f32, stride, offsets, n_clouds, d_poses);
+}
+
+int add_host(loamx_ctx* ctx, loamx_occupancy_map* map, const void* points, bool f32, size_t stride, size_t n, const double* pose) {
+  API_ENTER(ctx);
+  const size_t offsets[2] = {0, n};
+  size_t total = 0;
+  int rc = add_check(ctx, map, points, stride, offsets, 1, &total);
+  if (rc != LOAMX_OK || total == 0) return rc;
+  if (n > (~(size_t)0) / (stride * sizeof(double))) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "the cloud does not fit the address space");
+  const size_t in_bytes = n * stride * (f32 ? sizeof(float) : sizeof(double));
+  untimed(ctx);
+  ENSURE(ctx, WS_OCC_IN, in_bytes);
+  ENSURE(ctx, WS_OCC_POSE, 7 * sizeof(double));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_OCC_IN].p, points, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (pose) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_OCC_POSE].p, pose, 7 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  rc = add_locked(ctx, map, ctx->ws[WS_OCC_IN].p, f32, stride, offsets, 1, pose ? wsp<double>(ctx, WS_OCC_POSE) : nullptr);
+  if (rc != LOAMX_OK) {
+    (void)hipStreamSynchronize(ctx->stream);  // (the upload must not outlive the caller's array)
+    return rc;
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return LOAMX_OK;
+}
+
+int query_check(loamx_ctx* ctx, const loamx_occupancy_map* map, const void* points, size_t stride, size_t n) {
+  int rc = map_check(ctx, map);
+  if (rc != LOAMX_OK) return rc;
+  if (stride < 3) return fail(ctx, LOAMX_ERR_BAD_PARAM, "point_stride must be >= 3");
+  if (stride > 0xFFFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "point_stride does not fit 32 bits");
+  if (n && !points) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null points");
+  if (n > kOccMaxRead) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "a query takes at most 2^31 points");
+  return LOAMX_OK;
+}
+
+// *n: the voxels of the box (with_levels) or the columns of the slice
+int box_check(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t* vmin, const uint32_t* dims, bool with_levels, unsigned long long* n) {
+  int rc = map_check(ctx, map);
+  if (rc != LOAMX_OK) return rc;
+  if (!vmin || !dims) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  const unsigned long long plane = (unsigned long long)dims[0] * dims[1];
+  if (plane > kOccMaxRead || plane * (dims[2] ? dims[2] : 1u) > kOccMaxRead) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "a box holds at most 2^31 voxels");
+  *n = with_levels ? plane * dims[2] : plane;
+  return LOAMX_OK;
+}
+
+OccBox make_box(const int32_t* vmin, const uint32_t* dims) {
+  OccBox b;
+  for (int a = 0; a < 3; a++) b.vmin[a] = vmin[a], b.dims[a] = dims[a];
+  return b;
+}
+
+int launch_box(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t* vmin, const uint32_t* dims, uint32_t* d_counts, uint8_t* d_state) {
+  untimed(ctx);
+  launch_occupancy_box(map->t, map->state_rule, make_box(vmin, dims), d_counts, d_state, ctx->stream);
+  CHECK_LAUNCH(ctx, "occupancy box kernel");
+  return LOAMX_OK;
+}
+
+int launch_slice(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t* vmin, const uint32_t* dims, uint8_t* d_grid) {
+  untimed(ctx);
+  launch_occupancy_slice(map->t, map->state_rule, make_box(vmin, dims), d_grid, ctx->stream);
+  CHECK_LAUNCH(ctx, "occupancy slice kernel");
+  return LOAMX_OK;
+}
+
+// counts (n x 2 words) and states (n bytes) of the workspace's output block to the host arrays that were asked for
+int read_out(loamx_ctx* ctx, size_t n, uint32_t* counts_out, uint8_t* state_out) {
+  char* b = static_cast<char*>(ctx->ws[WS_OCC_OUT].p);
+  if (counts_out) HIP_TRY(ctx, hipMemcpyAsync(counts_out, b, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (state_out) HIP_TRY(ctx, hipMemcpyAsync(state_out, b + align256(n * 2 * sizeof(uint32_t)), n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return LOAMX_OK;
+}
+
+bool bad_double(double v) { return !isfinite(v) || v < 0.0; }
+
+}  // namespace
+
+extern "C" {
+
+void loamx_default_occupancy_params(loamx_occupancy_params* p) {
+  if (!p) return;
+  p->leaf = 0.2, p->min_range = 0.5, p->max_range = 80.0, p->end_margin = 0.2;
+  p->clip_long = 1, p->min_hits = 1, p->occ_ratio = 0.0, p->min_passes = 1;
+}
+
+int loamx_occupancy_create(loamx_ctx* ctx, const loamx_occupancy_params* params, size_t max_voxels, loamx_occupancy_map** out) {
+  API_ENTER(ctx);
+  if (!params || !out) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  *out = nullptr;
+  if (!isfinite(params->leaf) || !(params->leaf > 0.0)) return fail(ctx, LOAMX_ERR_BAD_PARAM, "leaf must be finite and positive");
+  if (bad_double(params->min_range) || bad_double(params->max_range) || bad_double(params->end_margin) || bad_double(params->occ_ratio))
+    return fail(ctx, LOAMX_ERR_BAD_PARAM, "min_range, max_range, end_margin and occ_ratio must be finite and not negative");
+  if (!(params->max_range >= params->min_range)) return fail(ctx, LOAMX_ERR_BAD_PARAM, "max_range must be at least min_range");
+  if (max_voxels == 0) return fail(ctx, LOAMX_ERR_BAD_PARAM, "max_voxels must be >= 1");
+  if (params->max_range / params->leaf > 4096.0) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "max_range / leaf > 4096 not supported");
+  if (max_voxels > kOccMaxVoxels) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "max_voxels > 2^30 not supported");
+  loamx_occupancy_map* map = new loamx_occupancy_map;
+  map->owner = ctx, map->device = ctx->device;
+  map->params = *params;
+  map->rule.leaf = params->leaf;
+  map->rule.min_r2 = params->min_range * params->min_range, map->rule.max_r2 = params->max_range * params->max_range;
+  map->rule.max_range = params->max_range, map->rule.end_margin = params->end_margin, map->rule.clip_long = params->clip_long ? 1u : 0u;
+  map->state_rule.min_hits = params->min_hits, map->state_rule.min_passes = params->min_passes, map->state_rule.occ_ratio = params->occ_ratio;
+  uint32_t log2_cap = 4;  // (voxel_hash takes 4 .. 32 bits)
+  while (((size_t)1 << log2_cap) < 2 * max_voxels) log2_cap++;
+  const size_t cap = (size_t)1 << log2_cap;
+  const size_t o_keys = 0, o_counts = o_keys + align256(cap * sizeof(unsigned long long));
+  const size_t o_words = o_counts + align256(cap * sizeof(unsigned long long));
+  const size_t bytes = o_words + align256(kOccWords * sizeof(unsigned long long));
+  hipError_t e = hipMalloc(&map->block, bytes);
+  if (e != hipSuccess) {
+    delete map;
+    return fail(ctx, LOAMX_ERR_HIP, std::string("occupancy map storage: ") + hipGetErrorString(e));
+  }
+  char* b = static_cast<char*>(map->block);
+  map->ones_bytes = o_counts, map->zeros_bytes = bytes - o_counts;
+  map->t.keys = reinterpret_cast<unsigned long long*>(b + o_keys), map->t.counts = reinterpret_cast<unsigned long long*>(b + o_counts);
+  map->t.words = reinterpret_cast<unsigned long long*>(b + o_words), map->t.log2_cap = log2_cap;
+  int rc = clear_locked(ctx, map);
+  if (rc != LOAMX_OK) {
+    (void)hipFree(map->block);
+    delete map;
+    return rc;
+  }
+  *out = map;
+  return LOAMX_OK;
+}
+
+void loamx_occupancy_destroy(loamx_ctx* ctx, loamx_occupancy_map* map) {
+  if (!map) return;
+  if (ctx) {
+    std::lock_guard<std::mutex> guard(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);  // (kernels still working on the map)
+    if (map->block) (void)hipFree(map->block);
+    delete map;
+    return;
+  }
+  if (map->block) (void)hipFree(map->block);
+  delete map;
+}
+
+int loamx_occupancy_clear(loamx_ctx* ctx, loamx_occupancy_map* map) {
+  API_ENTER(ctx);
+  int rc = map_check(ctx, map);
+  if (rc != LOAMX_OK) return rc;
+  return clear_locked(ctx, map);
+}
+
+int loamx_occupancy_add_clouds_dev(loamx_ctx* ctx, loamx_occupancy_map* map, const double* d_points, size_t point_stride, const size_t* cloud_offsets,
+                                   size_t n_clouds, const double* d_poses) {
+  return add_dev(ctx, map, d_points, false, point_stride, cloud_offsets, n_clouds, d_poses);
+}
+int loamx_occupancy_add_clouds_dev_f32(loamx_ctx* ctx, loamx_occupancy_map* map, const float* d_points, size_t point_stride, const size_t* cloud_offsets,
+                                       size_t n_clouds, const double* d_poses) {
+  return add_dev(ctx, map, d_points, true, point_stride, cloud_offsets, n_clouds, d_poses);
+}
+int loamx_occupancy_add_cloud(loamx_ctx* ctx, loamx_occupancy_map* map, const double* points, size_t point_stride, size_t n_points, const double pose[7]) {
+  return add_host(ctx, map, points, false, point_stride, n_points, pose);
+}
+int loamx_occupancy_add_cloud_f32(loamx_ctx* ctx, loamx_occupancy_map* map, const float* points, size_t point_stride, size_t n_points,
+                                  const double pose[7]) {
+  return add_host(ctx, map, points, true, point_stride, n_points, pose);
+}
+
+int loamx_occupancy_query_dev(loamx_ctx* ctx, const loamx_occupancy_map* map, const double* d_points, size_t point_stride, size_t n,
+                              uint32_t* d_counts_out, uint8_t* d_state_out) {
+  API_ENTER(ctx);
+  int rc = query_check(ctx, map, d_points, point_stride, n);
+  if (rc != LOAMX_OK || n == 0 || (!d_counts_out && !d_state_out)) return rc;
+  untimed(ctx);
+  launch_occupancy_query(map->t, map->rule.leaf, map->state_rule, d_points, (uint32_t)point_stride, n, d_counts_out, d_state_out, ctx->stream);
+  CHECK_LAUNCH(ctx, "occupancy query kernel");
+  return LOAMX_OK;
+}
+
+int loamx_occupancy_box_dev(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3], uint32_t* d_counts_out,
+                            uint8_t* d_state_out) {
+  API_ENTER(ctx);
+  unsigned long long n = 0;
+  int rc = box_check(ctx, map, vmin, dims, true, &n);
+  if (rc != LOAMX_OK || n == 0 || (!d_counts_out && !d_state_out)) return rc;
+  return launch_box(ctx, map, vmin, dims, d_counts_out, d_state_out);
+}
+
+int loamx_occupancy_slice_dev(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3], uint8_t* d_grid_out) {
+  API_ENTER(ctx);
+  unsigned long long n = 0;
+  int rc = box_check(ctx, map, vmin, dims, false, &n);
+  if (rc != LOAMX_OK || n == 0) return rc;
+  if (!d_grid_out) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null d_grid_out");
+  return launch_slice(ctx, map, vmin, dims, d_grid_out);
+}
+
+int loamx_occupancy_query(loamx_ctx* ctx, const loamx_occupancy_map* map, const double* points, size_t point_stride, size_t n, uint32_t* counts_out,
+                          uint8_t* state_out) {
+  API_ENTER(ctx);
+  int rc = query_check(ctx, map, points, point_stride, n);
+  if (rc != LOAMX_OK || n == 0 || (!counts_out && !state_out)) return rc;
+  if (n > (~(size_t)0) / (point_stride * sizeof(double))) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "the points do not fit the address space");
+  const size_t in_bytes = n * point_stride * sizeof(double);
+  untimed(ctx);
+  ENSURE(ctx, WS_OCC_IN, in_bytes);
+  ENSURE(ctx, WS_OCC_OUT, align256(n * 2 * sizeof(uint32_t)) + n);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_OCC_IN].p, points, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  char* b = static_cast<char*>(ctx->ws[WS_OCC_OUT].p);
+  launch_occupancy_query(map->t, map->rule.leaf, map->state_rule, wsp<double>(ctx, WS_OCC_IN), (uint32_t)point_stride, n, reinterpret_cast<uint32_t*>(b),
+                         reinterpret_cast<uint8_t*>(b + align256(n * 2 * sizeof(uint32_t))), ctx->stream);
+  rc = check_launch(ctx, "occupancy query kernel");
+  if (rc != LOAMX_OK) {
+    (void)hipStreamSynchronize(ctx->stream);  // (the upload must not outlive the caller's array)
+    return rc;
+  }
+  return read_out(ctx, n, counts_out, state_out);
+}
+
+int loamx_occupancy_box(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3], uint32_t* counts_out,
+                        uint8_t* state_out) {
+  API_ENTER(ctx);
+  unsigned long long n = 0;
+  int rc = box_check(ctx, map, vmin, dims, true, &n);
+  if (rc != LOAMX_OK || n == 0 || (!counts_out && !state_out)) return rc;
+  untimed(ctx);
+  ENSURE(ctx, WS_OCC_OUT, align256(n * 2 * sizeof(uint32_t)) + n);
+  char* b = static_cast<char*>(ctx->ws[WS_OCC_OUT].p);
+  rc = launch_box(ctx, map, vmin, dims, reinterpret_cast<uint32_t*>(b), reinterpret_cast<uint8_t*>(b + align256(n * 2 * sizeof(uint32_t))));
+  if (rc != LOAMX_OK) return rc;
+  return read_out(ctx, n, counts_out, state_out);
+}
+
+int loamx_occupancy_slice(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3], uint8_t* grid_out) {
+  API_ENTER(ctx);
+  unsigned long long n = 0;
+  int rc = box_check(ctx, map, vmin, dims, false, &n);
+  if (rc != LOAMX_OK || n == 0) return rc;
+  if (!grid_out) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null grid_out");
+  untimed(ctx);
+  ENSURE(ctx, WS_OCC_OUT, n);
+  rc = launch_slice(ctx, map, vmin, dims, wsp<uint8_t>(ctx, WS_OCC_OUT));
+  if (rc != LOAMX_OK) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(grid_out, ctx->ws[WS_OCC_OUT].p, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return LOAMX_OK;
+}
+
+int loamx_occupancy_stats_read(loamx_ctx* ctx, const loamx_occupancy_map* map, loamx_occupancy_stats* out) {
+  API_ENTER(ctx);
+  int rc = map_check(ctx, map);
+  if (rc != LOAMX_OK) return rc;
+  if (!out) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  unsigned long long words[kOccWords];
+  untimed(ctx);
+  HIP_TRY(ctx, hipMemcpyAsync(words, map->t.words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  out->rays_offered = map->offered, out->rays_hit = words[kOccWordHit], out->invalid = words[kOccWordInvalid];
+  out->range_short = words[kOccWordShort], out->range_long = words[kOccWordLong], out->outside = words[kOccWordOutside];
+  out->visits = words[kOccWordVisits], out->voxels = words[kOccWordVoxels], out->overflow = words[kOccWordOverflow];
+  return LOAMX_OK;
+}
+
+int loamx_occupancy_claims_read(loamx_ctx* ctx, const loamx_occupancy_map* map, uint64_t* claims) {
+  API_ENTER(ctx);
+  int rc = map_check(ctx, map);
+  if (rc != LOAMX_OK) return rc;
+  if (!claims) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  unsigned long long word = 0;
+  untimed(ctx);
+  HIP_TRY(ctx, hipMemcpyAsync(&word, map->t.words + kOccWordClaims, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *claims = word;
+  return LOAMX_OK;
+}
+
+}  // extern "C"

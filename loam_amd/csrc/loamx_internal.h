@@ -14,6 +14,7 @@
 #include "place_math.h"
 #include "segment_math.h"
 #include "visibility_math.h"
+#include "occupancy_math.h"
 #include "xcd_map.h"
 
 namespace loamx {
@@ -608,6 +609,35 @@ void launch_visibility_votes(const VisVotesCall& c, hipStream_t s);
 void launch_visibility_filter(const loamx_visibility_tally* d_votes, uint32_t n, uint32_t min_through, double through_ratio, const double* d_points,
                               uint32_t stride, uint8_t* d_keep, uint32_t* d_tiles, uint8_t* d_dynamic_out, double* d_xyz_out, uint32_t* d_index_out,
                               size_t capacity, uint32_t* d_n_out, hipStream_t s);
+
+/* ---- occupancy map (occupancy_kernels.hip; the rule: occupancy_math.h and loamx.h) ------------------------------------------------ */
+constexpr uint32_t kOccChunkRays = 1u << 30;                 // rays per launch of an add
+constexpr uint32_t kRegFlagNoOccupancyCombine = 1048576u;   // (loamx_ctx::reg_flags) one claim per visit, no run combining
+// counter words of a map (the rays offered are the host's)
+enum {
+  kOccWordHit = 0, kOccWordInvalid, kOccWordShort, kOccWordLong, kOccWordOutside, kOccWordVisits, kOccWordVoxels, kOccWordClaims,
+  kOccWordOverflow, kOccWords = 16
+};
+// Open-addressed table as CloudTable: 2^log2_cap slots; keys start as 0xFF bytes, counts and words as zero bytes.
+struct OccTable {
+  unsigned long long* keys;    // [cap] voxel key (map_math.h) or all ones (empty)
+  unsigned long long* counts;  // [cap] hits << 32 | passes
+  unsigned long long* words;   // [kOccWords]
+  uint32_t log2_cap;
+};
+// Rays p0 .. p0 + n - 1 of the call's array (0 < n <= kOccChunkRays), which lie in the clouds of `offs`; d_poses: the pose of
+// offs' first cloud onwards, or nullptr
+void launch_occupancy_walk(const void* d_points, bool f32, uint32_t stride, const OrgOffsets& offs, uint32_t n_clouds, unsigned long long p0,
+                           uint32_t n, const double* d_poses, const OccRule& rule, const OccTable& t, bool combine, hipStream_t s);
+// read-only, behind the walks on the same stream; the two outputs of the first two may each be nullptr
+void launch_occupancy_query(const OccTable& t, double leaf, const OccStateRule& sr, const double* d_points, uint32_t stride, unsigned long long n,
+                            uint32_t* d_counts_out, uint8_t* d_state_out, hipStream_t s);
+struct OccBox {
+  int32_t vmin[3];
+  uint32_t dims[3];
+};
+void launch_occupancy_box(const OccTable& t, const OccStateRule& sr, const OccBox& box, uint32_t* d_counts_out, uint8_t* d_state_out, hipStream_t s);
+void launch_occupancy_slice(const OccTable& t, const OccStateRule& sr, const OccBox& box, uint8_t* d_grid_out, hipStream_t s);
 
 /* ---- synthetic generator (synth_kernels.hip) --------------------------------------------------- */
 void launch_synth_pairs(uint64_t seed, uint64_t first_pair, size_t n_pairs, uint32_t H, uint32_t W, double sigma,

@@ -138,6 +138,30 @@ void cloud_map_add(loam::CloudMap& map, const py::array_t<T, py::array::c_style>
   loam::gpu::check(ctx, c_cloud_map_add(ctx, map.handle(), points.data(), (size_t)points.shape(1), (size_t)points.shape(0),
                                         world_T_sensor ? pose : nullptr));
 }
+// OccupancyMap: points and pose as for CloudMap
+inline int c_occupancy_add(loamx_ctx* c, loamx_occupancy_map* m, const double* p, size_t stride, size_t n, const double* pose) {
+  return loamx_occupancy_add_cloud(c, m, p, stride, n, pose);
+}
+inline int c_occupancy_add(loamx_ctx* c, loamx_occupancy_map* m, const float* p, size_t stride, size_t n, const double* pose) {
+  return loamx_occupancy_add_cloud_f32(c, m, p, stride, n, pose);
+}
+template <typename T>
+void occupancy_add(loam::OccupancyMap& map, const py::array_t<T, py::array::c_style>& points, const std::optional<loam::Pose3d>& world_T_sensor) {
+  if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
+  double pose[7];
+  if (world_T_sensor) world_T_sensor->toArray(pose);
+  loamx_ctx* ctx = loam::gpu::defaultContext();
+  py::gil_scoped_release release;
+  loam::gpu::check(ctx, c_occupancy_add(ctx, map.handle(), points.data(), (size_t)points.shape(1), (size_t)points.shape(0),
+                                        world_T_sensor ? pose : nullptr));
+}
+// vmin (3 ints) and dims (3 non-negative ints) of a voxel box
+inline void occupancy_box_args(const std::array<int64_t, 3>& vmin, const std::array<int64_t, 3>& dims, std::array<int32_t, 3>& v, std::array<uint32_t, 3>& d) {
+  for (int a = 0; a < 3; a++) {
+    if (vmin[a] < INT32_MIN || vmin[a] > INT32_MAX || dims[a] < 0 || dims[a] > (int64_t)UINT32_MAX) throw std::runtime_error("box: vmin or dims out of range");
+    v[a] = (int32_t)vmin[a], d[a] = (uint32_t)dims[a];
+  }
+}
 template <typename T>
 py::tuple organize_cloud(const py::array_t<T, py::array::c_style>& points, const loam::ScanLayout& layout, const std::optional<ArrRings>& rings) {
   if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
@@ -707,6 +731,73 @@ PYBIND11_MODULE(loam_python, m) {
         py::dict d;
         d["voxels"] = s.voxels, d["points_offered"] = s.points_offered, d["points_used"] = s.points_used, d["invalid"] = s.invalid;
         d["range"] = s.range, d["outside"] = s.outside, d["overflow"] = s.overflow;
+        return d;
+      });
+  // occupancy map (include/loamx.h: "occupancy map"): an extension like CloudMap
+  py::class_<loam::OccupancyParams>(m, "OccupancyParams")
+      .def(py::init<>())
+      .def_readwrite("leaf", &loam::OccupancyParams::leaf)
+      .def_readwrite("min_range", &loam::OccupancyParams::min_range)
+      .def_readwrite("max_range", &loam::OccupancyParams::max_range)
+      .def_readwrite("end_margin", &loam::OccupancyParams::end_margin)
+      .def_readwrite("clip_long", &loam::OccupancyParams::clip_long)
+      .def_readwrite("min_hits", &loam::OccupancyParams::min_hits)
+      .def_readwrite("occ_ratio", &loam::OccupancyParams::occ_ratio)
+      .def_readwrite("min_passes", &loam::OccupancyParams::min_passes);
+  py::class_<loam::OccupancyMap> occupancy_map(m, "OccupancyMap");
+  occupancy_map.attr("UNKNOWN") = (int)loam::Occupancy::UNKNOWN;
+  occupancy_map.attr("FREE") = (int)loam::Occupancy::FREE;
+  occupancy_map.attr("OCCUPIED") = (int)loam::Occupancy::OCCUPIED;
+  occupancy_map
+      .def(py::init<const loam::OccupancyParams&, size_t>(), py::arg("params") = loam::OccupancyParams(), py::arg("max_voxels") = (size_t)1 << 20)
+      .def_property_readonly("params", &loam::OccupancyMap::params)
+      .def_property_readonly("max_voxels", &loam::OccupancyMap::maxVoxels)
+      .def("add", &occupancy_add<float>, py::arg("points"), py::arg("world_T_sensor") = py::none())
+      .def("add", &occupancy_add<double>, py::arg("points"), py::arg("world_T_sensor") = py::none())
+      .def("clear", &loam::OccupancyMap::clear)
+      .def(
+          "query",
+          [](const loam::OccupancyMap& map, const Arr& points) {
+            if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
+            const py::ssize_t n = points.shape(0);
+            py::array_t<uint32_t> counts(std::vector<py::ssize_t>{n, 2});
+            py::array_t<uint8_t> states(n);
+            loamx_ctx* ctx = loam::gpu::defaultContext();
+            loam::gpu::check(ctx, loamx_occupancy_query(ctx, map.handle(), points.data(), (size_t)points.shape(1), (size_t)n, counts.mutable_data(),
+                                                        states.mutable_data()));
+            return py::make_tuple(counts, states);
+          },
+          py::arg("points"))
+      .def(
+          "box",
+          [](const loam::OccupancyMap& map, const std::array<int64_t, 3>& vmin, const std::array<int64_t, 3>& dims) {
+            std::array<int32_t, 3> v;
+            std::array<uint32_t, 3> d;
+            occupancy_box_args(vmin, dims, v, d);
+            py::array_t<uint32_t> counts(std::vector<py::ssize_t>{(py::ssize_t)d[2], (py::ssize_t)d[1], (py::ssize_t)d[0], 2});
+            py::array_t<uint8_t> states(std::vector<py::ssize_t>{(py::ssize_t)d[2], (py::ssize_t)d[1], (py::ssize_t)d[0]});
+            loamx_ctx* ctx = loam::gpu::defaultContext();
+            loam::gpu::check(ctx, loamx_occupancy_box(ctx, map.handle(), v.data(), d.data(), counts.mutable_data(), states.mutable_data()));
+            return py::make_tuple(counts, states);
+          },
+          py::arg("vmin"), py::arg("dims"))
+      .def(
+          "slice",
+          [](const loam::OccupancyMap& map, const std::array<int64_t, 3>& vmin, const std::array<int64_t, 3>& dims) {
+            std::array<int32_t, 3> v;
+            std::array<uint32_t, 3> d;
+            occupancy_box_args(vmin, dims, v, d);
+            py::array_t<uint8_t> grid(std::vector<py::ssize_t>{(py::ssize_t)d[1], (py::ssize_t)d[0]});
+            loamx_ctx* ctx = loam::gpu::defaultContext();
+            loam::gpu::check(ctx, loamx_occupancy_slice(ctx, map.handle(), v.data(), d.data(), grid.mutable_data()));
+            return grid;
+          },
+          py::arg("vmin"), py::arg("dims"))
+      .def("stats", [](const loam::OccupancyMap& map) {
+        const loam::OccupancyStats s = map.stats();
+        py::dict d;
+        d["rays_offered"] = s.rays_offered, d["rays_hit"] = s.rays_hit, d["invalid"] = s.invalid, d["range_short"] = s.range_short;
+        d["range_long"] = s.range_long, d["outside"] = s.outside, d["visits"] = s.visits, d["voxels"] = s.voxels, d["overflow"] = s.overflow;
         return d;
       });
   py::class_<loam::PoseGraphParams>(m, "PoseGraphParams")
