@@ -175,3 +175,9 @@ def real_scan(name, H=32, W=512, dtype=np.float64):
     import outdoor_scenes as S
     origin, yaw = S.sensor_origin(name, 0)
     return np.ascontiguousarray(S.scan_at(name, 0, origin, yaw, H=H, W=W, noise_seed=0).astype(dtype))
+
+
+def five_scans(H, W):
+    """three ray-cast scenes and two masks on a sphere, (5, H W, 3) float64: what the batch tests segment"""
+    return np.stack([real_scan("canyon", H, W), mask_scan(random_mask(H, W, 5)), real_scan("field", H, W), mask_scan(serpentine(H, W)),
+                     real_scan("lot", H, W)])

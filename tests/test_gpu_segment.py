@@ -234,9 +234,7 @@ def test_drop_switches():
         check(scan, H, W, capi.SegmentParams(drop_outliers=do, drop_ground=dg, min_cluster_points=6), where=("drop", do, dg))
 
 
-def five_scans(H, W):
-    return np.stack([M.real_scan("canyon", H, W), M.mask_scan(M.random_mask(H, W, 5)), M.real_scan("field", H, W), M.mask_scan(M.serpentine(H, W)),
-                     M.real_scan("lot", H, W)])
+five_scans = M.five_scans
 
 
 def test_a_batch_equals_single_calls_and_two_runs_give_the_same_bytes():
