@@ -1020,37 +1020,41 @@ class PlaceDb:
             pass
 
 
-class CloudMap:
-    """A cloud map (loamx_cloud_map; include/loamx.h, "cloud map"): posed clouds accumulated on a voxel grid as integer sums, one
-    centroid per voxel, the voxels in order of first appearance; on the context's device. close() frees it; the context must
-    still be open."""
+class _VoxelMap:
+    """What CloudMap and OccupancyMap share: the handle, clear, the two forms of an add, claims and close. A subclass names the
+    prefix of its C entry points, its parameters class and itself (the error texts)."""
+    _PREFIX = _PARAMS = _NAME = None
 
     def __init__(self, ctx, params=None, max_voxels=1 << 20):
-        self.ctx, self.params = ctx, params or CloudMapParams()
+        self.ctx, self.params = ctx, params or self._PARAMS()
         max_voxels = int(max_voxels)
         if max_voxels < 0:
-            raise ValueError("cloud_map: max_voxels is negative")
+            raise ValueError(f"{self._NAME.replace(' ', '_')}: max_voxels is negative")
         st = self.params.struct()
         h = C.c_void_p()
-        ctx._check(ctx.lib.loamx_cloud_map_create(ctx.h, C.byref(st), max_voxels, C.byref(h)))
+        ctx._check(self._fn("create")(ctx.h, C.byref(st), max_voxels, C.byref(h)))
         self.h, self.max_voxels = h, max_voxels
+
+    def _fn(self, name):
+        return getattr(self.ctx.lib, self._PREFIX + name)
 
     def _handle(self):
         if not getattr(self, "h", None):
-            raise ValueError("the cloud map is closed")
+            raise ValueError(f"the {self._NAME} is closed")
         return self.h
 
     def clear(self):
-        """an empty map again (loamx_cloud_map_clear). Asynchronous."""
-        self.ctx._check(self.ctx.lib.loamx_cloud_map_clear(self.ctx.h, self._handle()))
+        """an empty map again (loamx_cloud_map_clear / loamx_occupancy_clear). Asynchronous."""
+        self.ctx._check(self._fn("clear")(self.ctx.h, self._handle()))
 
     def add_clouds_dev(self, d_points, point_stride, cloud_offsets, d_poses=0, f32=False):
         """len(cloud_offsets) - 1 device-resident clouds back to back, cloud c at the pose d_poses[c] (a device address of
-        n_clouds x 7 doubles, or 0 = no transform) (loamx_cloud_map_add_clouds_dev[_f32]). Asynchronous."""
+        n_clouds x 7 doubles, or 0 = no transform) (loamx_cloud_map_add_clouds_dev[_f32] / loamx_occupancy_add_clouds_dev[_f32]).
+        Asynchronous."""
         off = _offsets(cloud_offsets, "add_clouds_dev")
         if int(point_stride) < 0:
             raise ValueError("add_clouds_dev: point_stride is negative")
-        fn = self.ctx.lib.loamx_cloud_map_add_clouds_dev_f32 if f32 else self.ctx.lib.loamx_cloud_map_add_clouds_dev
+        fn = self._fn("add_clouds_dev_f32" if f32 else "add_clouds_dev")
         self.ctx._check(fn(self.ctx.h, self._handle(), d_points or None, int(point_stride), off.ctypes.data_as(C.POINTER(C.c_size_t)),
                            off.size - 1, d_poses or None))
 
@@ -1067,8 +1071,35 @@ class CloudMap:
             p = np.ascontiguousarray(pose, dtype=np.float64)
             if p.shape != (7,):
                 raise ValueError(f"add_cloud: a pose is 7 numbers (qx qy qz qw tx ty tz), not {p.shape}")
-        fn = self.ctx.lib.loamx_cloud_map_add_cloud_f32 if pts.dtype == np.float32 else self.ctx.lib.loamx_cloud_map_add_cloud
+        fn = self._fn("add_cloud_f32" if pts.dtype == np.float32 else "add_cloud")
         self.ctx._check(fn(self.ctx.h, self._handle(), pts.ctypes.data, pts.shape[1], pts.shape[0], None if p is None else p.ctypes.data))
+
+    def claims(self):
+        """probes begun by the map's add kernel since the last clear: one per used point (cloud map) or per hit and per pass
+        (occupancy map) in the plain form, one per run of a wavefront with run combining (loamx_cloud_map_claims_read /
+        loamx_occupancy_claims_read; synchronises)"""
+        n = C.c_uint64(0)
+        self.ctx._check(self._fn("claims_read")(self.ctx.h, self._handle(), C.byref(n)))
+        return n.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self._fn("destroy")(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CloudMap(_VoxelMap):
+    """A cloud map (loamx_cloud_map; include/loamx.h, "cloud map"): posed clouds accumulated on a voxel grid as integer sums, one
+    centroid per voxel, the voxels in order of first appearance; on the context's device. close() frees it; the context must
+    still be open."""
+    _PREFIX, _PARAMS, _NAME = "loamx_cloud_map_", CloudMapParams, "cloud map"
 
     def emit_dev(self, d_xyz_out, capacity, d_n_out, min_points=1, d_count_out=0, d_first_out=0):
         """the centroids of the voxels with count >= min_points in list order, at most `capacity`, to device addresses; the
@@ -1098,25 +1129,6 @@ class CloudMap:
         self.ctx._check(self.ctx.lib.loamx_cloud_map_stats_read(self.ctx.h, self._handle(), st.ctypes.data))
         return st[0]
 
-    def claims(self):
-        """probes begun by the accumulate kernel since the last clear: one per used point in the plain form, one per run of a
-        wavefront with run combining (loamx_cloud_map_claims_read; synchronises)"""
-        n = C.c_uint64(0)
-        self.ctx._check(self.ctx.lib.loamx_cloud_map_claims_read(self.ctx.h, self._handle(), C.byref(n)))
-        return n.value
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                self.ctx.lib.loamx_cloud_map_destroy(self.ctx.h, self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _box_args(vmin, dims, what):
     """(int32[3], uint32[3]) of a voxel box"""
@@ -1128,54 +1140,11 @@ def _box_args(vmin, dims, what):
     return np.ascontiguousarray(v, dtype=np.int32), np.ascontiguousarray(d, dtype=np.uint32)
 
 
-class OccupancyMap:
+class OccupancyMap(_VoxelMap):
     """An occupancy map (loamx_occupancy_map; include/loamx.h, "occupancy map"): every beam of posed clouds walked through a voxel
     grid, two integer counts per voxel (hits, passes), read back as free / occupied / unknown per point, per voxel of a dense
     box or per column of a 2-D slice; on the context's device. close() frees it; the context must still be open."""
-
-    def __init__(self, ctx, params=None, max_voxels=1 << 20):
-        self.ctx, self.params = ctx, params or OccupancyParams()
-        max_voxels = int(max_voxels)
-        if max_voxels < 0:
-            raise ValueError("occupancy_map: max_voxels is negative")
-        st = self.params.struct()
-        h = C.c_void_p()
-        ctx._check(ctx.lib.loamx_occupancy_create(ctx.h, C.byref(st), max_voxels, C.byref(h)))
-        self.h, self.max_voxels = h, max_voxels
-
-    def _handle(self):
-        if not getattr(self, "h", None):
-            raise ValueError("the occupancy map is closed")
-        return self.h
-
-    def clear(self):
-        """an empty map again (loamx_occupancy_clear). Asynchronous."""
-        self.ctx._check(self.ctx.lib.loamx_occupancy_clear(self.ctx.h, self._handle()))
-
-    def add_clouds_dev(self, d_points, point_stride, cloud_offsets, d_poses=0, f32=False):
-        """the arguments of CloudMap.add_clouds_dev (loamx_occupancy_add_clouds_dev[_f32]). Asynchronous."""
-        off = _offsets(cloud_offsets, "add_clouds_dev")
-        if int(point_stride) < 0:
-            raise ValueError("add_clouds_dev: point_stride is negative")
-        fn = self.ctx.lib.loamx_occupancy_add_clouds_dev_f32 if f32 else self.ctx.lib.loamx_occupancy_add_clouds_dev
-        self.ctx._check(fn(self.ctx.h, self._handle(), d_points or None, int(point_stride), off.ctypes.data_as(C.POINTER(C.c_size_t)),
-                           off.size - 1, d_poses or None))
-
-    def add_cloud(self, points, pose=None):
-        """One cloud (or organised scan) in host memory, (n, k >= 3) float64 / float32, at a host pose7 or None (no transform)."""
-        pts = np.asarray(points)
-        if pts.dtype != np.float32:
-            pts = np.asarray(pts, dtype=np.float64)
-        if pts.ndim != 2 or pts.shape[1] < 3:
-            raise ValueError(f"add_cloud: points must be (n, 3) or (n, k >= 3), not {pts.shape}")
-        pts = np.ascontiguousarray(pts)
-        p = None
-        if pose is not None:
-            p = np.ascontiguousarray(pose, dtype=np.float64)
-            if p.shape != (7,):
-                raise ValueError(f"add_cloud: a pose is 7 numbers (qx qy qz qw tx ty tz), not {p.shape}")
-        fn = self.ctx.lib.loamx_occupancy_add_cloud_f32 if pts.dtype == np.float32 else self.ctx.lib.loamx_occupancy_add_cloud
-        self.ctx._check(fn(self.ctx.h, self._handle(), pts.ctypes.data, pts.shape[1], pts.shape[0], None if p is None else p.ctypes.data))
+    _PREFIX, _PARAMS, _NAME = "loamx_occupancy_", OccupancyParams, "occupancy map"
 
     def query_dev(self, d_points, point_stride, n, d_counts_out=0, d_state_out=0):
         """counts (uint32 [n][2]: hits, passes) and state (uint8 [n]) of the voxels of n device-resident points (double), to
@@ -1230,25 +1199,6 @@ class OccupancyMap:
         st = np.zeros(1, dtype=OCCUPANCY_STATS_DTYPE)
         self.ctx._check(self.ctx.lib.loamx_occupancy_stats_read(self.ctx.h, self._handle(), st.ctypes.data))
         return st[0]
-
-    def claims(self):
-        """probes begun by the walk kernel since the last clear: one per hit and per pass in the plain form, one per run of a
-        wavefront with run combining (loamx_occupancy_claims_read; synchronises)"""
-        n = C.c_uint64(0)
-        self.ctx._check(self.ctx.lib.loamx_occupancy_claims_read(self.ctx.h, self._handle(), C.byref(n)))
-        return n.value
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                self.ctx.lib.loamx_occupancy_destroy(self.ctx.h, self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class DeviceBuffer:

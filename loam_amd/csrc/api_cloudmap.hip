@@ -1,21 +1,15 @@
 // api_cloudmap.hip — the cloud map (loamx.h, "cloud map"): the map handle with its one device block (table, voxel list, counters,
 // the scratch of a round of launches), the add, emit, clear and stats entry points and their host forms.
-#include "api_host.h"
+#include "api_voxelmap.h"
 #include "cloudmap_math.h"
 
-struct loamx_cloud_map {
-  loamx_ctx* owner = nullptr;  // the context it was created on: its mutex and stream order every use of the scratch below
-  int device = 0;
+struct loamx_cloud_map : loamx::VoxelMapBase {  // ones: keys + first; zeros: sums, count, counters and lengths
   loamx_cloud_map_params params = {};
   loamx::CloudRule rule = {};
   loamx::CloudTable t = {};
-  void* block = nullptr;
-  size_t ones_bytes = 0;    // keys + first, at the block's start: 0xFF bytes in an empty map
-  size_t zeros_bytes = 0;   // sums, count, counters and lengths behind them: zero bytes in an empty map
   uint32_t* d_slot = nullptr;   // scratch of a round of an add: [kCloudChunkPoints]
   uint8_t* d_keep = nullptr;    // [max(kCloudChunkPoints, max_voxels)] (add and emit)
   uint32_t* d_tiles = nullptr;  // the compaction's tiles for as many
-  uint64_t offered = 0;         // points offered since the last clear (the host's copy is the running index of the next call)
 };
 
 using namespace loamx;
@@ -24,57 +18,21 @@ namespace {
 
 constexpr size_t kCloudMaxVoxels = (size_t)1 << 30;
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int map_check(loamx_ctx* ctx, const loamx_cloud_map* map) {
-  if (!map) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null cloud map");
-  if (map->owner != ctx) return fail(ctx, LOAMX_ERR_BAD_PARAM, "the cloud map was created on another context");
-  return LOAMX_OK;
-}
-
-int clear_locked(loamx_ctx* ctx, loamx_cloud_map* map) {
-  untimed(ctx);
-  HIP_TRY(ctx, hipMemsetAsync(map->block, 0xFF, map->ones_bytes, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(static_cast<char*>(map->block) + map->ones_bytes, 0, map->zeros_bytes, ctx->stream));
-  map->offered = 0;
-  return LOAMX_OK;
-}
-
-// the argument checks the device and the host forms of an add share; *total: the points of the call
-int add_check(loamx_ctx* ctx, const loamx_cloud_map* map, const void* points, size_t stride, const size_t* offsets, size_t n_clouds, size_t* total) {
-  int rc = map_check(ctx, map);
-  if (rc != LOAMX_OK) return rc;
-  *total = 0;
-  if (stride < 3) return fail(ctx, LOAMX_ERR_BAD_PARAM, "point_stride must be >= 3");
-  if (stride > 0xFFFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "point_stride does not fit 32 bits");
-  if (n_clouds == 0) return LOAMX_OK;
-  if (!offsets) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null cloud_offsets");
-  for (size_t c = 0; c < n_clouds; c++)
-    if (offsets[c + 1] < offsets[c]) return fail(ctx, LOAMX_ERR_BAD_PARAM, "cloud_offsets must ascend");
-  *total = offsets[n_clouds] - offsets[0];
-  if (*total && !points) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null points");
-  if (*total > kCloudMaxOffered || map->offered + *total > kCloudMaxOffered)
-    return fail(ctx, LOAMX_ERR_UNSUPPORTED, "a cloud map takes at most 2^32 - 2 points between two clears");
-  return LOAMX_OK;
-}
-
-// the clouds of the call, kOrgChunkClouds at a time (their offsets travel as a kernel argument), their points in rounds of
-// kCloudChunkPoints (the caller holds ctx->mu, has selected the device and checked the arguments)
-int add_locked(loamx_ctx* ctx, loamx_cloud_map* map, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
+// the clouds of the call chunk by chunk, their points in rounds of kCloudChunkPoints; `offered` is the running index of the call's
+// first point
+int add_locked(loamx_ctx* ctx, VoxelMapBase* base, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
                const double* d_poses) {
+  loamx_cloud_map* map = static_cast<loamx_cloud_map*>(base);
   const bool combine = !(ctx->reg_flags & kRegFlagNoCloudmapCombine);
   const double point_bytes = f32 ? 12.0 : 24.0;
-  for (size_t c0 = 0; c0 < n_clouds; c0 += kOrgChunkClouds) {
-    const uint32_t nc = (uint32_t)(n_clouds - c0 < kOrgChunkClouds ? n_clouds - c0 : kOrgChunkClouds);
-    OrgOffsets offs;
-    for (uint32_t c = 0; c <= kOrgChunkClouds; c++) offs.off[c] = offsets[c0 + (c < nc ? c : nc)];
-    for (unsigned long long p0 = offs.off[0]; p0 < offs.off[nc]; p0 += kCloudChunkPoints) {
-      const uint32_t n = (uint32_t)(offs.off[nc] - p0 < kCloudChunkPoints ? offs.off[nc] - p0 : kCloudChunkPoints);
+  for (CloudChunks ch(offsets, n_clouds); ch.next();) {
+    for (unsigned long long p0 = ch.offs.off[0]; p0 < ch.offs.off[ch.nc]; p0 += kCloudChunkPoints) {
+      const uint32_t n = (uint32_t)(ch.offs.off[ch.nc] - p0 < kCloudChunkPoints ? ch.offs.off[ch.nc] - p0 : kCloudChunkPoints);
       const uint32_t g0 = (uint32_t)(map->offered + (p0 - offsets[0]));
       {
         TimedScope timed(ctx, combine ? LOAMX_K_CLOUD_ACCUMULATE : LOAMX_K_CLOUD_ACCUMULATE_PLAIN, point_bytes * n, true);
-        launch_cloud_accumulate(d_points, f32, (uint32_t)stride, offs, nc, p0, n, g0, d_poses ? d_poses + c0 * 7 : nullptr, map->rule, map->t, combine,
-                                map->d_slot, ctx->stream);
+        launch_cloud_accumulate(d_points, f32, (uint32_t)stride, ch.offs, ch.nc, p0, n, g0, d_poses ? d_poses + ch.c0 * 7 : nullptr, map->rule, map->t,
+                                combine, map->d_slot, ctx->stream);
       }
       {
         TimedScope timed(ctx, LOAMX_K_CLOUD_LIST, 5.0 * n, true);
@@ -87,39 +45,10 @@ int add_locked(loamx_ctx* ctx, loamx_cloud_map* map, const void* d_points, bool 
   return LOAMX_OK;
 }
 
-int add_dev(loamx_ctx* ctx, loamx_cloud_map* map, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
-            const double* d_poses) {
-  API_ENTER(ctx);
-  size_t total = 0;
-  int rc = add_check(ctx, map, d_points, stride, offsets, n_clouds, &total);
-  if (rc != LOAMX_OK || total == 0) return rc;
-  return add_locked(ctx, map, d_points, f32, stride, offsets, n_clouds, d_poses);
-}
-
-int add_host(loamx_ctx* ctx, loamx_cloud_map* map, const void* points, bool f32, size_t stride, size_t n, const double* pose) {
-  API_ENTER(ctx);
-  const size_t offsets[2] = {0, n};
-  size_t total = 0;
-  int rc = add_check(ctx, map, points, stride, offsets, 1, &total);
-  if (rc != LOAMX_OK || total == 0) return rc;
-  if (n > (~(size_t)0) / (stride * sizeof(double))) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "the cloud does not fit the address space");
-  const size_t in_bytes = n * stride * (f32 ? sizeof(float) : sizeof(double));
-  untimed(ctx);
-  ENSURE(ctx, WS_CLOUD_IN, in_bytes);
-  ENSURE(ctx, WS_CLOUD_POSE, 7 * sizeof(double));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_CLOUD_IN].p, points, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (pose) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_CLOUD_POSE].p, pose, 7 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  rc = add_locked(ctx, map, ctx->ws[WS_CLOUD_IN].p, f32, stride, offsets, 1, pose ? wsp<double>(ctx, WS_CLOUD_POSE) : nullptr);
-  if (rc != LOAMX_OK) {
-    (void)hipStreamSynchronize(ctx->stream);  // (the upload must not outlive the caller's array)
-    return rc;
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return LOAMX_OK;
-}
+const VoxelMapKind kKind = {"cloud map", "a cloud map", "points", kCloudMaxOffered, WS_CLOUD_IN, WS_CLOUD_POSE, add_locked};
 
 int emit_check(loamx_ctx* ctx, const loamx_cloud_map* map, const void* xyz, size_t capacity, const void* n_out) {
-  int rc = map_check(ctx, map);
+  int rc = voxel_map_check(ctx, map, kKind);
   if (rc != LOAMX_OK) return rc;
   if (!n_out || (capacity && !xyz)) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
   return LOAMX_OK;
@@ -156,8 +85,7 @@ int loamx_cloud_map_create(loamx_ctx* ctx, const loamx_cloud_map_params* params,
   map->params = *params;
   map->rule.leaf = params->leaf;
   map->rule.min_r2 = params->min_range * params->min_range, map->rule.max_r2 = params->max_range * params->max_range;
-  uint32_t log2_cap = 4;  // (voxel_hash takes 4 .. 32 bits)
-  while (((size_t)1 << log2_cap) < 2 * max_voxels) log2_cap++;
+  const uint32_t log2_cap = voxel_table_log2(2 * max_voxels);
   const size_t cap = (size_t)1 << log2_cap, scratch = max_voxels > kCloudChunkPoints ? max_voxels : kCloudChunkPoints;
   const size_t o_keys = 0, o_first = o_keys + align256(cap * sizeof(unsigned long long));
   const size_t o_sums = o_first + align256(cap * sizeof(uint32_t)), o_count = o_sums + align256(cap * 3 * sizeof(unsigned long long));
@@ -179,7 +107,7 @@ int loamx_cloud_map_create(loamx_ctx* ctx, const loamx_cloud_map_params* params,
   map->t.log2_cap = log2_cap, map->t.max_voxels = (uint32_t)max_voxels;
   map->d_slot = reinterpret_cast<uint32_t*>(b + o_slot), map->d_keep = reinterpret_cast<uint8_t*>(b + o_keep);
   map->d_tiles = reinterpret_cast<uint32_t*>(b + o_tiles);
-  int rc = clear_locked(ctx, map);
+  int rc = voxel_map_clear(ctx, map);
   if (rc != LOAMX_OK) {
     (void)hipFree(map->block);
     delete map;
@@ -191,39 +119,31 @@ int loamx_cloud_map_create(loamx_ctx* ctx, const loamx_cloud_map_params* params,
 
 void loamx_cloud_map_destroy(loamx_ctx* ctx, loamx_cloud_map* map) {
   if (!map) return;
-  if (ctx) {
-    std::lock_guard<std::mutex> guard(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);  // (kernels still working on the map)
-    if (map->block) (void)hipFree(map->block);
-    delete map;
-    return;
-  }
-  if (map->block) (void)hipFree(map->block);
+  voxel_map_destroy(ctx, map);
   delete map;
 }
 
 int loamx_cloud_map_clear(loamx_ctx* ctx, loamx_cloud_map* map) {
   API_ENTER(ctx);
-  int rc = map_check(ctx, map);
+  int rc = voxel_map_check(ctx, map, kKind);
   if (rc != LOAMX_OK) return rc;
-  return clear_locked(ctx, map);
+  return voxel_map_clear(ctx, map);
 }
 
 int loamx_cloud_map_add_clouds_dev(loamx_ctx* ctx, loamx_cloud_map* map, const double* d_points, size_t point_stride, const size_t* cloud_offsets,
                                    size_t n_clouds, const double* d_poses) {
-  return add_dev(ctx, map, d_points, false, point_stride, cloud_offsets, n_clouds, d_poses);
+  return voxel_map_add_dev(ctx, map, kKind, d_points, false, point_stride, cloud_offsets, n_clouds, d_poses);
 }
 int loamx_cloud_map_add_clouds_dev_f32(loamx_ctx* ctx, loamx_cloud_map* map, const float* d_points, size_t point_stride, const size_t* cloud_offsets,
                                        size_t n_clouds, const double* d_poses) {
-  return add_dev(ctx, map, d_points, true, point_stride, cloud_offsets, n_clouds, d_poses);
+  return voxel_map_add_dev(ctx, map, kKind, d_points, true, point_stride, cloud_offsets, n_clouds, d_poses);
 }
 int loamx_cloud_map_add_cloud(loamx_ctx* ctx, loamx_cloud_map* map, const double* points, size_t point_stride, size_t n_points, const double pose[7]) {
-  return add_host(ctx, map, points, false, point_stride, n_points, pose);
+  return voxel_map_add_host(ctx, map, kKind, points, false, point_stride, n_points, pose);
 }
 int loamx_cloud_map_add_cloud_f32(loamx_ctx* ctx, loamx_cloud_map* map, const float* points, size_t point_stride, size_t n_points,
                                   const double pose[7]) {
-  return add_host(ctx, map, points, true, point_stride, n_points, pose);
+  return voxel_map_add_host(ctx, map, kKind, points, true, point_stride, n_points, pose);
 }
 
 int loamx_cloud_map_emit_dev(loamx_ctx* ctx, const loamx_cloud_map* map, uint32_t min_points, double* d_xyz_out, uint32_t* d_count_out,
@@ -264,7 +184,7 @@ int loamx_cloud_map_emit(loamx_ctx* ctx, const loamx_cloud_map* map, uint32_t mi
 
 int loamx_cloud_map_stats_read(loamx_ctx* ctx, const loamx_cloud_map* map, loamx_cloud_map_stats* out) {
   API_ENTER(ctx);
-  int rc = map_check(ctx, map);
+  int rc = voxel_map_check(ctx, map, kKind);
   if (rc != LOAMX_OK) return rc;
   if (!out) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
   unsigned long long words[kCloudWords];
@@ -280,16 +200,7 @@ int loamx_cloud_map_stats_read(loamx_ctx* ctx, const loamx_cloud_map* map, loamx
 }
 
 int loamx_cloud_map_claims_read(loamx_ctx* ctx, const loamx_cloud_map* map, uint64_t* claims) {
-  API_ENTER(ctx);
-  int rc = map_check(ctx, map);
-  if (rc != LOAMX_OK) return rc;
-  if (!claims) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
-  unsigned long long word = 0;
-  untimed(ctx);
-  HIP_TRY(ctx, hipMemcpyAsync(&word, map->t.words + kCloudWordClaims, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  *claims = word;
-  return LOAMX_OK;
+  return voxel_map_read_word(ctx, map, kKind, map ? map->t.words + kCloudWordClaims : nullptr, claims);
 }
 
 }  // extern "C"

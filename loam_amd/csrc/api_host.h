@@ -331,6 +331,27 @@ int reg_dump(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, const loamx_
 // activate: behind reg_solve, where every pair has stopped (see the definition)
 int reg_information(loamx_ctx* ctx, const RegBatch& B, const RegConfig& C, InfoPartial* info_partials, loamx_reg_information* d_info, bool activate);
 
+/* ---- the clouds of a call, kOrgChunkClouds at a time (their offsets travel as a kernel argument) ------------------------------ */
+// for (CloudChunks ch(offsets, n_clouds); ch.next();): clouds c0 .. c0 + nc - 1, their offsets in `offs` (the entries behind the
+// last cloud repeat its end), `largest`: the points of the chunk's largest cloud
+struct CloudChunks {
+  const size_t* offsets;
+  size_t n_clouds, c0 = 0;
+  uint32_t nc = 0;
+  OrgOffsets offs;
+  unsigned long long largest = 0;
+  CloudChunks(const size_t* offsets_, size_t n_clouds_) : offsets(offsets_), n_clouds(n_clouds_) {}
+  bool next() {
+    c0 += nc;
+    if (c0 >= n_clouds) return false;
+    nc = (uint32_t)(n_clouds - c0 < kOrgChunkClouds ? n_clouds - c0 : kOrgChunkClouds);
+    largest = 0;
+    for (uint32_t c = 0; c <= kOrgChunkClouds; c++) offs.off[c] = offsets[c0 + (c < nc ? c : nc)];
+    for (uint32_t c = 0; c < nc; c++) largest = offs.off[c + 1] - offs.off[c] > largest ? offs.off[c + 1] - offs.off[c] : largest;
+    return true;
+  }
+};
+
 /* ---- persistent index ------------------------------------------------------------------------------------------------ */
 // kind k of a persistent index as the search and build kernels take it
 inline GridSet index_grid_set(const loamx_target_index* idx, int k) {

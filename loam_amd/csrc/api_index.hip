@@ -287,11 +287,6 @@ MapTmp map_tmp_carve(void* base, size_t n) {
   t.keep = p;
   return t;
 }
-uint32_t voxel_table_log2(size_t slots_min) {
-  uint32_t l = 4;
-  while (((size_t)1 << l) < slots_min) l++;
-  return l;
-}
 
 // Brings kind k's occupancy table to "describes pts[k][0, n[k]) at `leaf`, with room for n_add more points below half
 // load". (Re)built from the map's own points when there is none, after a crop or a failed call (vox_valid), when the leaf

@@ -1,18 +1,12 @@
 // api_occupancy.hip — the occupancy map (loamx.h, "occupancy map"): the map handle with its one device block (table and counters),
 // the add, clear, query, box, slice and stats entry points and their host forms.
-#include "api_host.h"
+#include "api_voxelmap.h"
 
-struct loamx_occupancy_map {
-  loamx_ctx* owner = nullptr;  // the context it was created on: its mutex and stream order every use
-  int device = 0;
+struct loamx_occupancy_map : loamx::VoxelMapBase {  // ones: keys; zeros: counts and counters
   loamx_occupancy_params params = {};
   loamx::OccRule rule = {};
   loamx::OccStateRule state_rule = {};
   loamx::OccTable t = {};
-  void* block = nullptr;
-  size_t ones_bytes = 0;   // keys, at the block's start: 0xFF bytes in an empty map
-  size_t zeros_bytes = 0;  // counts and counters behind them: zero bytes in an empty map
-  uint64_t offered = 0;    // rays offered since the last clear
 };
 
 using namespace loamx;
@@ -22,53 +16,16 @@ namespace {
 constexpr size_t kOccMaxVoxels = (size_t)1 << 30;
 constexpr unsigned long long kOccMaxRead = 1ull << 31;  // points of a query, voxels of a box
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int map_check(loamx_ctx* ctx, const loamx_occupancy_map* map) {
-  if (!map) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null occupancy map");
-  if (map->owner != ctx) return fail(ctx, LOAMX_ERR_BAD_PARAM, "the occupancy map was created on another context");
-  return LOAMX_OK;
-}
-
-int clear_locked(loamx_ctx* ctx, loamx_occupancy_map* map) {
-  untimed(ctx);
-  HIP_TRY(ctx, hipMemsetAsync(map->block, 0xFF, map->ones_bytes, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(static_cast<char*>(map->block) + map->ones_bytes, 0, map->zeros_bytes, ctx->stream));
-  map->offered = 0;
-  return LOAMX_OK;
-}
-
-// the argument checks the device and the host forms of an add share; *total: the rays of the call
-int add_check(loamx_ctx* ctx, const loamx_occupancy_map* map, const void* points, size_t stride, const size_t* offsets, size_t n_clouds, size_t* total) {
-  int rc = map_check(ctx, map);
-  if (rc != LOAMX_OK) return rc;
-  *total = 0;
-  if (stride < 3) return fail(ctx, LOAMX_ERR_BAD_PARAM, "point_stride must be >= 3");
-  if (stride > 0xFFFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "point_stride does not fit 32 bits");
-  if (n_clouds == 0) return LOAMX_OK;
-  if (!offsets) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null cloud_offsets");
-  for (size_t c = 0; c < n_clouds; c++)
-    if (offsets[c + 1] < offsets[c]) return fail(ctx, LOAMX_ERR_BAD_PARAM, "cloud_offsets must ascend");
-  *total = offsets[n_clouds] - offsets[0];
-  if (*total && !points) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null points");
-  if (*total > kOccMaxOffered || map->offered + *total > kOccMaxOffered)
-    return fail(ctx, LOAMX_ERR_UNSUPPORTED, "an occupancy map takes at most 2^32 - 2 rays between two clears");
-  return LOAMX_OK;
-}
-
-// the clouds of the call, kOrgChunkClouds at a time (their offsets travel as a kernel argument), their rays in launches of
-// kOccChunkRays (the caller holds ctx->mu, has selected the device and checked the arguments)
-int add_locked(loamx_ctx* ctx, loamx_occupancy_map* map, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
+// the clouds of the call chunk by chunk, their rays in launches of kOccChunkRays
+int add_locked(loamx_ctx* ctx, VoxelMapBase* base, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
                const double* d_poses) {
+  loamx_occupancy_map* map = static_cast<loamx_occupancy_map*>(base);
   const bool combine = !(ctx->reg_flags & kRegFlagNoOccupancyCombine);
   untimed(ctx);
-  for (size_t c0 = 0; c0 < n_clouds; c0 += kOrgChunkClouds) {
-    const uint32_t nc = (uint32_t)(n_clouds - c0 < kOrgChunkClouds ? n_clouds - c0 : kOrgChunkClouds);
-    OrgOffsets offs;
-    for (uint32_t c = 0; c <= kOrgChunkClouds; c++) offs.off[c] = offsets[c0 + (c < nc ? c : nc)];
-    for (unsigned long long p0 = offs.off[0]; p0 < offs.off[nc]; p0 += kOccChunkRays) {
-      const uint32_t n = (uint32_t)(offs.off[nc] - p0 < kOccChunkRays ? offs.off[nc] - p0 : kOccChunkRays);
-      launch_occupancy_walk(d_points, f32, (uint32_t)stride, offs, nc, p0, n, d_poses ? d_poses + c0 * 7 : nullptr, map->rule, map->t, combine,
+  for (CloudChunks ch(offsets, n_clouds); ch.next();) {
+    for (unsigned long long p0 = ch.offs.off[0]; p0 < ch.offs.off[ch.nc]; p0 += kOccChunkRays) {
+      const uint32_t n = (uint32_t)(ch.offs.off[ch.nc] - p0 < kOccChunkRays ? ch.offs.off[ch.nc] - p0 : kOccChunkRays);
+      launch_occupancy_walk(d_points, f32, (uint32_t)stride, ch.offs, ch.nc, p0, n, d_poses ? d_poses + ch.c0 * 7 : nullptr, map->rule, map->t, combine,
                             ctx->stream);
       CHECK_LAUNCH(ctx, "occupancy walk kernel");
     }
@@ -77,39 +34,10 @@ int add_locked(loamx_ctx* ctx, loamx_occupancy_map* map, const void* d_points, b
   return LOAMX_OK;
 }
 
-int add_dev(loamx_ctx* ctx, loamx_occupancy_map* map, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
-            const double* d_poses) {
-  API_ENTER(ctx);
-  size_t total = 0;
-  int rc = add_check(ctx, map, d_points, stride, offsets, n_clouds, &total);
-  if (rc != LOAMX_OK || total == 0) return rc;
-  return add_locked(ctx, map, d_points, f32, stride, offsets, n_clouds, d_poses);
-}
-
-int add_host(loamx_ctx* ctx, loamx_occupancy_map* map, const void* points, bool f32, size_t stride, size_t n, const double* pose) {
-  API_ENTER(ctx);
-  const size_t offsets[2] = {0, n};
-  size_t total = 0;
-  int rc = add_check(ctx, map, points, stride, offsets, 1, &total);
-  if (rc != LOAMX_OK || total == 0) return rc;
-  if (n > (~(size_t)0) / (stride * sizeof(double))) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "the cloud does not fit the address space");
-  const size_t in_bytes = n * stride * (f32 ? sizeof(float) : sizeof(double));
-  untimed(ctx);
-  ENSURE(ctx, WS_OCC_IN, in_bytes);
-  ENSURE(ctx, WS_OCC_POSE, 7 * sizeof(double));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_OCC_IN].p, points, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (pose) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[WS_OCC_POSE].p, pose, 7 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  rc = add_locked(ctx, map, ctx->ws[WS_OCC_IN].p, f32, stride, offsets, 1, pose ? wsp<double>(ctx, WS_OCC_POSE) : nullptr);
-  if (rc != LOAMX_OK) {
-    (void)hipStreamSynchronize(ctx->stream);  // (the upload must not outlive the caller's array)
-    return rc;
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return LOAMX_OK;
-}
+const VoxelMapKind kKind = {"occupancy map", "an occupancy map", "rays", kOccMaxOffered, WS_OCC_IN, WS_OCC_POSE, add_locked};
 
 int query_check(loamx_ctx* ctx, const loamx_occupancy_map* map, const void* points, size_t stride, size_t n) {
-  int rc = map_check(ctx, map);
+  int rc = voxel_map_check(ctx, map, kKind);
   if (rc != LOAMX_OK) return rc;
   if (stride < 3) return fail(ctx, LOAMX_ERR_BAD_PARAM, "point_stride must be >= 3");
   if (stride > 0xFFFFFFFFull) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "point_stride does not fit 32 bits");
@@ -120,7 +48,7 @@ int query_check(loamx_ctx* ctx, const loamx_occupancy_map* map, const void* poin
 
 // *n: the voxels of the box (with_levels) or the columns of the slice
 int box_check(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t* vmin, const uint32_t* dims, bool with_levels, unsigned long long* n) {
-  int rc = map_check(ctx, map);
+  int rc = voxel_map_check(ctx, map, kKind);
   if (rc != LOAMX_OK) return rc;
   if (!vmin || !dims) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
   const unsigned long long plane = (unsigned long long)dims[0] * dims[1];
@@ -188,8 +116,7 @@ int loamx_occupancy_create(loamx_ctx* ctx, const loamx_occupancy_params* params,
   map->rule.min_r2 = params->min_range * params->min_range, map->rule.max_r2 = params->max_range * params->max_range;
   map->rule.max_range = params->max_range, map->rule.end_margin = params->end_margin, map->rule.clip_long = params->clip_long ? 1u : 0u;
   map->state_rule.min_hits = params->min_hits, map->state_rule.min_passes = params->min_passes, map->state_rule.occ_ratio = params->occ_ratio;
-  uint32_t log2_cap = 4;  // (voxel_hash takes 4 .. 32 bits)
-  while (((size_t)1 << log2_cap) < 2 * max_voxels) log2_cap++;
+  const uint32_t log2_cap = voxel_table_log2(2 * max_voxels);
   const size_t cap = (size_t)1 << log2_cap;
   const size_t o_keys = 0, o_counts = o_keys + align256(cap * sizeof(unsigned long long));
   const size_t o_words = o_counts + align256(cap * sizeof(unsigned long long));
@@ -203,7 +130,7 @@ int loamx_occupancy_create(loamx_ctx* ctx, const loamx_occupancy_params* params,
   map->ones_bytes = o_counts, map->zeros_bytes = bytes - o_counts;
   map->t.keys = reinterpret_cast<unsigned long long*>(b + o_keys), map->t.counts = reinterpret_cast<unsigned long long*>(b + o_counts);
   map->t.words = reinterpret_cast<unsigned long long*>(b + o_words), map->t.log2_cap = log2_cap;
-  int rc = clear_locked(ctx, map);
+  int rc = voxel_map_clear(ctx, map);
   if (rc != LOAMX_OK) {
     (void)hipFree(map->block);
     delete map;
@@ -215,39 +142,31 @@ int loamx_occupancy_create(loamx_ctx* ctx, const loamx_occupancy_params* params,
 
 void loamx_occupancy_destroy(loamx_ctx* ctx, loamx_occupancy_map* map) {
   if (!map) return;
-  if (ctx) {
-    std::lock_guard<std::mutex> guard(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);  // (kernels still working on the map)
-    if (map->block) (void)hipFree(map->block);
-    delete map;
-    return;
-  }
-  if (map->block) (void)hipFree(map->block);
+  voxel_map_destroy(ctx, map);
   delete map;
 }
 
 int loamx_occupancy_clear(loamx_ctx* ctx, loamx_occupancy_map* map) {
   API_ENTER(ctx);
-  int rc = map_check(ctx, map);
+  int rc = voxel_map_check(ctx, map, kKind);
   if (rc != LOAMX_OK) return rc;
-  return clear_locked(ctx, map);
+  return voxel_map_clear(ctx, map);
 }
 
 int loamx_occupancy_add_clouds_dev(loamx_ctx* ctx, loamx_occupancy_map* map, const double* d_points, size_t point_stride, const size_t* cloud_offsets,
                                    size_t n_clouds, const double* d_poses) {
-  return add_dev(ctx, map, d_points, false, point_stride, cloud_offsets, n_clouds, d_poses);
+  return voxel_map_add_dev(ctx, map, kKind, d_points, false, point_stride, cloud_offsets, n_clouds, d_poses);
 }
 int loamx_occupancy_add_clouds_dev_f32(loamx_ctx* ctx, loamx_occupancy_map* map, const float* d_points, size_t point_stride, const size_t* cloud_offsets,
                                        size_t n_clouds, const double* d_poses) {
-  return add_dev(ctx, map, d_points, true, point_stride, cloud_offsets, n_clouds, d_poses);
+  return voxel_map_add_dev(ctx, map, kKind, d_points, true, point_stride, cloud_offsets, n_clouds, d_poses);
 }
 int loamx_occupancy_add_cloud(loamx_ctx* ctx, loamx_occupancy_map* map, const double* points, size_t point_stride, size_t n_points, const double pose[7]) {
-  return add_host(ctx, map, points, false, point_stride, n_points, pose);
+  return voxel_map_add_host(ctx, map, kKind, points, false, point_stride, n_points, pose);
 }
 int loamx_occupancy_add_cloud_f32(loamx_ctx* ctx, loamx_occupancy_map* map, const float* points, size_t point_stride, size_t n_points,
                                   const double pose[7]) {
-  return add_host(ctx, map, points, true, point_stride, n_points, pose);
+  return voxel_map_add_host(ctx, map, kKind, points, true, point_stride, n_points, pose);
 }
 
 int loamx_occupancy_query_dev(loamx_ctx* ctx, const loamx_occupancy_map* map, const double* d_points, size_t point_stride, size_t n,
@@ -332,7 +251,7 @@ int loamx_occupancy_slice(loamx_ctx* ctx, const loamx_occupancy_map* map, const 
 
 int loamx_occupancy_stats_read(loamx_ctx* ctx, const loamx_occupancy_map* map, loamx_occupancy_stats* out) {
   API_ENTER(ctx);
-  int rc = map_check(ctx, map);
+  int rc = voxel_map_check(ctx, map, kKind);
   if (rc != LOAMX_OK) return rc;
   if (!out) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
   unsigned long long words[kOccWords];
@@ -346,16 +265,7 @@ int loamx_occupancy_stats_read(loamx_ctx* ctx, const loamx_occupancy_map* map, l
 }
 
 int loamx_occupancy_claims_read(loamx_ctx* ctx, const loamx_occupancy_map* map, uint64_t* claims) {
-  API_ENTER(ctx);
-  int rc = map_check(ctx, map);
-  if (rc != LOAMX_OK) return rc;
-  if (!claims) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
-  unsigned long long word = 0;
-  untimed(ctx);
-  HIP_TRY(ctx, hipMemcpyAsync(&word, map->t.words + kOccWordClaims, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  *claims = word;
-  return LOAMX_OK;
+  return voxel_map_read_word(ctx, map, kKind, map ? map->t.words + kOccWordClaims : nullptr, claims);
 }
 
 }  // extern "C"

@@ -24,10 +24,9 @@ int organize_locked(loamx_ctx* ctx, const loamx_scan_layout* l, const void* d_po
   const bool nearest = l->keep == LOAMX_ORGANIZE_KEEP_NEAREST;
   // the workspace of the largest chunk, before anything is enqueued
   size_t most_clouds = 0, most_points = 0;
-  for (size_t c0 = 0; c0 < n_clouds; c0 += kOrgChunkClouds) {
-    const size_t nc = n_clouds - c0 < kOrgChunkClouds ? n_clouds - c0 : kOrgChunkClouds;
-    most_clouds = nc > most_clouds ? nc : most_clouds;
-    most_points = offsets[c0 + nc] - offsets[c0] > most_points ? offsets[c0 + nc] - offsets[c0] : most_points;
+  for (CloudChunks ch(offsets, n_clouds); ch.next();) {
+    most_clouds = ch.nc > most_clouds ? ch.nc : most_clouds;
+    most_points = ch.offs.off[ch.nc] - ch.offs.off[0] > most_points ? ch.offs.off[ch.nc] - ch.offs.off[0] : most_points;
   }
   ENSURE(ctx, WS_ORG_WINNER, most_clouds * HW * sizeof(uint32_t));
   ENSURE(ctx, WS_ORG_COUNTS, most_clouds * kOrgCounterWords * sizeof(uint32_t));
@@ -37,19 +36,14 @@ int organize_locked(loamx_ctx* ctx, const loamx_scan_layout* l, const void* d_po
   }
   untimed(ctx);
   const OrgTables L = layout_tables(l);
-  for (size_t c0 = 0; c0 < n_clouds; c0 += kOrgChunkClouds) {
-    const uint32_t nc = (uint32_t)(n_clouds - c0 < kOrgChunkClouds ? n_clouds - c0 : kOrgChunkClouds);
-    OrgOffsets offs;
-    unsigned long long largest = 0;
-    for (uint32_t c = 0; c <= kOrgChunkClouds; c++) offs.off[c] = offsets[c0 + (c < nc ? c : nc)];
-    for (uint32_t c = 0; c < nc; c++) largest = offs.off[c + 1] - offs.off[c] > largest ? offs.off[c + 1] - offs.off[c] : largest;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ws[WS_ORG_WINNER].p, 0xFF, nc * HW * sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ws[WS_ORG_COUNTS].p, 0, nc * kOrgCounterWords * sizeof(uint32_t), ctx->stream));
-    if (nearest) HIP_TRY(ctx, hipMemsetAsync(ctx->ws[WS_ORG_RANGE].p, 0xFF, nc * HW * sizeof(unsigned long long), ctx->stream));
-    launch_organize(d_points, f32, (uint32_t)stride, d_rings, offs, nc, largest, L, nearest, wsp<uint32_t>(ctx, WS_ORG_WINNER),
+  for (CloudChunks ch(offsets, n_clouds); ch.next();) {
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ws[WS_ORG_WINNER].p, 0xFF, ch.nc * HW * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ws[WS_ORG_COUNTS].p, 0, ch.nc * kOrgCounterWords * sizeof(uint32_t), ctx->stream));
+    if (nearest) HIP_TRY(ctx, hipMemsetAsync(ctx->ws[WS_ORG_RANGE].p, 0xFF, ch.nc * HW * sizeof(unsigned long long), ctx->stream));
+    launch_organize(d_points, f32, (uint32_t)stride, d_rings, ch.offs, ch.nc, ch.largest, L, nearest, wsp<uint32_t>(ctx, WS_ORG_WINNER),
                     wsp<unsigned long long>(ctx, WS_ORG_RANGE), wsp<uint32_t>(ctx, WS_ORG_CELL), wsp<uint32_t>(ctx, WS_ORG_COUNTS),
-                    static_cast<unsigned char*>(d_scans) + c0 * HW * 3 * scalar, d_src_idx ? d_src_idx + c0 * HW : nullptr,
-                    d_stats ? d_stats + c0 * 4 : nullptr, ctx->stream);
+                    static_cast<unsigned char*>(d_scans) + ch.c0 * HW * 3 * scalar, d_src_idx ? d_src_idx + ch.c0 * HW : nullptr,
+                    d_stats ? d_stats + ch.c0 * 4 : nullptr, ctx->stream);
     CHECK_LAUNCH(ctx, "organize kernels");
   }
   return LOAMX_OK;

@@ -93,15 +93,10 @@ int descriptors_locked(loamx_ctx* ctx, const loamx_place_db* db, const void* d_p
   const size_t most_clouds = n_clouds < kOrgChunkClouds ? n_clouds : kOrgChunkClouds;
   ENSURE(ctx, WS_PLACE_TABLE, most_clouds * RS * sizeof(uint32_t));
   untimed(ctx);
-  for (size_t c0 = 0; c0 < n_clouds; c0 += kOrgChunkClouds) {
-    const uint32_t nc = (uint32_t)(n_clouds - c0 < kOrgChunkClouds ? n_clouds - c0 : kOrgChunkClouds);
-    OrgOffsets offs;
-    unsigned long long largest = 0;
-    for (uint32_t c = 0; c <= kOrgChunkClouds; c++) offs.off[c] = offsets[c0 + (c < nc ? c : nc)];
-    for (uint32_t c = 0; c < nc; c++) largest = offs.off[c + 1] - offs.off[c] > largest ? offs.off[c + 1] - offs.off[c] : largest;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ws[WS_PLACE_TABLE].p, 0, nc * RS * sizeof(uint32_t), ctx->stream));
-    launch_place_descriptors(d_points, f32, (uint32_t)stride, offs, nc, largest, db->shape, db->d_dirs, wsp<uint32_t>(ctx, WS_PLACE_TABLE),
-                             d_desc + c0 * RS, ctx->stream);
+  for (CloudChunks ch(offsets, n_clouds); ch.next();) {
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ws[WS_PLACE_TABLE].p, 0, ch.nc * RS * sizeof(uint32_t), ctx->stream));
+    launch_place_descriptors(d_points, f32, (uint32_t)stride, ch.offs, ch.nc, ch.largest, db->shape, db->d_dirs, wsp<uint32_t>(ctx, WS_PLACE_TABLE),
+                             d_desc + ch.c0 * RS, ctx->stream);
     CHECK_LAUNCH(ctx, "place descriptor kernels");
   }
   return LOAMX_OK;

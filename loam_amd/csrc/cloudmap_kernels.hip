@@ -9,6 +9,7 @@
 #include "cloudmap_math.h"
 #include "loamx_internal.h"
 #include "map_compact.h"
+#include "voxel_table.h"
 
 namespace loamx {
 namespace {
@@ -16,21 +17,14 @@ namespace {
 constexpr int kCloudThreads = (int)kMapTile;  // one point per thread; the tiles of the compaction are the workgroups
 constexpr uint32_t kCloudCounted = 5;         // words a workgroup counts in LDS: kCloudUsed .. kCloudOutside, then the claims
 
-template <typename T>
-__device__ __forceinline__ Vec3 load_cloud_point(const T* __restrict__ pts, unsigned long long row, uint32_t stride) {
-  const T* p = pts + (size_t)row * stride;
-  return v3((double)p[0], (double)p[1], (double)p[2]);
-}
-
 __device__ __forceinline__ unsigned long long shfl_down_u64(unsigned long long v, uint32_t d) {
   const uint32_t lo = __shfl_down((uint32_t)v, d, 64), hi = __shfl_down((uint32_t)(v >> 32), d, 64);
   return (unsigned long long)hi << 32 | lo;
 }
 
 /* ---- accumulate ----------------------------------------------------------------------------------------------------
- * Thread i holds point p0 + i of the call's array. Its cloud: the workgroup's first point is placed by a bisection of the
- * offsets (uniform, at most 8 steps), a thread then walks on from there (a workgroup rarely meets a cloud boundary). Validity,
- * p' = pose_c.act(p) with the pose read from device memory, key and offsets as cloudmap_math.h has them.
+ * Thread i holds point p0 + i of the call's array; its cloud is cloud_of_row's (voxel_table.h). Validity, p' = pose_c.act(p)
+ * with the pose read from device memory, key and offsets as cloudmap_math.h has them.
  *
  * kCombine: neighbouring cells of a scan line mostly share a voxel, and one CAS chain plus five atomics per point would then
  * be contention on a few addresses. Lanes that hold the same key in adjacent lanes with a voxel form a run; a run's number is
@@ -42,9 +36,8 @@ __device__ __forceinline__ unsigned long long shfl_down_u64(unsigned long long v
  * it must carry zeros (they are forced below, also for a point whose voxel is out of range on one axis only). The sums are integers:
  * combined or not, the table ends up with the same bytes.
  *
- * The claim is the one of voxel_claim_kernel (map_kernels.hip): EVERY probe is a 64-bit atomicCAS(empty -> key) whose returned
- * value decides, and no key slot is read by a plain load in this launch. The probe gives up after `capacity` slots; the run's
- * points are then counted as overflow and touch nothing else. slot_out[i]: the slot a head claimed, kMapNoSlot for every
+ * The claim follows the rule of voxel_table.h (voxel_claim). When the probe gives up, the run's points are counted as overflow
+ * and touch nothing else. slot_out[i]: the slot a head claimed, kMapNoSlot for every
  * other thread. Counters: one atomic per workgroup and word that has something to add; the claims word counts the heads, that
  * is, the CAS chains begun (loamx_cloud_map_claims_read: what tools/bench_cloudmap.py prices the two forms with). */
 template <typename T, bool kCombine>
@@ -61,16 +54,8 @@ __global__ __launch_bounds__(kCloudThreads) void cloud_accumulate_kernel(const T
   uint64_t key = 0;
   uint32_t u[3] = {0u, 0u, 0u};
   if (in) {
-    const unsigned long long row_b = p0 + (unsigned long long)blockIdx.x * kCloudThreads;
-    uint32_t lo = 0, hi = n_clouds;  // largest c with off[c] <= row_b: the cloud that holds it (empty clouds share an offset)
-    while (hi - lo > 1u) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (offs.off[mid] <= row_b) lo = mid;
-      else hi = mid;
-    }
-    uint32_t c = lo;
-    while (c + 1u < n_clouds && row >= offs.off[c + 1u]) c++;
-    Vec3 p = load_cloud_point(pts, row, stride);
+    const uint32_t c = cloud_of_row(offs, n_clouds, p0 + (unsigned long long)blockIdx.x * kCloudThreads, row);
+    Vec3 p = load_point_strided(pts, row, stride);
     what = cloud_validity(p, rule.min_r2, rule.max_r2);
     if (what == kCloudUsed) {
       if (poses) {
@@ -91,9 +76,7 @@ __global__ __launch_bounds__(kCloudThreads) void cloud_accumulate_kernel(const T
   uint32_t cnt = ok ? 1u : 0u;
   bool head = ok;
   if (kCombine) {
-    const uint32_t key_lo = __shfl_up((uint32_t)key, 1, 64), key_hi = __shfl_up((uint32_t)(key >> 32), 1, 64);
-    const bool ok_before = lane != 0 && (m_ok >> (lane - 1u) & 1ull);
-    head = ok && !(ok_before && ((unsigned long long)key_hi << 32 | key_lo) == key);
+    head = run_head(ok, key, lane, m_ok);
     const unsigned long long m_head = __ballot(head);
     if (m_head != m_ok) {  // (uniform) some run has more than one lane
       const uint32_t run = (uint32_t)__popcll(m_head & (~0ull >> (63u - lane)));  // heads up to and including this lane
@@ -109,16 +92,8 @@ __global__ __launch_bounds__(kCloudThreads) void cloud_accumulate_kernel(const T
   uint32_t slot = kMapNoSlot;
   bool gave_up = false;
   if (head) {
-    const uint32_t mask = (1u << t.log2_cap) - 1u;
-    uint32_t s = voxel_hash(key, t.log2_cap);
-    for (uint32_t probe = 0; probe <= mask; probe++) {
-      const unsigned long long old = atomicCAS(t.keys + s, (unsigned long long)kVoxelEmpty, (unsigned long long)key);
-      if (old == kVoxelEmpty || old == key) {
-        slot = s;
-        break;
-      }
-      s = (s + 1u) & mask;
-    }
+    bool opened;
+    slot = voxel_claim(t.keys, t.log2_cap, key, opened);
     if (slot != kMapNoSlot) {
       atomicAdd(t.sums + (size_t)slot * 3, s0);
       atomicAdd(t.sums + (size_t)slot * 3 + 1, s1);

@@ -481,6 +481,9 @@ void launch_place_shift_stage(const PlaceEntries& E, const PlaceShape& P, const 
                               const PlaceCand* cands, uint32_t n_queries, uint32_t K, loamx_place_match* d_tmp, loamx_place_match* d_out,
                               hipStream_t s);
 
+// arrays carved out of one device block start on 256-byte boundaries (the pose graph's workspace, the maps' blocks and outputs)
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
 /* ---- pose graph (posegraph_kernels.hip; the rule: posegraph_math.h and loamx.h) ----------------------------------------------- */
 // byte offsets of a solve's arrays in its one workspace block (every array starts on a 256-byte boundary)
 struct PgoLayout {
@@ -516,6 +519,12 @@ struct VoxelTable {
   uint32_t* owner;
   uint32_t log2_cap;
 };
+// log2 of the slots of a table (this one, the cloud map's, the occupancy map's) with room for slots_min: voxel_hash takes 4 .. 32 bits
+inline uint32_t voxel_table_log2(size_t slots_min) {
+  uint32_t l = 4;
+  while (((size_t)1 << l) < slots_min) l++;
+  return l;
+}
 void launch_voxel_claim(const double* d_pts, uint32_t n, const double* pose, double leaf, const VoxelTable& t, uint32_t base, double* d_moved,
                         uint32_t* d_slot, uint32_t* d_flags, uint32_t bad_word, hipStream_t s);
 void launch_voxel_keep(const VoxelTable& t, const uint32_t* d_slot, uint32_t n, uint32_t base, uint8_t* d_keep, hipStream_t s);

@@ -4,6 +4,7 @@
 #include "loamx_internal.h"
 #include "map_compact.h"
 #include "map_math.h"
+#include "voxel_table.h"
 
 namespace loamx {
 namespace {
@@ -27,14 +28,10 @@ __device__ __forceinline__ void store_point(double* __restrict__ pts, uint32_t i
 }
 
 /* ---- claim ---------------------------------------------------------------------------------------------------------
- * One thread per point: p' = pose.act(p) (skipped for the identity), key of its voxel, then a linear probe from the
- * key's hash. EVERY probe is a 64-bit atomicCAS(empty -> key) on the key slot and the value it returns decides: empty
- * (the slot is now this key's), the key itself (another point of the voxel was first) or another key (next slot). No key
- * slot is read by a plain load in this launch: the L2s of the eight XCDs are not coherent with each other, atomics are
- * performed at the memory side. The winner of a voxel is the LOWEST point index (atomicMin on the slot's owner word), so
- * the outcome does not depend on which thread came first; which slot a key ends up in does, and nothing reads that.
- * The probe loop ends after `capacity` slots at the latest (never reached while the table is at most half full) and
- * raises flags[kMapFlagGaveUp]; a point without a voxel (non-finite, or out of range) raises flags[bad_word].
+ * One thread per point: p' = pose.act(p) (skipped for the identity), key of its voxel, then the claim of its slot under the
+ * rule of voxel_table.h (voxel_claim). The winner of a voxel is the LOWEST point index (atomicMin on the slot's owner word), so
+ * the outcome does not depend on which thread came first. A probe that gave up raises flags[kMapFlagGaveUp]; a point without a
+ * voxel (non-finite, or out of range) raises flags[bad_word].
  * moved / slot_out may be null (the points of the map itself, when a table is built or caught up). */
 __global__ __launch_bounds__(kMapThreads) void voxel_claim_kernel(const double* __restrict__ pts, uint32_t n, Pose7 pose, uint32_t identity, double leaf,
                                                                    unsigned long long* keys, uint32_t* owner, uint32_t log2_cap, uint32_t base,
@@ -48,16 +45,8 @@ __global__ __launch_bounds__(kMapThreads) void voxel_claim_kernel(const double* 
   uint32_t slot = kMapNoSlot;
   uint64_t key;
   if (voxel_key(p, leaf, key)) {
-    const uint32_t mask = (1u << log2_cap) - 1u;
-    uint32_t s = voxel_hash(key, log2_cap);
-    for (uint32_t probe = 0; probe <= mask; probe++) {
-      const unsigned long long old = atomicCAS(keys + s, (unsigned long long)kVoxelEmpty, (unsigned long long)key);
-      if (old == kVoxelEmpty || old == key) {
-        slot = s;
-        break;
-      }
-      s = (s + 1u) & mask;
-    }
+    bool opened;
+    slot = voxel_claim(keys, log2_cap, key, opened);
     if (slot != kMapNoSlot) atomicMin(owner + slot, base + i);
     else atomicOr(flags + kMapFlagGaveUp, 1u);
   } else {

@@ -4,6 +4,7 @@
 // on that ray alone: every schedule, every split over workgroups and every batch split leaves the same bytes. No launch waits for
 // another workgroup, and every loop has a bound that is known before it starts.
 #include "loamx_internal.h"
+#include "voxel_table.h"
 
 namespace loamx {
 namespace {
@@ -11,16 +12,9 @@ namespace {
 constexpr int kOccThreads = 256;
 constexpr uint32_t kOccCounted = 8;  // words a workgroup counts in LDS: kOccWordHit .. kOccWordClaims
 
-template <typename T>
-__device__ __forceinline__ Vec3 load_ray_point(const T* __restrict__ pts, unsigned long long row, uint32_t stride) {
-  const T* p = pts + (size_t)row * stride;
-  return v3((double)p[0], (double)p[1], (double)p[2]);
-}
-
 /* One visit per lane (or none): `unit` is added to the count word of `key`, 1 for a pass and 2^32 for a hit.
  *
- * The claim is cloud_accumulate_kernel's: EVERY probe is a 64-bit atomicCAS(empty -> key) whose returned value decides, no key
- * slot is read by a plain load in this launch, and ONE 64-bit atomicAdd follows. The probe gives up after `capacity` slots; the
+ * The claim follows the rule of voxel_table.h (voxel_claim), and ONE 64-bit atomicAdd follows. When the probe gives up, the
  * visits it stood for are counted as overflow and touch nothing else.
  *
  * kCombine: the lanes of a wavefront are neighbouring beams, and near the sensor their walks stand in the same voxel step after
@@ -37,9 +31,7 @@ __device__ __forceinline__ void occ_emit(bool on, uint64_t key, unsigned long lo
   bool head = on;
   uint32_t cnt = 1u;
   if (kCombine) {
-    const uint32_t key_lo = __shfl_up((uint32_t)key, 1, 64), key_hi = __shfl_up((uint32_t)(key >> 32), 1, 64);
-    const bool on_before = lane != 0u && (m_on >> (lane - 1u) & 1ull);
-    head = on && !(on_before && ((unsigned long long)key_hi << 32 | key_lo) == key);
+    head = run_head(on, key, lane, m_on);
     const unsigned long long m_head = __ballot(head);
     const unsigned long long above = lane == 63u ? 0ull : ~0ull << (lane + 1u);
     const unsigned long long stop = (m_head | ~m_on) & above;
@@ -48,28 +40,16 @@ __device__ __forceinline__ void occ_emit(bool on, uint64_t key, unsigned long lo
   n_claims += (uint32_t)__popcll(__ballot(head));
   bool won = false;
   if (head) {
-    const uint32_t mask = (uint32_t)((1ull << t.log2_cap) - 1ull);
-    uint32_t s = voxel_hash(key, t.log2_cap);
-    bool placed = false;
-    for (uint32_t probe = 0; probe <= mask; probe++) {
-      const unsigned long long old = atomicCAS(t.keys + s, (unsigned long long)kVoxelEmpty, (unsigned long long)key);
-      if (old == kVoxelEmpty || old == key) {
-        won = old == kVoxelEmpty;
-        atomicAdd(t.counts + s, unit * cnt);
-        placed = true;
-        break;
-      }
-      s = (s + 1u) & mask;
-    }
-    if (!placed) atomicAdd(t.words + kOccWordOverflow, (unsigned long long)cnt);
+    const uint32_t s = voxel_claim(t.keys, t.log2_cap, key, won);
+    if (s != kMapNoSlot) atomicAdd(t.counts + s, unit * cnt);
+    else atomicAdd(t.words + kOccWordOverflow, (unsigned long long)cnt);
   }
   n_won += (uint32_t)__popcll(__ballot(won));
 }
 
 /* ---- walk -------------------------------------------------------------------------------------------------------------------
- * Thread i holds ray p0 + i of the call's array; its cloud is found as cloud_accumulate_kernel finds it (a bisection for the
- * workgroup's first ray, a short walk on from there). Steps 1 to 4 of the rule up to the walk's first voxel are occ_ray's. The
- * hit goes through occ_emit first, then the wavefront loops while any lane has a voxel left to visit: a lane whose voxel is its
+ * Thread i holds ray p0 + i of the call's array; its cloud is cloud_of_row's (voxel_table.h). Steps 1 to 4 of the rule up to the
+ * walk's first voxel are occ_ray's. The hit goes through occ_emit first, then the wavefront loops while any lane has a voxel left to visit: a lane whose voxel is its
  * own hit voxel, or that has finished, takes no part in that step's runs. The length of every lane's walk is known before the loop
  * starts. Counters: ballots summed per wavefront in uniform registers, met in LDS, one atomic per workgroup and word that has
  * something to add. */
@@ -85,16 +65,8 @@ __global__ __launch_bounds__(kOccThreads) void occupancy_walk_kernel(const T* __
   r.kind = -1, r.has_hit = r.outside = r.walks = false, r.hit_key = 0;
   r.w = OccWalk{};  // (a lane without a walk still forms a key in the loop below; it takes no part, but it reads no indeterminate value)
   if (i < n) {
-    const unsigned long long row_b = p0 + (unsigned long long)blockIdx.x * kOccThreads;
-    uint32_t lo = 0, hi = n_clouds;  // largest c with off[c] <= row_b: the cloud that holds it (empty clouds share an offset)
-    while (hi - lo > 1u) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (offs.off[mid] <= row_b) lo = mid;
-      else hi = mid;
-    }
-    uint32_t c = lo;
-    while (c + 1u < n_clouds && row >= offs.off[c + 1u]) c++;
-    const Vec3 p = load_ray_point(pts, row, stride);
+    const uint32_t c = cloud_of_row(offs, n_clouds, p0 + (unsigned long long)blockIdx.x * kOccThreads, row);
+    const Vec3 p = load_point_strided(pts, row, stride);
     double P[7] = {0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
     if (poses) {
 #pragma unroll
@@ -129,17 +101,10 @@ __global__ __launch_bounds__(kOccThreads) void occupancy_walk_kernel(const T* __
 }
 
 /* ---- read-outs: plain loads, behind the walks on the same stream ------------------------------------------------------------ */
-// the count word of a voxel, 0 without a slot; at most `capacity` probes
+// the count word of a voxel, 0 without a slot
 __device__ __forceinline__ unsigned long long occ_lookup(const OccTable& t, uint64_t key) {
-  const uint32_t mask = (uint32_t)((1ull << t.log2_cap) - 1ull);
-  uint32_t s = voxel_hash(key, t.log2_cap);
-  for (uint32_t probe = 0; probe <= mask; probe++) {
-    const unsigned long long k = t.keys[s];
-    if (k == key) return t.counts[s];
-    if (k == kVoxelEmpty) return 0ull;
-    s = (s + 1u) & mask;
-  }
-  return 0ull;
+  const uint32_t s = voxel_find(t.keys, t.log2_cap, key);
+  return s != kMapNoSlot ? t.counts[s] : 0ull;
 }
 __device__ __forceinline__ void occ_write(unsigned long long word, const OccStateRule& sr, unsigned long long i, uint32_t* __restrict__ counts_out,
                                           uint8_t* __restrict__ state_out) {
@@ -155,7 +120,7 @@ __global__ __launch_bounds__(kOccThreads) void occupancy_query_kernel(OccTable t
   if (i >= n) return;
   uint64_t key = 0;
   uint32_t u[3];
-  const bool ok = cloud_cell(load_ray_point(pts, i, stride), leaf, key, u);
+  const bool ok = cloud_cell(load_point_strided(pts, i, stride), leaf, key, u);
   occ_write(ok ? occ_lookup(t, key) : 0ull, sr, i, counts_out, state_out);
 }
 

@@ -300,7 +300,6 @@ __global__ __launch_bounds__(kT) void pgo_edges_from_results_kernel(const loamx_
 }
 
 inline uint32_t chunks_of(size_t n) { return (uint32_t)((n + kPgoChunk - 1) / kPgoChunk); }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 

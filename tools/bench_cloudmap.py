@@ -88,7 +88,7 @@ out = dict(source_hash=B.source_hash(), scans=n, scan_shape=[H, W], points=point
            add_ms_median=dict(combined=round(med[0], 3), plain=round(med[1], 3)),
            add_ms=dict(combined=[round(t, 3) for t in times[0][2:]], plain=[round(t, 3) for t in times[1][2:]]),
            add_points_per_s=dict(combined=round(points / med[0] * 1e3), plain=round(points / med[1] * 1e3)),
-           emit_ms_median=round(statistics.median(t_emit[2:]), 3), emit_voxels=stats["voxels"],
+           emit_ms_median=round(statistics.median(t_emit[2:]), 3), emit_ms=[round(t, 3) for t in t_emit[2:]], emit_voxels=stats["voxels"],
            claims=dict(combined=claims[0], plain=claims[1]),
            claims_per_offered_point=dict(combined=round(claims[0] / max(points, 1), 4), plain=round(claims[1] / max(points, 1), 4)),
            points_per_claim=dict(combined=round(stats["points_used"] / max(claims[0], 1), 3), plain=round(stats["points_used"] / max(claims[1], 1), 3)),

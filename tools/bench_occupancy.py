@@ -112,8 +112,9 @@ out = dict(source_hash=B.source_hash(), scans=n, scan_shape=[H, W], rays=rays, l
                                           plain=round((stats["visits"] + stats["rays_hit"]) / max(claims[1], 1), 3)),
            visits_per_ray=round(stats["visits"] / max(rays, 1), 2), table_slots=cap, table_load=round(stats["voxels"] / cap, 4),
            box=dict(vmin=box_vmin.tolist(), dims=box_dims.tolist(), ms_median=round(statistics.median(t_box[2:]), 3),
+                    ms=[round(t, 3) for t in t_box[2:]],
                     occupied=int((states == M.OCCUPIED).sum()), free=int((states == M.FREE).sum()), unknown=int((states == M.UNKNOWN).sum())),
-           slice_ms_median=round(statistics.median(t_slice[2:]), 3),
+           slice_ms_median=round(statistics.median(t_slice[2:]), 3), slice_ms=[round(t, 3) for t in t_slice[2:]],
            cloud_map_add_ms_median=round(cloud_ms, 3), add_over_cloud_map_add=round(med[0] / cloud_ms, 2))
 assert claims[1] == stats["visits"] + stats["rays_hit"], "the plain form claims once per hit and per pass"
 print(json.dumps(out), flush=True)
