@@ -261,6 +261,7 @@ int loamx_ctx_last_assoc_coop_forms(loamx_ctx* ctx, int which_kind, uint32_t out
  *   segmentation:  NO_SEGMENT_TILES (every connected edge through the global union, no tile labelling in LDS: the same bytes, see "scan segmentation")
  *   map cleaning:  NO_VISIBILITY_RANGES (the votes kernel reads the scans' points, no first launch that writes every cell's squared range: the same bytes, see "map cleaning")
  *   occupancy map: NO_OCCUPANCY_COMBINE (one claim per visit instead of one per run of a wavefront: the same bytes, see "occupancy map")
+ *   surfel map:    NO_SURFEL_COMBINE (one claim per point instead of one per run of a wavefront: the same bytes, see "surfel map")
  * Unknown name: LOAMX_ERR_BAD_PARAM.
  *
  * Non-finite input. The reference is undefined on NaN / Inf coordinates (loam/include/loam/features-inl.h:38 sorts on
@@ -1287,6 +1288,99 @@ int loamx_occupancy_query(loamx_ctx* ctx, const loamx_occupancy_map* map, const 
 int loamx_occupancy_box(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3], uint32_t* counts_out,
                         uint8_t* state_out);
 int loamx_occupancy_slice(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3], uint8_t* grid_out);
+
+/* ---- surfel map (no reference counterpart; the per-voxel Gaussians of NDT, the surfels of a point-to-plane map). What the
+ * consumers of a map need beyond a centroid: per voxel the mean, the covariance, its eigenvalues and the normal, turned towards
+ * where the voxel was seen from. The inputs are the cloud map's; the sums are integers, so every schedule and every partial
+ * combine gives the same bytes, and a Python model is compared by equality (tests/surfel_common.py). The rule is executable in
+ * loam_amd/csrc/surfel_math.h; every product, quotient, sum and difference is rounded on its own, in the order written, and sqrt is
+ * the only libm call.
+ *
+ * Per point p of cloud c:
+ *   1 validity   the cloud map's (`invalid`, `range`).
+ *   2 transform  p' = pose_c.act(p), pose_c from DEVICE memory; no pose array: p' = p.
+ *   3 voxel      the cloud map's key and 32-bit offsets u at the map's leaf (|v| < 2^20, otherwise `outside`): at equal leaf a surfel
+ *                key IS a cloud-map key.
+ *   4 offsets    q[a] = u[a] >> 16: 16 bits, steps of leaf / 65536. A product q[a] q[b] < 2^32 and at most 2^32 - 2 points are
+ *                offered between two clears, so no 64-bit sum below can wrap (the width is derived, not tuned).
+ *                s[a] += q[a] (3 words, each < 2^48); S[ab] += q[a] q[b], ab = xx xy xz yy yz zz (6 words); count += 1;
+ *                first = min(first, g), g the running index exactly as the cloud map defines it.
+ *   5 view       o = the translation of pose_c (0 without poses); x[a] = ((o[a] - p'[a]) / leaf) 256.0, then x = -2^30 unless
+ *                x >= -2^30, x = 2^30 if x > 2^30 (FP64), w[a] = (int64) floor(x); W[a] += w[a]: three signed 64-bit words,
+ *                |W| < 2^62. The clamp keeps a non-unit quaternion or a far-away pose from wrapping a sum.
+ * The record of a voxel, surfel_finish(key, s, S, W, count, first, leaf), with dn = (double) count, h = leaf / 65536.0:
+ *   mean[a]  = ((double) v[a] + ((double) s[a] / dn) / 65536.0) leaf.
+ *   N[ab]    = count S[ab] - s[a] s[b], EXACT in 128-bit integers (each term < 2^96), to FP64 as
+ *              sign ((double) hi 18446744073709551616.0 + (double) lo) of the magnitude's two 64-bit halves.
+ *   cov[ab]  = (N[ab] / (dn dn)) (h h): the population covariance (S / n - mean^2 in FP64 would cancel for a thin wall far
+ *              from the voxel's corner, which is why the numerator is formed in integers).
+ *   eigen    the cyclic Jacobi of the registration's line fit: rotations (0,1), (0,2), (1,2) per sweep, at most 32 sweeps, stops when
+ *              the three off-diagonals are exactly 0. Eigenvalues ascending by a stable sort of three (ties keep column order),
+ *              not clamped at 0. normal = the column of the smallest.
+ *   facing   dot = n0 (double) W0 + n1 (double) W1 + n2 (double) W2, left to right. The normal is negated when dot < 0; when
+ *              dot == 0 it is negated if its component of largest magnitude is negative (the lowest axis on ties). A voxel of
+ *              one point has cov = 0 and gets what this gives (the x axis, turned): defined, not special-cased.
+ * Voxel order, storage, overflow and ownership are the cloud map's: the voxels are listed in order of first appearance (a list of
+ * slots appended to, never sorted); a table of 2^k >= 2 max_voxels slots (key, first, twelve 64-bit sums and count: 112 B each),
+ * the list and the scratch of one round of launches are allocated at create and never grown; `overflow` counts as there, and
+ * FROM THE FIRST OVERFLOW UNTIL THE NEXT CLEAR only "every call returns and the stats say so" is promised. A map belongs to the
+ * context it was created on. Context option NO_SURFEL_COMBINE: one claim per used point instead of one per run of a wavefront;
+ * the same bytes.
+ *
+ * NAMES. On this handle the plain name is the device form (asynchronous on the context's stream, no host wait) and the host
+ * forms carry _host. */
+typedef struct {
+  double mean[3];
+  double cov[6];    /* xx xy xz yy yz zz */
+  double eval[3];   /* ascending */
+  double normal[3]; /* unit, towards the sensor positions */
+  uint32_t count, first;
+} loamx_surfel; /* 128 bytes */
+typedef struct {
+  double leaf;      /* 0.5 */
+  double min_range; /* 0.5 */
+  double max_range; /* 120.0 */
+} loamx_surfel_map_params;
+typedef struct {
+  uint64_t voxels, points_offered, points_used, invalid, range, outside, overflow;
+} loamx_surfel_map_stats;
+typedef struct loamx_surfel_map loamx_surfel_map;
+void loamx_default_surfel_map_params(loamx_surfel_map_params* p);
+/* the refusals of loamx_cloud_map_create */
+int loamx_surfel_map_create(loamx_ctx* ctx, const loamx_surfel_map_params* params, size_t max_voxels, loamx_surfel_map** out);
+void loamx_surfel_map_destroy(loamx_ctx* ctx, loamx_surfel_map* map);
+/* an empty map again, running index 0. Asynchronous. */
+int loamx_surfel_map_clear(loamx_ctx* ctx, loamx_surfel_map* map);
+/* the arguments, conventions and refusals of loamx_cloud_map_add_clouds_dev (DEVICE points and poses, HOST cloud_offsets).
+ * Asynchronous; a refused call changes nothing. */
+int loamx_surfel_map_add_clouds(loamx_ctx* ctx, loamx_surfel_map* map, const double* d_points, size_t point_stride,
+                                const size_t* cloud_offsets, size_t n_clouds, const double* d_poses);
+int loamx_surfel_map_add_clouds_f32(loamx_ctx* ctx, loamx_surfel_map* map, const float* d_points, size_t point_stride,
+                                    const size_t* cloud_offsets, size_t n_clouds, const double* d_poses);
+/* The voxels with count >= min_points in list order, to DEVICE memory: the records (d_out, capacity), the means (d_xyz_out,
+ * capacity x 3) and the normals (d_normal_out, capacity x 3); each of the three may be NULL. *d_n_out is the number that qualify
+ * even beyond capacity; every entry below min(n, capacity) of each non-null output is written and nothing beyond. Asynchronous.
+ * LOAMX_ERR_BAD_PARAM: a null map or d_n_out. */
+int loamx_surfel_map_emit(loamx_ctx* ctx, const loamx_surfel_map* map, uint32_t min_points, loamx_surfel* d_out, double* d_xyz_out,
+                          double* d_normal_out, size_t capacity, uint32_t* d_n_out);
+/* Per device-resident point (double, map frame, point_stride scalars apart): the record of its voxel, the signed distance
+ * normal . (p - mean) evaluated left to right, and the voxel's count; each output may be NULL. A point without a voxel (not
+ * finite, |v| >= 2^20, no slot) or in a voxel with count < min_points: a record of zero bytes, distance 0.0, count 0. Asynchronous.
+ * LOAMX_ERR_BAD_PARAM: a null map, null points with n_points > 0, point_stride < 3; LOAMX_ERR_UNSUPPORTED: n_points > 2^31, a
+ * point_stride beyond 32 bits. */
+int loamx_surfel_map_query(loamx_ctx* ctx, const loamx_surfel_map* map, const double* d_points, size_t point_stride, size_t n_points,
+                           uint32_t min_points, loamx_surfel* d_out, double* d_distance_out, uint32_t* d_count_out);
+/* synchronise */
+int loamx_surfel_map_stats_read(loamx_ctx* ctx, const loamx_surfel_map* map, loamx_surfel_map_stats* out);
+/* the claims since the last clear: probes begun by the accumulate kernel, each followed by its fourteen atomics */
+int loamx_surfel_map_claims_read(loamx_ctx* ctx, const loamx_surfel_map* map, uint64_t* claims);
+/* host forms, synchronous: one cloud in host memory with a HOST pose (NULL = no transform); the records to a host array */
+int loamx_surfel_map_add_cloud_host(loamx_ctx* ctx, loamx_surfel_map* map, const double* points, size_t point_stride, size_t n_points,
+                                    const double pose[7]);
+int loamx_surfel_map_add_cloud_host_f32(loamx_ctx* ctx, loamx_surfel_map* map, const float* points, size_t point_stride, size_t n_points,
+                                        const double pose[7]);
+int loamx_surfel_map_emit_host(loamx_ctx* ctx, const loamx_surfel_map* map, uint32_t min_points, loamx_surfel* out, size_t capacity,
+                               size_t* n_out);
 
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are

@@ -231,6 +231,32 @@ class CloudMapParams:
 CLOUD_MAP_STATS_DTYPE = np.dtype([(n, np.uint64) for n in ("voxels", "points_offered", "points_used", "invalid", "range", "outside", "overflow")])
 
 
+class SurfelMapParamsStruct(C.Structure):
+    """loamx_surfel_map_params (include/loamx.h)"""
+    _fields_ = [("leaf", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double)]
+
+
+class SurfelMapParams:
+    """The rule of a surfel map (loamx_surfel_map_params): voxel edge, and the range band outside which a point is dropped.
+    Anything left out takes the C ABI's default."""
+
+    def __init__(self, leaf=None, min_range=None, max_range=None):
+        d = SurfelMapParamsStruct()
+        load().loamx_default_surfel_map_params(C.byref(d))
+        self.leaf = d.leaf if leaf is None else float(leaf)
+        self.min_range = d.min_range if min_range is None else float(min_range)
+        self.max_range = d.max_range if max_range is None else float(max_range)
+
+    def struct(self):
+        return SurfelMapParamsStruct(float(self.leaf), float(self.min_range), float(self.max_range))
+
+
+# loamx_surfel (128 bytes) and loamx_surfel_map_stats
+SURFEL_DTYPE = np.dtype([("mean", np.float64, 3), ("cov", np.float64, 6), ("eval", np.float64, 3), ("normal", np.float64, 3),
+                         ("count", np.uint32), ("first", np.uint32)])
+SURFEL_MAP_STATS_DTYPE = np.dtype([(n, np.uint64) for n in ("voxels", "points_offered", "points_used", "invalid", "range", "outside", "overflow")])
+
+
 class OccupancyParamsStruct(C.Structure):
     """loamx_occupancy_params (include/loamx.h)"""
     _fields_ = [("leaf", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double), ("end_margin", C.c_double),
@@ -440,6 +466,10 @@ EXPORTS = [
     "loamx_occupancy_add_clouds_dev", "loamx_occupancy_add_clouds_dev_f32", "loamx_occupancy_query_dev", "loamx_occupancy_box_dev",
     "loamx_occupancy_slice_dev", "loamx_occupancy_stats_read", "loamx_occupancy_claims_read", "loamx_occupancy_add_cloud",
     "loamx_occupancy_add_cloud_f32", "loamx_occupancy_query", "loamx_occupancy_box", "loamx_occupancy_slice",
+    "loamx_default_surfel_map_params", "loamx_surfel_map_create", "loamx_surfel_map_destroy", "loamx_surfel_map_clear",
+    "loamx_surfel_map_add_clouds", "loamx_surfel_map_add_clouds_f32", "loamx_surfel_map_emit", "loamx_surfel_map_query",
+    "loamx_surfel_map_stats_read", "loamx_surfel_map_claims_read", "loamx_surfel_map_add_cloud_host", "loamx_surfel_map_add_cloud_host_f32",
+    "loamx_surfel_map_emit_host",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -711,6 +741,21 @@ def load(build_if_missing=True):
     lib.loamx_occupancy_claims_read.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
     lib.loamx_occupancy_add_cloud.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.loamx_occupancy_add_cloud_f32.argtypes = lib.loamx_occupancy_add_cloud.argtypes
+    lib.loamx_default_surfel_map_params.argtypes = [C.POINTER(SurfelMapParamsStruct)]
+    lib.loamx_default_surfel_map_params.restype = None
+    lib.loamx_surfel_map_create.argtypes = [vp, C.POINTER(SurfelMapParamsStruct), C.c_size_t, C.POINTER(vp)]
+    lib.loamx_surfel_map_destroy.argtypes = [vp, vp]
+    lib.loamx_surfel_map_destroy.restype = None
+    lib.loamx_surfel_map_clear.argtypes = [vp, vp]
+    lib.loamx_surfel_map_add_clouds.argtypes = [vp, vp, vp, C.c_size_t, szp, C.c_size_t, vp]
+    lib.loamx_surfel_map_add_clouds_f32.argtypes = lib.loamx_surfel_map_add_clouds.argtypes
+    lib.loamx_surfel_map_emit.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, C.c_size_t, vp]
+    lib.loamx_surfel_map_query.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_uint32, vp, vp, vp]
+    lib.loamx_surfel_map_stats_read.argtypes = [vp, vp, vp]
+    lib.loamx_surfel_map_claims_read.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
+    lib.loamx_surfel_map_add_cloud_host.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
+    lib.loamx_surfel_map_add_cloud_host_f32.argtypes = lib.loamx_surfel_map_add_cloud_host.argtypes
+    lib.loamx_surfel_map_emit_host.argtypes = [vp, vp, C.c_uint32, vp, C.c_size_t, szp]
     lib.loamx_default_segment_params.argtypes = [C.POINTER(SegmentParamsStruct)]
     lib.loamx_default_segment_params.restype = None
     lib.loamx_segment_constants.argtypes = [C.POINTER(SegmentParamsStruct), dp]
@@ -1021,7 +1066,7 @@ class PlaceDb:
 
 
 class _VoxelMap:
-    """What CloudMap and OccupancyMap share: the handle, clear, the two forms of an add, claims and close. A subclass names the
+    """What CloudMap, OccupancyMap and SurfelMap share: the handle, clear, the two forms of an add, claims and close. A subclass names the
     prefix of its C entry points, its parameters class and itself (the error texts)."""
     _PREFIX = _PARAMS = _NAME = None
 
@@ -1198,6 +1243,74 @@ class OccupancyMap(_VoxelMap):
         """one OCCUPANCY_STATS_DTYPE record (loamx_occupancy_stats_read; synchronises)"""
         st = np.zeros(1, dtype=OCCUPANCY_STATS_DTYPE)
         self.ctx._check(self.ctx.lib.loamx_occupancy_stats_read(self.ctx.h, self._handle(), st.ctypes.data))
+        return st[0]
+
+
+class SurfelMap(_VoxelMap):
+    """A surfel map (loamx_surfel_map; include/loamx.h, "surfel map"): posed clouds accumulated on a voxel grid as integer first
+    and second moments and a view sum; per voxel the mean, the covariance, its eigenvalues and the normal turned towards the sensor,
+    the voxels in order of first appearance; on the context's device. close() frees it; the context must still be open."""
+    _PREFIX, _PARAMS, _NAME = "loamx_surfel_map_", SurfelMapParams, "surfel map"
+    # on this handle the C names without a suffix are the device forms
+    _C_NAMES = {"add_clouds_dev": "add_clouds", "add_clouds_dev_f32": "add_clouds_f32", "add_cloud": "add_cloud_host",
+                "add_cloud_f32": "add_cloud_host_f32"}
+
+    def _fn(self, name):
+        return getattr(self.ctx.lib, self._PREFIX + self._C_NAMES.get(name, name))
+
+    def emit_dev(self, capacity, d_n_out, min_points=1, d_out=0, d_xyz_out=0, d_normal_out=0):
+        """the voxels with count >= min_points in list order, at most `capacity`, to device addresses: SURFEL_DTYPE records, the
+        means and the normals (capacity x 3 doubles each), any of them 0 = not wanted; the number that qualify to d_n_out
+        (loamx_surfel_map_emit). Asynchronous."""
+        if int(capacity) < 0 or not 0 <= int(min_points) <= 0xFFFFFFFF:
+            raise ValueError("emit_dev: capacity is negative or min_points does not fit 32 bits")
+        self.ctx._check(self.ctx.lib.loamx_surfel_map_emit(self.ctx.h, self._handle(), int(min_points), d_out or None, d_xyz_out or None,
+                                                           d_normal_out or None, int(capacity), d_n_out or None))
+
+    def emit(self, min_points=1, capacity=None):
+        """(records (m,) SURFEL_DTYPE, n): m = min(n, capacity) voxels in list order, n the number that qualify; capacity None:
+        room for every voxel the map can hold (loamx_surfel_map_emit_host; synchronises)."""
+        capacity = self.max_voxels if capacity is None else int(capacity)
+        if capacity < 0 or not 0 <= int(min_points) <= 0xFFFFFFFF:
+            raise ValueError("emit: capacity is negative or min_points does not fit 32 bits")
+        room = min(capacity, self.max_voxels)
+        out = np.zeros(room, dtype=SURFEL_DTYPE)
+        n = C.c_size_t(0)
+        self.ctx._check(self.ctx.lib.loamx_surfel_map_emit_host(self.ctx.h, self._handle(), int(min_points), out.ctypes.data, room, C.byref(n)))
+        return out[:min(n.value, room)], n.value
+
+    def query_dev(self, d_points, point_stride, n, min_points=1, d_out=0, d_distance_out=0, d_count_out=0):
+        """per device-resident point (double): the record of its voxel, the signed distance to its plane and the voxel's count, to
+        device addresses, any of them 0 = not wanted (loamx_surfel_map_query). Asynchronous."""
+        if int(point_stride) < 0 or int(n) < 0 or not 0 <= int(min_points) <= 0xFFFFFFFF:
+            raise ValueError("query_dev: point_stride or n is negative, or min_points does not fit 32 bits")
+        self.ctx._check(self.ctx.lib.loamx_surfel_map_query(self.ctx.h, self._handle(), d_points or None, int(point_stride), int(n), int(min_points),
+                                                            d_out or None, d_distance_out or None, d_count_out or None))
+
+    def query(self, points, min_points=1):
+        """host points (n, k >= 3) -> (records (n,) SURFEL_DTYPE, distance (n,) float64, count (n,) uint32); synchronises"""
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] < 3:
+            raise ValueError(f"query: points must be (n, 3) or (n, k >= 3), not {pts.shape}")
+        n = len(pts)
+        rec, dist, cnt = np.zeros(n, dtype=SURFEL_DTYPE), np.zeros(n), np.zeros(n, dtype=np.uint32)
+        if n == 0:
+            return rec, dist, cnt
+        bufs = [self.ctx.alloc(pts.nbytes), self.ctx.alloc(rec.nbytes), self.ctx.alloc(dist.nbytes), self.ctx.alloc(cnt.nbytes)]
+        try:
+            bufs[0].upload(pts)
+            self.query_dev(bufs[0].ptr, pts.shape[1], n, min_points, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr)
+            self.ctx.synchronize()
+            rec, dist, cnt = bufs[1].download(SURFEL_DTYPE, n), bufs[2].download(np.float64, n), bufs[3].download(np.uint32, n)
+        finally:
+            for b in bufs:
+                b.free()
+        return rec, dist, cnt
+
+    def stats(self):
+        """one SURFEL_MAP_STATS_DTYPE record (loamx_surfel_map_stats_read; synchronises)"""
+        st = np.zeros(1, dtype=SURFEL_MAP_STATS_DTYPE)
+        self.ctx._check(self.ctx.lib.loamx_surfel_map_stats_read(self.ctx.h, self._handle(), st.ctypes.data))
         return st[0]
 
 
@@ -1880,6 +1993,9 @@ class Context:
     # ---- cloud map (include/loamx.h, "cloud map") ---------------------------------------------------------------
     def cloud_map(self, params=None, max_voxels=1 << 20):
         return CloudMap(self, params, max_voxels)
+
+    def surfel_map(self, params=None, max_voxels=1 << 20):
+        return SurfelMap(self, params, max_voxels)
 
     def occupancy_map(self, params=None, max_voxels=1 << 20):
         return OccupancyMap(self, params, max_voxels)

@@ -648,6 +648,33 @@ struct OccBox {
 void launch_occupancy_box(const OccTable& t, const OccStateRule& sr, const OccBox& box, uint32_t* d_counts_out, uint8_t* d_state_out, hipStream_t s);
 void launch_occupancy_slice(const OccTable& t, const OccStateRule& sr, const OccBox& box, uint8_t* d_grid_out, hipStream_t s);
 
+/* ---- surfel map (surfel_kernels.hip; the rule: surfel_math.h and loamx.h) ----------------------------------------------------------- */
+constexpr uint32_t kRegFlagNoSurfelCombine = 2097152u;  // (loamx_ctx::reg_flags) one claim per point, no run combining
+constexpr uint32_t kSurfelSlotWords = 12;               // 64-bit sums of a slot: s[3], S[6], W[3] (surfel_math.h: kSurfelMoments)
+// Open-addressed table as CloudTable, with the cloud map's counter and length words (kCloudWord*, kCloudLen*): keys and first
+// start as 0xFF bytes, everything else as zero bytes.
+struct SurfelTable {
+  unsigned long long* keys;   // [cap]
+  uint32_t* first;            // [cap] lowest running index of a point of the voxel
+  unsigned long long* mom;    // [cap][kSurfelSlotWords]
+  uint32_t* count;            // [cap]
+  uint32_t log2_cap;
+  uint32_t max_voxels;
+  uint32_t* list;             // [max_voxels] slots in order of first appearance
+  unsigned long long* words;  // [kCloudWords]
+  uint32_t* lens;             // [kCloudLens]
+};
+// the arguments of launch_cloud_accumulate / _list / _emit, on a SurfelTable
+void launch_surfel_accumulate(const void* d_points, bool f32, uint32_t stride, const OrgOffsets& offs, uint32_t n_clouds, unsigned long long p0,
+                              uint32_t n, uint32_t g0, const double* d_poses, const CloudRule& rule, const SurfelTable& t, bool combine, uint32_t* d_slot,
+                              hipStream_t s);
+void launch_surfel_list(const SurfelTable& t, const uint32_t* d_slot, uint32_t n, uint32_t g0, uint8_t* d_keep, uint32_t* d_tiles, hipStream_t s);
+void launch_surfel_emit(const SurfelTable& t, double leaf, uint32_t min_points, uint8_t* d_keep, uint32_t* d_tiles, loamx_surfel* d_out,
+                        double* d_xyz_out, double* d_normal_out, size_t capacity, uint32_t* d_n_out, hipStream_t s);
+// read-only, behind the adds on the same stream; each output may be nullptr
+void launch_surfel_query(const SurfelTable& t, double leaf, uint32_t min_points, const double* d_points, uint32_t stride, unsigned long long n,
+                         loamx_surfel* d_out, double* d_distance_out, uint32_t* d_count_out, hipStream_t s);
+
 /* ---- synthetic generator (synth_kernels.hip) --------------------------------------------------- */
 void launch_synth_pairs(uint64_t seed, uint64_t first_pair, size_t n_pairs, uint32_t H, uint32_t W, double sigma,
                         double* d_xyz, hipStream_t s);

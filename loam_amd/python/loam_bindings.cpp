@@ -138,6 +138,39 @@ void cloud_map_add(loam::CloudMap& map, const py::array_t<T, py::array::c_style>
   loam::gpu::check(ctx, c_cloud_map_add(ctx, map.handle(), points.data(), (size_t)points.shape(1), (size_t)points.shape(0),
                                         world_T_sensor ? pose : nullptr));
 }
+// SurfelMap: points and pose as for CloudMap
+inline int c_surfel_map_add(loamx_ctx* c, loamx_surfel_map* m, const double* p, size_t stride, size_t n, const double* pose) {
+  return loamx_surfel_map_add_cloud_host(c, m, p, stride, n, pose);
+}
+inline int c_surfel_map_add(loamx_ctx* c, loamx_surfel_map* m, const float* p, size_t stride, size_t n, const double* pose) {
+  return loamx_surfel_map_add_cloud_host_f32(c, m, p, stride, n, pose);
+}
+template <typename T>
+void surfel_map_add(loam::SurfelMap& map, const py::array_t<T, py::array::c_style>& points, const std::optional<loam::Pose3d>& world_T_sensor) {
+  if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
+  double pose[7];
+  if (world_T_sensor) world_T_sensor->toArray(pose);
+  loamx_ctx* ctx = loam::gpu::defaultContext();
+  py::gil_scoped_release release;
+  loam::gpu::check(ctx, c_surfel_map_add(ctx, map.handle(), points.data(), (size_t)points.shape(1), (size_t)points.shape(0),
+                                         world_T_sensor ? pose : nullptr));
+}
+// surfels as a dict of arrays: mean (n, 3), cov (n, 6), eval (n, 3), normal (n, 3), count (n,), first (n,)
+inline py::dict surfel_arrays(const std::vector<loam::Surfel>& s) {
+  const py::ssize_t n = (py::ssize_t)s.size();
+  Arr mean(std::vector<py::ssize_t>{n, 3}), cov(std::vector<py::ssize_t>{n, 6}), eval(std::vector<py::ssize_t>{n, 3}), normal(std::vector<py::ssize_t>{n, 3});
+  py::array_t<uint32_t> count(n), first(n);
+  for (py::ssize_t i = 0; i < n; i++) {
+    std::memcpy(mean.mutable_data() + 3 * i, s[i].mean, sizeof(s[i].mean));
+    std::memcpy(cov.mutable_data() + 6 * i, s[i].cov, sizeof(s[i].cov));
+    std::memcpy(eval.mutable_data() + 3 * i, s[i].eval, sizeof(s[i].eval));
+    std::memcpy(normal.mutable_data() + 3 * i, s[i].normal, sizeof(s[i].normal));
+    count.mutable_data()[i] = s[i].count, first.mutable_data()[i] = s[i].first;
+  }
+  py::dict d;
+  d["mean"] = mean, d["cov"] = cov, d["eval"] = eval, d["normal"] = normal, d["count"] = count, d["first"] = first;
+  return d;
+}
 // OccupancyMap: points and pose as for CloudMap
 inline int c_occupancy_add(loamx_ctx* c, loamx_occupancy_map* m, const double* p, size_t stride, size_t n, const double* pose) {
   return loamx_occupancy_add_cloud(c, m, p, stride, n, pose);
@@ -728,6 +761,44 @@ PYBIND11_MODULE(loam_python, m) {
           py::arg("min_points") = 1)
       .def("stats", [](const loam::CloudMap& map) {
         const loam::CloudMapStats s = map.stats();
+        py::dict d;
+        d["voxels"] = s.voxels, d["points_offered"] = s.points_offered, d["points_used"] = s.points_used, d["invalid"] = s.invalid;
+        d["range"] = s.range, d["outside"] = s.outside, d["overflow"] = s.overflow;
+        return d;
+      });
+  // surfel map (include/loamx.h: "surfel map"): an extension like CloudMap
+  py::class_<loam::SurfelMapParams>(m, "SurfelMapParams")
+      .def(py::init<>())
+      .def_readwrite("leaf", &loam::SurfelMapParams::leaf)
+      .def_readwrite("min_range", &loam::SurfelMapParams::min_range)
+      .def_readwrite("max_range", &loam::SurfelMapParams::max_range);
+  py::class_<loam::SurfelMap>(m, "SurfelMap")
+      .def(py::init<const loam::SurfelMapParams&, size_t>(), py::arg("params") = loam::SurfelMapParams(), py::arg("max_voxels") = (size_t)1 << 20)
+      .def_property_readonly("params", &loam::SurfelMap::params)
+      .def_property_readonly("max_voxels", &loam::SurfelMap::maxVoxels)
+      .def("add", &surfel_map_add<float>, py::arg("points"), py::arg("world_T_sensor") = py::none())
+      .def("add", &surfel_map_add<double>, py::arg("points"), py::arg("world_T_sensor") = py::none())
+      .def("clear", &loam::SurfelMap::clear)
+      .def(
+          "surfels", [](const loam::SurfelMap& map, uint32_t min_points) { return surfel_arrays(map.surfels(min_points)); }, py::arg("min_points") = 1)
+      .def(
+          "query",
+          [](const loam::SurfelMap& map, const Arr& points, uint32_t min_points) {
+            if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
+            const size_t n = (size_t)points.shape(0), stride = (size_t)points.shape(1);
+            std::vector<double> xyz(3 * n);
+            for (size_t i = 0; i < n; i++)
+              for (size_t a = 0; a < 3; a++) xyz[3 * i + a] = points.data()[i * stride + a];
+            const loam::SurfelQuery q = map.query(xyz, min_points);
+            py::dict d = surfel_arrays(q.surfels);
+            Arr dist((py::ssize_t)n);
+            if (n) std::memcpy(dist.mutable_data(), q.distances.data(), n * sizeof(double));
+            d["distance"] = dist;
+            return d;
+          },
+          py::arg("points"), py::arg("min_points") = 1)
+      .def("stats", [](const loam::SurfelMap& map) {
+        const loam::SurfelMapStats s = map.stats();
         py::dict d;
         d["voxels"] = s.voxels, d["points_offered"] = s.points_offered, d["points_used"] = s.points_used, d["invalid"] = s.invalid;
         d["range"] = s.range, d["outside"] = s.outside, d["overflow"] = s.overflow;
