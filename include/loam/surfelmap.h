@@ -5,6 +5,9 @@
  * covariance, eigenvalues ascending, and the unit normal turned towards where the voxel was seen from; query() looks up the
  * surfel of a point and its signed distance to the surfel's plane. The sums are integers, so the map does not depend on how the
  * device schedules its threads. The rule is written out in loamx.h ("surfel map").
+ *
+ * localize() places a cloud in the map: point-to-plane Gauss-Newton against the voxels' fitted planes, solved on the device
+ * (loamx.h, "surfel localisation").
  */
 #pragma once
 #include <cstdint>
@@ -14,6 +17,7 @@
 
 #include "common.h"
 #include "geometry.h"
+#include "registration.h"
 
 namespace loam {
 
@@ -40,6 +44,32 @@ struct SurfelQuery {
   std::vector<double> distances;
   std::vector<uint32_t> counts;
   size_t size() const { return counts.size(); }
+};
+
+/// loamx_localize_params; the defaults are loamx_default_localize_params'
+struct LocalizeParams {
+  uint32_t neighborhood = 7;      ///< 7: the home voxel and its six face neighbours; 1: the home voxel only
+  uint32_t min_points = 5;        ///< a voxel with fewer points offers no plane
+  double planarity = 0.1;         ///< a plane needs eval[0] <= planarity eval[1]
+  double max_distance = 0.0;      ///< gate on the point-to-plane distance; 0: the map's leaf
+  double huber_delta = 0.1;       ///< 0: no Huber
+  uint32_t max_iterations = 10;
+  uint32_t min_rows = 100;
+  double rotation_convergence_thresh = 1e-3;
+  double position_convergence_thresh = 1e-2;
+  double min_eigenvalue_per_row = 1e-3;  ///< a direction is solved for where its eigenvalue exceeds this times the rows
+};
+
+/// loamx_localize_result, field for field (128 bytes); termination: LOAMX_LOCALIZE_*
+using LocalizeResult = loamx_localize_result;
+static_assert(sizeof(LocalizeResult) == 128, "loamx_localize_result is 128 bytes");
+
+/// What SurfelMap::localize returns: the pose, the record of the solve and the information matrix at the pose
+struct Localization {
+  Pose3d map_T_cloud;
+  LocalizeResult result;
+  RegistrationInformation information;
+  bool converged() const { return result.termination == LOAMX_LOCALIZE_CONVERGED; }
 };
 
 /// The map (loamx_surfel_map): table, voxel list and counters on the device. Cheap to copy (shared handle).
@@ -114,7 +144,48 @@ class SurfelMap {
     out.range = s.range, out.outside = s.outside, out.overflow = s.overflow;
     return out;
   }
+  /// Places one cloud (sensor frame) in the map, starting from `init` = map_T_cloud. The map is not changed. The localiser behind
+  /// it is kept between calls and made anew when a larger cloud arrives.
+  template <template <typename> class Accessor = FieldAccessor, typename PointType, typename Alloc>
+  Localization localize(const std::vector<PointType, Alloc>& points, const Pose3d& init, const LocalizeParams& params = LocalizeParams()) {
+    loamx_ctx* ctx = gpu::defaultContext();
+    loamx_localize_params p;
+    loamx_default_localize_params(&p);
+    p.neighborhood = params.neighborhood, p.min_points = params.min_points, p.planarity = params.planarity;
+    p.max_distance = params.max_distance, p.huber_delta = params.huber_delta, p.max_iterations = params.max_iterations;
+    p.min_rows = params.min_rows, p.rotation_convergence_thresh = params.rotation_convergence_thresh;
+    p.position_convergence_thresh = params.position_convergence_thresh, p.min_eigenvalue_per_row = params.min_eigenvalue_per_row;
+    double pose[7];
+    init.toArray(pose);
+    loamx_surfel_localizer* loc = localizer(points.size());
+    Localization out;
+    loamx_reg_information info;
+    if constexpr (gpu::float_scan_v<Accessor, PointType>) {
+      const std::vector<float> xyz = gpu::packFloat(points);
+      gpu::check(ctx, loamx_surfel_localizer_run_host_f32(ctx, loc, xyz.data(), 3, points.size(), pose, &p, &out.result, &info));
+    } else {
+      const std::vector<double> xyz = gpu::pack<Accessor>(points);
+      gpu::check(ctx, loamx_surfel_localizer_run_host(ctx, loc, xyz.data(), 3, points.size(), pose, &p, &out.result, &info));
+    }
+    out.map_T_cloud = Pose3d::fromArray(out.result.pose);
+    out.information = gpu::fromC(info);
+    return out;
+  }
   loamx_surfel_map* handle() const { return handle_.get(); }
+  /// the localiser for clouds of up to n_points points (kept; destroyed before the map it reads)
+  loamx_surfel_localizer* localizer(size_t n_points) {
+    if (!localizer_ || localizer_points_ < n_points) {
+      loamx_ctx* ctx = gpu::defaultContext();
+      localizer_.reset();
+      loamx_surfel_localizer* h = nullptr;
+      const size_t room = n_points > 4096 ? n_points : 4096;
+      gpu::check(ctx, loamx_surfel_localizer_create(ctx, handle_.get(), 1, room, &h));
+      std::shared_ptr<loamx_surfel_map> keep = handle_;  // (the map outlives its localiser)
+      localizer_ = std::shared_ptr<loamx_surfel_localizer>(h, [keep](loamx_surfel_localizer* l) { loamx_surfel_localizer_destroy(gpu::defaultContext(), l); });
+      localizer_points_ = room;
+    }
+    return localizer_.get();
+  }
 
  private:
   template <template <typename> class Accessor, typename PointType, typename Alloc>
@@ -132,6 +203,8 @@ class SurfelMap {
   SurfelMapParams params_;
   size_t max_voxels_;
   std::shared_ptr<loamx_surfel_map> handle_;
+  std::shared_ptr<loamx_surfel_localizer> localizer_;
+  size_t localizer_points_ = 0;
 };
 
 }  // namespace loam

@@ -262,6 +262,7 @@ int loamx_ctx_last_assoc_coop_forms(loamx_ctx* ctx, int which_kind, uint32_t out
  *   map cleaning:  NO_VISIBILITY_RANGES (the votes kernel reads the scans' points, no first launch that writes every cell's squared range: the same bytes, see "map cleaning")
  *   occupancy map: NO_OCCUPANCY_COMBINE (one claim per visit instead of one per run of a wavefront: the same bytes, see "occupancy map")
  *   surfel map:    NO_SURFEL_COMBINE (one claim per point instead of one per run of a wavefront: the same bytes, see "surfel map")
+ *   localisation:  NO_LOCALIZE_PLANES (no plane cache, every candidate voxel finished where it is looked at: the same bytes, see "surfel localisation")
  * Unknown name: LOAMX_ERR_BAD_PARAM.
  *
  * Non-finite input. The reference is undefined on NaN / Inf coordinates (loam/include/loam/features-inl.h:38 sorts on
@@ -1381,6 +1382,117 @@ int loamx_surfel_map_add_cloud_host_f32(loamx_ctx* ctx, loamx_surfel_map* map, c
                                         const double pose[7]);
 int loamx_surfel_map_emit_host(loamx_ctx* ctx, const loamx_surfel_map* map, uint32_t min_points, loamx_surfel* out, size_t capacity,
                                size_t* n_out);
+
+/* ---- surfel localisation (no reference counterpart; the point-to-plane scan-to-map step of SuMa, VoxelMap and the NDT family).
+ * Places clouds in a surfel map: association is a hash lookup of the voxel's fitted plane, so it takes any cloud (a full scan, an
+ * unordered cloud, the planar features alone) and needs no k-NN index. The whole solve stays on the device: a call enqueues
+ * 1 + 2 max_iterations + 2 launches per group of 256 clouds and reads nothing back, so add -> localise the next scan -> add it at
+ * the localised pose runs without a synchronise. The rule is executable in loam_amd/csrc/localize_math.h (host + device,
+ * every operation rounded on its own in the order written, sqrt the only libm call); a g++ build of it (tests/hostcheck_localize)
+ * runs the solve in the kernels' orders and is compared with the device by bytes.
+ *
+ * One evaluation of cloud c at the pose T = map_T_cloud (7 doubles, x y z w tx ty tz), per point p:
+ *   1 validity    the cloud map's, with the MAP's ranges; a point that fails is counted in n_unused.
+ *   2 move        v = T.act(p).
+ *   3 home voxel  the cloud map's cell of v at the map's leaf; a point without one (not finite, |v| >= 2^20) is counted in n_unused.
+ *   4 candidates  the home voxel; with neighborhood == 7 the six face neighbours follow in the order -x, +x, -y, +y, -z, +z. A
+ *                 neighbour whose coordinate leaves |v| < 2^20 is skipped. A candidate is USABLE iff it has a slot,
+ *                 count >= min_points, eval[1] > 0 and eval[0] <= planarity eval[1] (no division), eval the eigenvalues of
+ *                 surfel_finish.
+ *   5 choice      the usable candidate with the smallest |v - mean|^2 = dx dx + dy dy + dz dz, summed left to right; on a tie the
+ *                 earlier in the order above wins. No usable candidate: counted in n_no_surfel.
+ *   6 gate        s = normal . (v - mean), exactly the distance of the surfel map's query; |s| > max_distance: counted in n_gated
+ *                 (max_distance == 0 stands for the map's leaf).
+ *   7 row         r = |s|, g = copysign(1, s) normal, J = [v x g, g]: the plane row of loamx_reg_information in the same LEFT
+ *                 basis, with the subtraction done first (the s of the gate). A row with a non-finite entry is dropped and counted
+ *                 in n_unused. Huber at huber_delta: for r > huber_delta, J and r are scaled by sqrt(huber_delta / r) and the row
+ *                 is counted in n_huber; huber_delta == 0 switches it off.
+ *   8 sums        the upper triangle of J^T J (21), J^T r (6) and r^2 (1) of the scaled rows.
+ * Order of the sums, a function of the cloud alone: chunk k of a cloud is its points [4096 k, 4096 (k + 1)); thread t of 256 takes
+ * the points t, t + 256, ... of the chunk in that order; a wavefront's 64 values meet in a shuffle-down tree over 32 .. 1; the four
+ * wavefronts are added in order; the chunks are added in order. A cloud has the same bytes alone and inside any batch.
+ * The solve, per cloud: H = the mirrored triangle, eigenpairs as loamx_reg_information has them. Direction i is USED iff
+ * eigenvalue[i] > min_eigenvalue_per_row n_rows (bit i of used_mask); the step is d = - sum over the used i, ascending, of
+ * evec_i (evec_i . gradient) / eigenvalue_i (LOAM's degeneracy remapping: a floor-only map moves z, roll and pitch only); the
+ * retraction is on the left, T <- (normalise([omega / 2, 1]), t) o T with d = [omega, t]. Plain Gauss-Newton: every evaluation
+ * associates anew, there is no trust region. Per iteration, in this order:
+ *   0 a non-finite pose           -> LOAMX_LOCALIZE_NOT_FINITE, the pose stays (such a pose gives no row: it is looked at before 1)
+ *   1 n_rows < min_rows           -> LOAMX_LOCALIZE_TOO_FEW_ROWS, the pose stays
+ *   2 a non-finite d or new pose  -> LOAMX_LOCALIZE_NOT_FINITE, the pose stays
+ *   3 the step is applied, iterations += 1; last_rotation = |omega|, last_translation = |t|
+ *   4 |omega| < rotation_convergence_thresh && |t| < position_convergence_thresh -> LOAMX_LOCALIZE_CONVERGED
+ *   5 iterations == max_iterations -> LOAMX_LOCALIZE_MAX_ITERATIONS
+ * Then ONE more evaluation of every cloud at its returned pose fills final_cost, the counters, used_mask and the optional
+ * loamx_reg_information record (n_edge = 0, n_plane = n_rows, n_dropped = 0, the eigenpairs of that pass). initial_cost and
+ * n_rows_initial are those of the first evaluation. max_iterations == 0 returns the pose bit for bit (termination
+ * LOAMX_LOCALIZE_MAX_ITERATIONS) and the information at it. The costs are sums of scaled r^2, not halved.
+ * The localiser owns a plane cache of one 64-byte record per table slot (mean, normal, count, usable), rebuilt at the start of every
+ * call, so a map that was cleared or added to between two calls is fine. Context option NO_LOCALIZE_PLANES: no cache, every candidate
+ * is finished where it is looked at; the same bytes. PRECONDITION: a map that has not overflowed since its last clear. The cache is
+ * written for the LISTED voxels; past the first overflow the map holds claimed slots outside its list, whose cache records are
+ * whatever an earlier call left, so the two forms may then differ and, as for the map itself, only "every call returns" is promised.
+ * WHAT CONVERGED MEANS: the last step was small, not that the pose is right. This is plain Gauss-Newton without a trust region: where
+ * the map leaves a direction nearly open (a street seen along its axis, open ground) its eigenvalue can lie just above
+ * min_eigenvalue_per_row n_rows, the step along it is large and poorly founded, and a cloud can end metres off and still report
+ * LOAMX_LOCALIZE_CONVERGED. A caller gates on used_mask and on the eigenvalues of the information record, not on termination alone. The map is only read. Destroying the map before its localiser is the caller's
+ * error. On this handle the plain name is the device form and the host form carries _host. */
+enum {
+  LOAMX_LOCALIZE_CONVERGED = 0,
+  LOAMX_LOCALIZE_MAX_ITERATIONS = 1,
+  LOAMX_LOCALIZE_TOO_FEW_ROWS = 2,
+  LOAMX_LOCALIZE_NOT_FINITE = 3
+};
+typedef struct {
+  uint32_t neighborhood;              /* 7 (or 1: the home voxel only) */
+  uint32_t min_points;                /* 5 */
+  double planarity;                   /* 0.1 */
+  double max_distance;                /* 0: the map's leaf */
+  double huber_delta;                 /* 0.1; 0: no Huber */
+  uint32_t max_iterations;            /* 10, at most 1000 */
+  uint32_t min_rows;                  /* 100 */
+  double rotation_convergence_thresh; /* 1e-3 */
+  double position_convergence_thresh; /* 1e-2 */
+  double min_eigenvalue_per_row;      /* 1e-3 */
+} loamx_localize_params;              /* 64 bytes */
+typedef struct {
+  double pose[7];
+  double initial_cost, final_cost;
+  double last_rotation, last_translation; /* of the last applied step; 0 without one */
+  uint32_t iterations, termination;
+  uint32_t n_rows, n_huber, n_no_surfel, n_gated, n_unused; /* of the evaluation at the returned pose */
+  uint32_t used_mask;
+  uint32_t n_rows_initial;
+  uint32_t reserved;
+} loamx_localize_result; /* 128 bytes */
+typedef struct loamx_surfel_localizer loamx_surfel_localizer;
+void loamx_default_localize_params(loamx_localize_params* p);
+/* Everything a call needs is allocated here: the plane cache (64 B per table slot), the partial sums of max_points points and the
+ * state of max_clouds clouds. LOAMX_ERR_BAD_PARAM: a null argument, a map of another context, max_clouds == 0;
+ * LOAMX_ERR_UNSUPPORTED: max_clouds > 2^24, max_points > 2^32 - 2. */
+int loamx_surfel_localizer_create(loamx_ctx* ctx, const loamx_surfel_map* map, size_t max_clouds, size_t max_points,
+                                  loamx_surfel_localizer** out);
+void loamx_surfel_localizer_destroy(loamx_ctx* ctx, loamx_surfel_localizer* loc);
+/* n_clouds device-resident clouds back to back (cloud c = the points cloud_offsets[c] .. cloud_offsets[c + 1] - 1 of d_points,
+ * point_stride scalars apart; cloud_offsets in HOST memory), each from its pose d_poses_in[c] in DEVICE memory (the layout
+ * loamx_compose_trajectory_dev and loamx_pose_graph_optimize_dev leave). Writes d_poses_out (n_clouds x 7, may equal d_poses_in),
+ * d_results (n_clouds records) and, unless NULL, d_info (n_clouds records). Asynchronous on the context's stream, no host wait.
+ * A refused call changes nothing. LOAMX_ERR_BAD_PARAM: a null localiser, params, cloud_offsets, d_poses_in, d_poses_out or
+ * d_results, null points with points, a localiser of another context, point_stride < 3, neighborhood other than 1 or 7, a
+ * non-finite or negative parameter, decreasing offsets. LOAMX_ERR_UNSUPPORTED: n_clouds > max_clouds, more points than
+ * max_points, max_iterations > 1000, a point_stride beyond 32 bits. n_clouds == 0: LOAMX_OK. */
+int loamx_surfel_localizer_run(loamx_ctx* ctx, loamx_surfel_localizer* loc, const double* d_points, size_t point_stride,
+                               const size_t* cloud_offsets, size_t n_clouds, const double* d_poses_in, double* d_poses_out,
+                               loamx_localize_result* d_results, loamx_reg_information* d_info, const loamx_localize_params* params);
+int loamx_surfel_localizer_run_f32(loamx_ctx* ctx, loamx_surfel_localizer* loc, const float* d_points, size_t point_stride,
+                                   const size_t* cloud_offsets, size_t n_clouds, const double* d_poses_in, double* d_poses_out,
+                                   loamx_localize_result* d_results, loamx_reg_information* d_info, const loamx_localize_params* params);
+/* host form, synchronous: one cloud and one pose in host memory; the pose comes back in result->pose; info may be NULL */
+int loamx_surfel_localizer_run_host(loamx_ctx* ctx, loamx_surfel_localizer* loc, const double* points, size_t point_stride, size_t n_points,
+                                    const double pose[7], const loamx_localize_params* params, loamx_localize_result* result,
+                                    loamx_reg_information* info);
+int loamx_surfel_localizer_run_host_f32(loamx_ctx* ctx, loamx_surfel_localizer* loc, const float* points, size_t point_stride, size_t n_points,
+                                        const double pose[7], const loamx_localize_params* params, loamx_localize_result* result,
+                                        loamx_reg_information* info);
 
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are

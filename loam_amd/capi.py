@@ -227,6 +227,43 @@ class CloudMapParams:
         return CloudMapParamsStruct(float(self.leaf), float(self.min_range), float(self.max_range))
 
 
+class LocalizeParamsStruct(C.Structure):
+    """loamx_localize_params (include/loamx.h, "surfel localisation"): 64 bytes"""
+    _fields_ = [("neighborhood", C.c_uint32), ("min_points", C.c_uint32), ("planarity", C.c_double), ("max_distance", C.c_double),
+                ("huber_delta", C.c_double), ("max_iterations", C.c_uint32), ("min_rows", C.c_uint32),
+                ("rotation_convergence_thresh", C.c_double), ("position_convergence_thresh", C.c_double), ("min_eigenvalue_per_row", C.c_double)]
+
+
+class LocalizeParams:
+    """The parameters of a localisation call (loamx_localize_params). Anything left out takes the C ABI's default."""
+    _NAMES = tuple(f[0] for f in LocalizeParamsStruct._fields_)
+    _INTS = ("neighborhood", "min_points", "max_iterations", "min_rows")
+
+    def __init__(self, **kw):
+        d = LocalizeParamsStruct()
+        load().loamx_default_localize_params(C.byref(d))
+        unknown = set(kw) - set(self._NAMES)
+        if unknown:
+            raise ValueError(f"LocalizeParams: unknown parameter {sorted(unknown)}")
+        for n in self._NAMES:
+            setattr(self, n, getattr(d, n) if kw.get(n) is None else kw[n])
+
+    def struct(self):
+        for n in self._INTS:
+            if not 0 <= int(getattr(self, n)) <= 0xFFFFFFFF:
+                raise ValueError(f"LocalizeParams: {n} does not fit 32 bits")
+        return LocalizeParamsStruct(*[int(getattr(self, n)) if n in self._INTS else float(getattr(self, n)) for n in self._NAMES])
+
+
+# loamx_localize_result (128 bytes) and its termination codes
+LOCALIZE_RESULT_DTYPE = np.dtype([("pose", np.float64, 7), ("initial_cost", np.float64), ("final_cost", np.float64), ("last_rotation", np.float64),
+                                  ("last_translation", np.float64), ("iterations", np.uint32), ("termination", np.uint32), ("n_rows", np.uint32),
+                                  ("n_huber", np.uint32), ("n_no_surfel", np.uint32), ("n_gated", np.uint32), ("n_unused", np.uint32),
+                                  ("used_mask", np.uint32), ("n_rows_initial", np.uint32), ("reserved", np.uint32)])
+assert LOCALIZE_RESULT_DTYPE.itemsize == 128
+LOCALIZE_CONVERGED, LOCALIZE_MAX_ITERATIONS, LOCALIZE_TOO_FEW_ROWS, LOCALIZE_NOT_FINITE = 0, 1, 2, 3
+
+
 # loamx_cloud_map_stats
 CLOUD_MAP_STATS_DTYPE = np.dtype([(n, np.uint64) for n in ("voxels", "points_offered", "points_used", "invalid", "range", "outside", "overflow")])
 
@@ -470,6 +507,8 @@ EXPORTS = [
     "loamx_surfel_map_add_clouds", "loamx_surfel_map_add_clouds_f32", "loamx_surfel_map_emit", "loamx_surfel_map_query",
     "loamx_surfel_map_stats_read", "loamx_surfel_map_claims_read", "loamx_surfel_map_add_cloud_host", "loamx_surfel_map_add_cloud_host_f32",
     "loamx_surfel_map_emit_host",
+    "loamx_default_localize_params", "loamx_surfel_localizer_create", "loamx_surfel_localizer_destroy", "loamx_surfel_localizer_run",
+    "loamx_surfel_localizer_run_f32", "loamx_surfel_localizer_run_host", "loamx_surfel_localizer_run_host_f32",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -756,6 +795,15 @@ def load(build_if_missing=True):
     lib.loamx_surfel_map_add_cloud_host.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.loamx_surfel_map_add_cloud_host_f32.argtypes = lib.loamx_surfel_map_add_cloud_host.argtypes
     lib.loamx_surfel_map_emit_host.argtypes = [vp, vp, C.c_uint32, vp, C.c_size_t, szp]
+    lib.loamx_default_localize_params.argtypes = [C.POINTER(LocalizeParamsStruct)]
+    lib.loamx_default_localize_params.restype = None
+    lib.loamx_surfel_localizer_create.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    lib.loamx_surfel_localizer_destroy.argtypes = [vp, vp]
+    lib.loamx_surfel_localizer_destroy.restype = None
+    lib.loamx_surfel_localizer_run.argtypes = [vp, vp, vp, C.c_size_t, szp, C.c_size_t, vp, vp, vp, vp, C.POINTER(LocalizeParamsStruct)]
+    lib.loamx_surfel_localizer_run_f32.argtypes = lib.loamx_surfel_localizer_run.argtypes
+    lib.loamx_surfel_localizer_run_host.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(LocalizeParamsStruct), vp, vp]
+    lib.loamx_surfel_localizer_run_host_f32.argtypes = lib.loamx_surfel_localizer_run_host.argtypes
     lib.loamx_default_segment_params.argtypes = [C.POINTER(SegmentParamsStruct)]
     lib.loamx_default_segment_params.restype = None
     lib.loamx_segment_constants.argtypes = [C.POINTER(SegmentParamsStruct), dp]
@@ -1312,6 +1360,72 @@ class SurfelMap(_VoxelMap):
         st = np.zeros(1, dtype=SURFEL_MAP_STATS_DTYPE)
         self.ctx._check(self.ctx.lib.loamx_surfel_map_stats_read(self.ctx.h, self._handle(), st.ctypes.data))
         return st[0]
+
+    def localizer(self, max_clouds=1, max_points=1 << 20):
+        """a SurfelLocalizer on this map for calls of at most max_clouds clouds and max_points points (loamx_surfel_localizer_create)"""
+        return SurfelLocalizer(self, max_clouds, max_points)
+
+
+class SurfelLocalizer:
+    """Scan-to-map localisation on a surfel map (loamx_surfel_localizer; include/loamx.h, "surfel localisation"): point-to-plane
+    Gauss-Newton against the voxels' fitted planes, solved on the device. close() frees it, before its map is closed."""
+
+    def __init__(self, surfel_map, max_clouds, max_points):
+        max_clouds, max_points = int(max_clouds), int(max_points)
+        if max_clouds < 0 or max_points < 0:
+            raise ValueError("localizer: max_clouds or max_points is negative")
+        self.map, self.ctx, self.max_clouds, self.max_points = surfel_map, surfel_map.ctx, max_clouds, max_points
+        h = C.c_void_p()
+        self.ctx._check(self.ctx.lib.loamx_surfel_localizer_create(self.ctx.h, surfel_map._handle(), max_clouds, max_points, C.byref(h)))
+        self.h = h
+
+    def _handle(self):
+        if not getattr(self, "h", None):
+            raise ValueError("the localizer is closed")
+        return self.h
+
+    def run_dev(self, d_points, point_stride, cloud_offsets, d_poses_in, d_poses_out, d_results, d_info=0, params=None, f32=False):
+        """len(cloud_offsets) - 1 device-resident clouds from their device poses (n_clouds x 7 doubles); the poses, the
+        LOCALIZE_RESULT_DTYPE records and (d_info != 0) the INFORMATION_DTYPE records to device addresses; d_poses_out may be
+        d_poses_in (loamx_surfel_localizer_run[_f32]). Asynchronous."""
+        off = _offsets(cloud_offsets, "run_dev")
+        if int(point_stride) < 0:
+            raise ValueError("run_dev: point_stride is negative")
+        st = (params or LocalizeParams()).struct()
+        fn = self.ctx.lib.loamx_surfel_localizer_run_f32 if f32 else self.ctx.lib.loamx_surfel_localizer_run
+        self.ctx._check(fn(self.ctx.h, self._handle(), d_points or None, int(point_stride), off.ctypes.data_as(C.POINTER(C.c_size_t)), off.size - 1,
+                           d_poses_in or None, d_poses_out or None, d_results or None, d_info or None, C.byref(st)))
+
+    def run(self, points, pose, params=None, information=True):
+        """One cloud in host memory, (n, k >= 3) float64 / float32, from a host pose7 -> (pose (7,), one LOCALIZE_RESULT_DTYPE record,
+        one INFORMATION_DTYPE record or None) (loamx_surfel_localizer_run_host[_f32]; synchronises)."""
+        pts = np.asarray(points)
+        if pts.dtype != np.float32:
+            pts = np.asarray(pts, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] < 3:
+            raise ValueError(f"run: points must be (n, 3) or (n, k >= 3), not {pts.shape}")
+        pts = np.ascontiguousarray(pts)
+        p = np.ascontiguousarray(pose, dtype=np.float64)
+        if p.shape != (7,):
+            raise ValueError(f"run: a pose is 7 numbers (qx qy qz qw tx ty tz), not {p.shape}")
+        st = (params or LocalizeParams()).struct()
+        res, info = np.zeros(1, dtype=LOCALIZE_RESULT_DTYPE), np.zeros(1, dtype=INFORMATION_DTYPE)
+        fn = self.ctx.lib.loamx_surfel_localizer_run_host_f32 if pts.dtype == np.float32 else self.ctx.lib.loamx_surfel_localizer_run_host
+        self.ctx._check(fn(self.ctx.h, self._handle(), pts.ctypes.data, pts.shape[1], pts.shape[0], p.ctypes.data, C.byref(st), res.ctypes.data,
+                           info.ctypes.data if information else None))
+        return res[0]["pose"].copy(), res[0], (info[0] if information else None)
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.ctx.lib.loamx_surfel_localizer_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceBuffer:

@@ -38,7 +38,8 @@ const OptionName kOptionNames[] = {
     {"NO_SMALL_SETS", false, kRegFlagNoSmallSets}, {"FORCE_LATE_VERIFY", false, kRegFlagForceLate},
     {"NO_LIVE_DEAL", false, kRegFlagNoLiveDeal}, {"NO_CLOUDMAP_COMBINE", false, kRegFlagNoCloudmapCombine},
     {"NO_SEGMENT_TILES", false, kRegFlagNoSegmentTiles}, {"NO_VISIBILITY_RANGES", false, kRegFlagNoVisibilityRanges},
-    {"NO_OCCUPANCY_COMBINE", false, kRegFlagNoOccupancyCombine}, {"NO_SURFEL_COMBINE", false, kRegFlagNoSurfelCombine}};
+    {"NO_OCCUPANCY_COMBINE", false, kRegFlagNoOccupancyCombine}, {"NO_SURFEL_COMBINE", false, kRegFlagNoSurfelCombine},
+    {"NO_LOCALIZE_PLANES", false, kRegFlagNoLocalizePlanes}};
 
 }  // namespace
 

@@ -31,6 +31,7 @@ enum WsId {
   WS_VIS_RANGES, WS_VIS_CENSUS, WS_VIS_KEEP, WS_VIS_TILES, WS_VIS_IN, WS_VIS_SCANS, WS_VIS_POSES, WS_VIS_OUT,
   WS_OCC_IN, WS_OCC_POSE, WS_OCC_OUT,
   WS_SURFEL_IN, WS_SURFEL_POSE, WS_SURFEL_OUT,
+  WS_LOC_IN, WS_LOC_POSE, WS_LOC_OUT,
   WS_COUNT
 };
 // the buffers that exist once per feature kind: loamx_ctx::wsk[id][kEdge | kPlane]

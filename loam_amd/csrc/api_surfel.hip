@@ -1,17 +1,8 @@
 // api_surfel.hip — the surfel map (loamx.h, "surfel map"): the map handle with its one device block (table, voxel list, counters,
 // the scratch of a round of launches), the add, emit, query, clear and stats entry points and their host forms. On this handle
 // the plain names are the device forms.
-#include "api_voxelmap.h"
+#include "api_surfel.h"
 #include "surfel_math.h"
-
-struct loamx_surfel_map : loamx::VoxelMapBase {  // ones: keys + first; zeros: sums, count, counters and lengths
-  loamx_surfel_map_params params = {};
-  loamx::CloudRule rule = {};
-  loamx::SurfelTable t = {};
-  uint32_t* d_slot = nullptr;   // scratch of a round of an add: [kCloudChunkPoints]
-  uint8_t* d_keep = nullptr;    // [max(kCloudChunkPoints, max_voxels)] (add and emit)
-  uint32_t* d_tiles = nullptr;  // the compaction's tiles for as many
-};
 
 using namespace loamx;
 

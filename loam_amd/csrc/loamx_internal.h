@@ -675,6 +675,32 @@ void launch_surfel_emit(const SurfelTable& t, double leaf, uint32_t min_points, 
 void launch_surfel_query(const SurfelTable& t, double leaf, uint32_t min_points, const double* d_points, uint32_t stride, unsigned long long n,
                          loamx_surfel* d_out, double* d_distance_out, uint32_t* d_count_out, hipStream_t s);
 
+/* ---- surfel localisation (localize_kernels.hip; the rule: localize_math.h and loamx.h) ------------------------------------------- */
+constexpr uint32_t kRegFlagNoLocalizePlanes = 4194304u;  // (loamx_ctx::reg_flags) no plane cache: every candidate through surfel_of_slot
+struct LocPlane;   // localize_math.h
+struct LocRule;
+struct LocSolve;
+struct LocState;
+struct LocResult;
+// what localize_accumulate_kernel leaves per (cloud, chunk of the cloud's points): the sums of info_math.h and the counters
+struct LocPartial {
+  double s[28];
+  uint32_t c[8];
+};
+size_t localize_partials(size_t max_points);  // partials a launch of at most kOrgChunkClouds clouds and max_points points can write
+// the plane cache (cache may be nullptr: the plain form) and the state of the call's n_clouds clouds from d_poses_in
+void launch_localize_planes(const SurfelTable& t, double leaf, uint32_t min_points, double planarity, LocPlane* cache, const double* d_poses_in,
+                            uint32_t n_clouds, uint32_t max_iterations, LocState* state, hipStream_t s);
+// one evaluation of the clouds of `offs` (at most kOrgChunkClouds, `largest` the points of the largest) at the poses of `state`
+// (the state of offs' first cloud onwards); final_pass: clouds that have stopped are evaluated too
+void launch_localize_accumulate(const void* d_points, bool f32, uint32_t stride, const OrgOffsets& offs, uint32_t n_clouds, unsigned long long largest,
+                                const LocState* state, const LocRule& rule, const SurfelTable& t, const LocPlane* cache, bool final_pass,
+                                LocPartial* partials, hipStream_t s);
+// behind it: one iteration of the solve per cloud, or (final_pass) the poses, result records and information records (d_info may be
+// nullptr), each from offs' first cloud onwards
+void launch_localize_step(const OrgOffsets& offs, uint32_t n_clouds, LocState* state, const LocSolve& P, const LocPartial* partials, bool final_pass,
+                          double* d_poses_out, LocResult* d_results, loamx_reg_information* d_info, hipStream_t s);
+
 /* ---- synthetic generator (synth_kernels.hip) --------------------------------------------------- */
 void launch_synth_pairs(uint64_t seed, uint64_t first_pair, size_t n_pairs, uint32_t H, uint32_t W, double sigma,
                         double* d_xyz, hipStream_t s);

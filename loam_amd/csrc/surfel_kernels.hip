@@ -10,6 +10,7 @@
 #include "loamx_internal.h"
 #include "map_compact.h"
 #include "surfel_math.h"
+#include "surfel_slot.h"
 #include "voxel_table.h"
 
 namespace loamx {
@@ -162,18 +163,7 @@ __global__ void surfel_commit_kernel(SurfelTable t) {
 }
 
 /* ---- read-outs ---------------------------------------------------------------------------------------------------------------- */
-// the record of slot s (behind a kernel boundary from the last add: plain loads)
-__device__ __forceinline__ loamx_surfel surfel_of_slot(const SurfelTable& t, uint32_t s, uint32_t count, double leaf) {
-  const unsigned long long* w = t.mom + (size_t)s * kSurfelSlotWords;
-  uint64_t sum[3], S[6];
-  int64_t W[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) sum[a] = w[a], W[a] = (int64_t)w[9 + a];
-#pragma unroll
-  for (int a = 0; a < 6; a++) S[a] = w[3 + a];
-  return surfel_finish(t.keys[s], sum, S, W, count, t.first[s], leaf);
-}
-
+// (the record of a slot: surfel_of_slot of surfel_slot.h)
 // one thread per list entry up to the list's capacity (its length is known on the device only)
 __global__ __launch_bounds__(kSurfelThreads) void surfel_emit_flags_kernel(SurfelTable t, uint32_t min_points, uint8_t* __restrict__ keep) {
   const uint32_t j = blockIdx.x * kSurfelThreads + threadIdx.x;

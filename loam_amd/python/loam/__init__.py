@@ -9,3 +9,4 @@ from .loam_python import RegistrationInformation, registrationInformation  # noq
 from .loam_python import PoseGraph, PoseGraphParams, PoseGraphSummary  # noqa: F401  (extension: pose graph)
 from .loam_python import CloudMap, CloudMapParams  # noqa: F401  (extension: cloud map)
 from .loam_python import VisibilityParams, removeDynamicPoints, visibilityVotes  # noqa: F401  (extension: map cleaning)
+from .loam_python import LocalizeParams, LocalizeResult, SurfelMap, SurfelMapParams  # noqa: F401  (extension: surfel map and localisation)

@@ -155,6 +155,37 @@ void surfel_map_add(loam::SurfelMap& map, const py::array_t<T, py::array::c_styl
   loam::gpu::check(ctx, c_surfel_map_add(ctx, map.handle(), points.data(), (size_t)points.shape(1), (size_t)points.shape(0),
                                          world_T_sensor ? pose : nullptr));
 }
+// SurfelMap.localize: points as for add, from init = map_T_cloud -> (pose, result, information)
+inline int c_localize(loamx_ctx* c, loamx_surfel_localizer* l, const double* p, size_t stride, size_t n, const double* pose, const loamx_localize_params* lp,
+                      loamx_localize_result* res, loamx_reg_information* info) {
+  return loamx_surfel_localizer_run_host(c, l, p, stride, n, pose, lp, res, info);
+}
+inline int c_localize(loamx_ctx* c, loamx_surfel_localizer* l, const float* p, size_t stride, size_t n, const double* pose, const loamx_localize_params* lp,
+                      loamx_localize_result* res, loamx_reg_information* info) {
+  return loamx_surfel_localizer_run_host_f32(c, l, p, stride, n, pose, lp, res, info);
+}
+template <typename T>
+py::tuple surfel_map_localize(loam::SurfelMap& map, const py::array_t<T, py::array::c_style>& points, const loam::Pose3d& init,
+                              const loam::LocalizeParams& params) {
+  if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
+  loamx_localize_params p;
+  loamx_default_localize_params(&p);
+  p.neighborhood = params.neighborhood, p.min_points = params.min_points, p.planarity = params.planarity;
+  p.max_distance = params.max_distance, p.huber_delta = params.huber_delta, p.max_iterations = params.max_iterations;
+  p.min_rows = params.min_rows, p.rotation_convergence_thresh = params.rotation_convergence_thresh;
+  p.position_convergence_thresh = params.position_convergence_thresh, p.min_eigenvalue_per_row = params.min_eigenvalue_per_row;
+  double pose[7];
+  init.toArray(pose);
+  loamx_ctx* ctx = loam::gpu::defaultContext();
+  loamx_surfel_localizer* loc = map.localizer((size_t)points.shape(0));
+  loam::LocalizeResult res;
+  loamx_reg_information info;
+  {
+    py::gil_scoped_release release;
+    loam::gpu::check(ctx, c_localize(ctx, loc, points.data(), (size_t)points.shape(1), (size_t)points.shape(0), pose, &p, &res, &info));
+  }
+  return py::make_tuple(loam::Pose3d::fromArray(res.pose), res, loam::gpu::fromC(info));
+}
 // surfels as a dict of arrays: mean (n, 3), cov (n, 6), eval (n, 3), normal (n, 3), count (n,), first (n,)
 inline py::dict surfel_arrays(const std::vector<loam::Surfel>& s) {
   const py::ssize_t n = (py::ssize_t)s.size();
@@ -772,6 +803,34 @@ PYBIND11_MODULE(loam_python, m) {
       .def_readwrite("leaf", &loam::SurfelMapParams::leaf)
       .def_readwrite("min_range", &loam::SurfelMapParams::min_range)
       .def_readwrite("max_range", &loam::SurfelMapParams::max_range);
+  py::class_<loam::LocalizeParams>(m, "LocalizeParams")
+      .def(py::init<>())
+      .def_readwrite("neighborhood", &loam::LocalizeParams::neighborhood)
+      .def_readwrite("min_points", &loam::LocalizeParams::min_points)
+      .def_readwrite("planarity", &loam::LocalizeParams::planarity)
+      .def_readwrite("max_distance", &loam::LocalizeParams::max_distance)
+      .def_readwrite("huber_delta", &loam::LocalizeParams::huber_delta)
+      .def_readwrite("max_iterations", &loam::LocalizeParams::max_iterations)
+      .def_readwrite("min_rows", &loam::LocalizeParams::min_rows)
+      .def_readwrite("rotation_convergence_thresh", &loam::LocalizeParams::rotation_convergence_thresh)
+      .def_readwrite("position_convergence_thresh", &loam::LocalizeParams::position_convergence_thresh)
+      .def_readwrite("min_eigenvalue_per_row", &loam::LocalizeParams::min_eigenvalue_per_row);
+  py::class_<loam::LocalizeResult>(m, "LocalizeResult")
+      .def_property_readonly("pose", [](const loam::LocalizeResult& r) { return matrix_to_array(r.pose, 7, 1); })
+      .def_readonly("initial_cost", &loam::LocalizeResult::initial_cost)
+      .def_readonly("final_cost", &loam::LocalizeResult::final_cost)
+      .def_readonly("last_rotation", &loam::LocalizeResult::last_rotation)
+      .def_readonly("last_translation", &loam::LocalizeResult::last_translation)
+      .def_readonly("iterations", &loam::LocalizeResult::iterations)
+      .def_readonly("termination", &loam::LocalizeResult::termination)
+      .def_readonly("n_rows", &loam::LocalizeResult::n_rows)
+      .def_readonly("n_huber", &loam::LocalizeResult::n_huber)
+      .def_readonly("n_no_surfel", &loam::LocalizeResult::n_no_surfel)
+      .def_readonly("n_gated", &loam::LocalizeResult::n_gated)
+      .def_readonly("n_unused", &loam::LocalizeResult::n_unused)
+      .def_readonly("used_mask", &loam::LocalizeResult::used_mask)
+      .def_readonly("n_rows_initial", &loam::LocalizeResult::n_rows_initial)
+      .def("tobytes", [](const loam::LocalizeResult& r) { return py::bytes(reinterpret_cast<const char*>(&r), sizeof(r)); });
   py::class_<loam::SurfelMap>(m, "SurfelMap")
       .def(py::init<const loam::SurfelMapParams&, size_t>(), py::arg("params") = loam::SurfelMapParams(), py::arg("max_voxels") = (size_t)1 << 20)
       .def_property_readonly("params", &loam::SurfelMap::params)
@@ -779,6 +838,8 @@ PYBIND11_MODULE(loam_python, m) {
       .def("add", &surfel_map_add<float>, py::arg("points"), py::arg("world_T_sensor") = py::none())
       .def("add", &surfel_map_add<double>, py::arg("points"), py::arg("world_T_sensor") = py::none())
       .def("clear", &loam::SurfelMap::clear)
+      .def("localize", &surfel_map_localize<float>, py::arg("points"), py::arg("init"), py::arg("params") = loam::LocalizeParams())
+      .def("localize", &surfel_map_localize<double>, py::arg("points"), py::arg("init"), py::arg("params") = loam::LocalizeParams())
       .def(
           "surfels", [](const loam::SurfelMap& map, uint32_t min_points) { return surfel_arrays(map.surfels(min_points)); }, py::arg("min_points") = 1)
       .def(
