@@ -67,6 +67,11 @@ class CloudMap {
     loamx_ctx* ctx = gpu::defaultContext();
     gpu::check(ctx, loamx_cloud_map_clear(ctx, handle_.get()));
   }
+  /// Removes the voxels outside the box center + [lo, hi] (metres, map frame, widened to voxel boundaries; loamx.h, "map window"):
+  /// the map keeps following the sensor at a fixed max_voxels. Infinite bounds are allowed. Synchronises.
+  MapCrop crop(const std::array<double, 3>& lo, const std::array<double, 3>& hi, const std::array<double, 3>& center = {0.0, 0.0, 0.0}) {
+    return gpu::cropWindow(loamx_cloud_map_crop, handle_.get(), lo, hi, center);
+  }
   /// The centroids of the voxels that hold at least min_points points, in order of first appearance
   CloudMapPoints points(uint32_t min_points = 1) const {
     loamx_ctx* ctx = gpu::defaultContext();

@@ -3,8 +3,10 @@
  * behaviour); the heavy lifting happens in libloamx.so (MI355X HIP kernels) behind include/loamx.h.
  */
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <cstdlib>
 #include <exception>
 #include <mutex>
@@ -158,6 +160,37 @@ std::vector<float> packFloat(const std::vector<PointType, Alloc>& pts) {
   std::vector<float> xyz(pts.size() * 3);
   for (size_t i = 0; i < pts.size(); i++) xyz[3 * i] = pts[i].x, xyz[3 * i + 1] = pts[i].y, xyz[3 * i + 2] = pts[i].z;
   return xyz;
+}
+
+}  // namespace gpu
+
+/// What a map's crop returns: the voxels it kept and the voxels it removed
+struct MapCrop {
+  uint32_t kept = 0, removed = 0;
+};
+
+namespace gpu {
+
+/// The crop of CloudMap, SurfelMap and OccupancyMap (loamx.h, "map window") around a host-side centre: the centre is folded into
+/// lo and hi here and no pose is passed, which gives the bytes of the same centre in a device pose (0.0 + x == x). Synchronises.
+template <typename Map, typename CropFn>
+MapCrop cropWindow(CropFn crop_fn, Map* map, const std::array<double, 3>& lo, const std::array<double, 3>& hi, const std::array<double, 3>& center) {
+  loamx_ctx* ctx = defaultContext();
+  double l[3], h[3];
+  for (int a = 0; a < 3; a++) {
+    if (!std::isfinite(center[a])) throw std::runtime_error("crop: the center is not finite");
+    l[a] = center[a] + lo[a], h[a] = center[a] + hi[a];
+  }
+  void* d_counts = nullptr;
+  check(ctx, loamx_dev_alloc(ctx, 4 * sizeof(uint32_t), &d_counts));
+  uint32_t counts[4] = {0, 0, 0, 0};
+  int rc = crop_fn(ctx, map, nullptr, l, h, static_cast<uint32_t*>(d_counts));
+  if (rc == LOAMX_OK) rc = loamx_copy_to_host(ctx, counts, d_counts, sizeof(counts));
+  loamx_dev_free(ctx, d_counts);
+  check(ctx, rc);
+  MapCrop out;
+  out.kept = counts[0], out.removed = counts[1];
+  return out;
 }
 
 }  // namespace gpu

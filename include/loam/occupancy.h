@@ -79,6 +79,11 @@ class OccupancyMap {
     loamx_ctx* ctx = gpu::defaultContext();
     gpu::check(ctx, loamx_occupancy_clear(ctx, handle_.get()));
   }
+  /// Removes the voxels outside the box center + [lo, hi] (metres, map frame, widened to voxel boundaries; loamx.h, "map window"):
+  /// the map keeps following the sensor at a fixed max_voxels. Infinite bounds are allowed. Synchronises.
+  MapCrop crop(const std::array<double, 3>& lo, const std::array<double, 3>& hi, const std::array<double, 3>& center = {0.0, 0.0, 0.0}) {
+    return gpu::cropWindow(loamx_occupancy_crop, handle_.get(), lo, hi, center);
+  }
   /// Counts and state of the voxel of each point (map frame, packed x y z)
   OccupancyCells query(const std::vector<double>& xyz) const {
     loamx_ctx* ctx = gpu::defaultContext();

@@ -103,6 +103,11 @@ class SurfelMap {
     loamx_ctx* ctx = gpu::defaultContext();
     gpu::check(ctx, loamx_surfel_map_clear(ctx, handle_.get()));
   }
+  /// Removes the voxels outside the box center + [lo, hi] (metres, map frame, widened to voxel boundaries; loamx.h, "map window"):
+  /// the map keeps following the sensor at a fixed max_voxels. Infinite bounds are allowed. Synchronises.
+  MapCrop crop(const std::array<double, 3>& lo, const std::array<double, 3>& hi, const std::array<double, 3>& center = {0.0, 0.0, 0.0}) {
+    return gpu::cropWindow(loamx_surfel_map_crop, handle_.get(), lo, hi, center);
+  }
   /// The voxels that hold at least min_points points, in order of first appearance
   std::vector<Surfel> surfels(uint32_t min_points = 1) const {
     loamx_ctx* ctx = gpu::defaultContext();

@@ -1494,6 +1494,48 @@ int loamx_surfel_localizer_run_host_f32(loamx_ctx* ctx, loamx_surfel_localizer* 
                                         const double pose[7], const loamx_localize_params* params, loamx_localize_result* result,
                                         loamx_reg_information* info);
 
+/* ---- map window (no reference counterpart). A mapper runs for as long as the vehicle drives, and max_voxels is fixed at create:
+ * a crop removes the voxels of a cloud map, a surfel map or an occupancy map outside a box around a pose, so that a map of fixed
+ * size follows the sensor. One rule and one set of kernels (loam_amd/csrc/crop_kernels.hip) serve the three maps. The rule is
+ * executable in loam_amd/csrc/crop_math.h (host + device, every operation rounded on its own); tests/hostcheck_crop compares a g++
+ * build of it with numpy.
+ *
+ * d_pose: DEVICE memory, one pose of 7 doubles in the layout loamx_compose_trajectory_dev and the localiser's d_poses_out leave
+ * (quaternion first, translation in [4..6]). Only the translation is read: the window stays axis-aligned in the map frame, and a
+ * quaternion that is no unit quaternion or a NaN is not looked at. NULL: the centre is (0, 0, 0). With a device pose a crop can
+ * follow a pose the host has never seen. lo, hi: HOST values in metres relative to the centre; infinite bounds are allowed.
+ * d_counts_out: DEVICE memory or NULL, four words {kept, removed, skipped, 0}.
+ *   1 centre   c[a] = d_pose[4 + a], or +0.0 without a pose.
+ *   2 skip     if a c[a] is not finite the crop is SKIPPED: the map keeps every byte and the counts are {voxels, 0, 1, 0}. A NaN
+ *              pose from a lost localisation does not erase the map.
+ *   3 bounds   flo[a] = floor((c[a] + lo[a]) / leaf), fhi[a] = floor((c[a] + hi[a]) / leaf): the cloud map's cell function on the
+ *              corners of the box. +-inf stays +-inf.
+ *   4 keep     a voxel with the integer cell v (unpacked from its key) is kept iff (double)v[a] >= flo[a] && (double)v[a] <= fhi[a]
+ *              on all three axes. Every point of the closed box lies in a kept cell: the box is widened to voxel boundaries, never
+ *              narrowed.
+ * Because 0.0 + x == x, a caller that folds a host-side centre into lo and hi and passes NULL gets the same bytes; the conveniences
+ * of capi.py (crop), of include/loam and of the module loam do exactly that.
+ * The cloud map and the surfel map afterwards: the kept voxels keep every byte (key, first, sums or moments, W, count) and their
+ * relative order in the list; stats.voxels is `kept`; the running index, points_offered, points_used, the drop counters, overflow
+ * and claims are not touched. The room in the list is regained: later adds append behind the kept voxels. A removed voxel that is
+ * seen again is a new voxel: it gets the new running index as `first` and goes to the end of the list. Emit, query and the
+ * localiser see exactly the map with the removed entries deleted, by bytes. The occupancy map afterwards: the kept voxels keep
+ * their hits and passes, stats.voxels is `kept`, every other counter is untouched; query, box and slice read UNKNOWN and (0, 0)
+ * where a voxel was removed.
+ * A map that has overflowed since its last clear keeps the promise it had: the crop returns, nothing else is specified, and the
+ * overflow counter is not reset. The limit of 2^32 - 2 points or rays between two clears stays: a crop does not renumber `first`.
+ * Asynchronous on the context's stream, six launches, no host wait, nothing read back. The staging of a crop belongs to the handle:
+ * it is allocated at the handle's FIRST crop (that call may wait on the allocator), sized once by max_voxels (the occupancy map: by
+ * its table's slots), and freed at destroy; every later crop only enqueues. A refused call changes nothing.
+ * LOAMX_ERR_BAD_PARAM: a null map, a map of another context, null lo or hi, lo[a] > hi[a], a NaN bound. LOAMX_ERR_HIP: the
+ * allocation of the staging failed. */
+int loamx_cloud_map_crop(loamx_ctx* ctx, loamx_cloud_map* map, const double* d_pose, const double lo[3], const double hi[3],
+                         uint32_t* d_counts_out);
+int loamx_surfel_map_crop(loamx_ctx* ctx, loamx_surfel_map* map, const double* d_pose, const double lo[3], const double hi[3],
+                          uint32_t* d_counts_out);
+int loamx_occupancy_crop(loamx_ctx* ctx, loamx_occupancy_map* map, const double* d_pose, const double lo[3], const double hi[3],
+                         uint32_t* d_counts_out);
+
 /* ---- multi-GPU batch mode (BASELINE configs[3]) ------------------------------------------------
  * The reference has no counterpart (registration-inl.h:11-78 takes everything by value / const-ref: scan pairs are
  * independent units). One process per GPU owns a contiguous block of pair ids and runs the single-GPU entry points

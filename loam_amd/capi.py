@@ -509,6 +509,7 @@ EXPORTS = [
     "loamx_surfel_map_emit_host",
     "loamx_default_localize_params", "loamx_surfel_localizer_create", "loamx_surfel_localizer_destroy", "loamx_surfel_localizer_run",
     "loamx_surfel_localizer_run_f32", "loamx_surfel_localizer_run_host", "loamx_surfel_localizer_run_host_f32",
+    "loamx_cloud_map_crop", "loamx_surfel_map_crop", "loamx_occupancy_crop",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -786,6 +787,8 @@ def load(build_if_missing=True):
     lib.loamx_surfel_map_destroy.argtypes = [vp, vp]
     lib.loamx_surfel_map_destroy.restype = None
     lib.loamx_surfel_map_clear.argtypes = [vp, vp]
+    for name in ("loamx_cloud_map_crop", "loamx_surfel_map_crop", "loamx_occupancy_crop"):
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, vp]
     lib.loamx_surfel_map_add_clouds.argtypes = [vp, vp, vp, C.c_size_t, szp, C.c_size_t, vp]
     lib.loamx_surfel_map_add_clouds_f32.argtypes = lib.loamx_surfel_map_add_clouds.argtypes
     lib.loamx_surfel_map_emit.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, C.c_size_t, vp]
@@ -1139,6 +1142,42 @@ class _VoxelMap:
     def clear(self):
         """an empty map again (loamx_cloud_map_clear / loamx_occupancy_clear). Asynchronous."""
         self.ctx._check(self._fn("clear")(self.ctx.h, self._handle()))
+
+    @staticmethod
+    def _crop_bounds(lo, hi, what):
+        lo, hi = np.asarray(lo), np.asarray(hi)
+        if lo.shape != (3,) or hi.shape != (3,) or lo.dtype.kind not in "fiu" or hi.dtype.kind not in "fiu":
+            raise ValueError(f"{what}: lo and hi are three numbers each")
+        return np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+
+    def crop_dev(self, lo, hi, d_pose=0, d_counts_out=0):
+        """the voxels outside the box centre + [lo, hi] leave the map (include/loamx.h, "map window"); the centre is the translation
+        of the pose at the device address d_pose (7 doubles), or (0, 0, 0) for 0; lo, hi: host values, three each; d_counts_out: a
+        device address of four uint32 {kept, removed, skipped, 0}, or 0 (loamx_cloud_map_crop / loamx_surfel_map_crop /
+        loamx_occupancy_crop). Asynchronous; the handle's first crop allocates its staging."""
+        lo, hi = self._crop_bounds(lo, hi, "crop_dev")
+        self.ctx._check(self._fn("crop")(self.ctx.h, self._handle(), d_pose or None, lo.ctypes.data, hi.ctypes.data, d_counts_out or None))
+
+    def crop(self, lo, hi, center=None):
+        """crop_dev with a host centre (three numbers, None = the origin) folded into lo and hi on the host, which gives the same
+        bytes as the same centre in a device pose -> (kept, removed); synchronises"""
+        lo, hi = self._crop_bounds(lo, hi, "crop")
+        if center is not None:
+            c = np.asarray(center)
+            if c.shape != (3,) or c.dtype.kind not in "fiu":
+                raise ValueError("crop: center is three numbers")
+            c = c.astype(np.float64)
+            if not np.isfinite(c).all():
+                raise ValueError("crop: center is not finite")
+            lo, hi = c + lo, c + hi
+        buf = self.ctx.alloc(16)
+        try:
+            self.crop_dev(lo, hi, 0, buf.ptr)
+            self.ctx.synchronize()
+            counts = buf.download(np.uint32, 4)
+        finally:
+            buf.free()
+        return int(counts[0]), int(counts[1])
 
     def add_clouds_dev(self, d_points, point_stride, cloud_offsets, d_poses=0, f32=False):
         """len(cloud_offsets) - 1 device-resident clouds back to back, cloud c at the pose d_poses[c] (a device address of

@@ -130,6 +130,13 @@ int loamx_cloud_map_clear(loamx_ctx* ctx, loamx_cloud_map* map) {
   return voxel_map_clear(ctx, map);
 }
 
+int loamx_cloud_map_crop(loamx_ctx* ctx, loamx_cloud_map* map, const double* d_pose, const double lo[3], const double hi[3], uint32_t* d_counts_out) {
+  CropTable t = {};
+  if (map)
+    t = {map->t.keys, map->t.sums, map->t.first, map->t.count, map->t.list, map->t.lens + kCloudLenListed, nullptr, map->t.log2_cap, 3u, map->t.max_voxels};
+  return voxel_map_crop(ctx, map, kKind, t, map ? map->rule.leaf : 0.0, d_pose, lo, hi, d_counts_out);
+}
+
 int loamx_cloud_map_add_clouds_dev(loamx_ctx* ctx, loamx_cloud_map* map, const double* d_points, size_t point_stride, const size_t* cloud_offsets,
                                    size_t n_clouds, const double* d_poses) {
   return voxel_map_add_dev(ctx, map, kKind, d_points, false, point_stride, cloud_offsets, n_clouds, d_poses);

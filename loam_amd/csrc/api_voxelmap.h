@@ -1,5 +1,5 @@
 // api_voxelmap.h — the host side that the handles of the cloud map (api_cloudmap.hip) and of the occupancy map
-// (api_occupancy.hip) share: the head of the handle, the checks, clear and destroy, and the two forms of an add around the
+// (api_occupancy.hip) share: the head of the handle, the checks, clear, crop and destroy, and the two forms of an add around the
 // map's own add_locked. Each map names itself in a VoxelMapKind, so every error text reads as that map's.
 #pragma once
 #include "api_host.h"
@@ -14,6 +14,7 @@ struct VoxelMapBase {
   size_t ones_bytes = 0;       // at the block's start (the keys first): 0xFF bytes in an empty map
   size_t zeros_bytes = 0;      // behind them: zero bytes in an empty map
   uint64_t offered = 0;        // points or rays offered since the last clear (the cloud map's running index of the next call)
+  void* crop_block = nullptr;  // the scratch of a crop (crop_kernels.hip), allocated at the handle's first crop, freed at destroy
 };
 
 struct VoxelMapKind {
@@ -48,6 +49,31 @@ inline void voxel_map_destroy(loamx_ctx* ctx, VoxelMapBase* map) {
     (void)hipStreamSynchronize(ctx->stream);
   }
   if (map->block) (void)hipFree(map->block);
+  if (map->crop_block) (void)hipFree(map->crop_block);
+}
+
+// The map window (loamx.h, "map window") of any of the three maps: `t` is the map's table as the crop sees it. The checks and their
+// texts are those of loamx_target_index_crop; a refused call changes nothing. The handle's first crop allocates the scratch (and
+// may wait on the allocator), every later one only enqueues. The counters, `offered` and the overflow word are not touched.
+inline int voxel_map_crop(loamx_ctx* ctx, VoxelMapBase* map, const VoxelMapKind& kind, const CropTable& t, double leaf, const double* d_pose,
+                          const double* lo, const double* hi, uint32_t* d_counts_out) {
+  API_ENTER(ctx);
+  int rc = voxel_map_check(ctx, map, kind);
+  if (rc != LOAMX_OK) return rc;
+  if (!lo || !hi) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  for (int c = 0; c < 3; c++)
+    if (!(lo[c] <= hi[c])) return fail(ctx, LOAMX_ERR_BAD_PARAM, "crop box: lo <= hi on every axis (and no NaN)");
+  if (!map->crop_block) {
+    hipError_t e = hipMalloc(&map->crop_block, crop_scratch_bytes(t));
+    if (e != hipSuccess) {
+      map->crop_block = nullptr;
+      return fail(ctx, LOAMX_ERR_HIP, std::string(kind.name) + " crop scratch: " + hipGetErrorString(e));
+    }
+  }
+  untimed(ctx);
+  launch_voxel_crop(t, crop_scratch_carve(map->crop_block, t), leaf, d_pose, lo, hi, d_counts_out, ctx->stream);
+  CHECK_LAUNCH(ctx, "map crop kernels");
+  return LOAMX_OK;
 }
 
 // the argument checks the device and the host forms of an add share; *total: the items of the call

@@ -701,6 +701,38 @@ void launch_localize_accumulate(const void* d_points, bool f32, uint32_t stride,
 void launch_localize_step(const OrgOffsets& offs, uint32_t n_clouds, LocState* state, const LocSolve& P, const LocPartial* partials, bool final_pass,
                           double* d_poses_out, LocResult* d_results, loamx_reg_information* d_info, hipStream_t s);
 
+/* ---- map window (crop_kernels.hip; the rule: crop_math.h and loamx.h) -------------------------------------------------------------- */
+// One of the three voxel tables as the crop sees it: key slots, `payload_words` 64-bit words per slot, and what only the listed
+// maps have (nullptr in the occupancy map, whose entries are its slots).
+struct CropTable {
+  unsigned long long* keys;     // [cap]
+  unsigned long long* payload;  // [cap][payload_words]: the cloud map's sums, the surfel map's moments, the occupancy map's counts
+  uint32_t* first;              // [cap] or nullptr
+  uint32_t* count;              // [cap] or nullptr
+  uint32_t* list;               // [entries] slots in order of first appearance, or nullptr: entry j is slot j
+  uint32_t* listed;             // the list's length (lens + kCloudLenListed), nullptr without a list
+  unsigned long long* voxels;   // the occupancy map's voxel counter (words + kOccWordVoxels), nullptr with a list
+  uint32_t log2_cap, payload_words;
+  uint32_t entries;             // max_voxels with a list, 2^log2_cap without
+};
+enum { kCropCtlKept = 0, kCropCtlSkip = 1, kCropCtlWords = 4 };
+// the scratch of a crop (a handle's, allocated at its first crop): flags, tiles and control words, then the staged voxels
+struct CropScratch {
+  uint8_t* keep;                // [entries]
+  uint32_t* tiles;              // map_compact_ws_bytes(entries)
+  uint32_t* ctl;                // [kCropCtlWords]
+  unsigned long long* keys;     // [entries]
+  unsigned long long* payload;  // [payload_words][entries]
+  uint32_t* first;              // [entries] (unused without CropTable::first)
+  uint32_t* count;              // [entries]
+};
+size_t crop_scratch_bytes(const CropTable& t);
+CropScratch crop_scratch_carve(void* block, const CropTable& t);
+// six launches: flags, the two of the tile offsets, gather, reset, scatter (which also commits the length). d_pose, d_counts_out: may
+// be nullptr.
+void launch_voxel_crop(const CropTable& t, const CropScratch& w, double leaf, const double* d_pose, const double lo[3], const double hi[3],
+                       uint32_t* d_counts_out, hipStream_t s);
+
 /* ---- synthetic generator (synth_kernels.hip) --------------------------------------------------- */
 void launch_synth_pairs(uint64_t seed, uint64_t first_pair, size_t n_pairs, uint32_t H, uint32_t W, double sigma,
                         double* d_xyz, hipStream_t s);

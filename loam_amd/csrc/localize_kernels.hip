@@ -31,6 +31,10 @@ static_assert(kLocCounters <= 8, "LocPartial::c holds the counters");
 
 // one listed voxel per thread: surfel_finish and the usable test, one record at the voxel's SLOT. Thread j < n_clouds also sets
 // up the state of cloud j from the call's poses (before any launch writes d_poses_out, which may be the same array).
+// A crop of the map (crop_kernels.hip) rebuilds the table, so a voxel may sit in another slot than in the call before, and slots that
+// held a removed voxel keep the record an earlier call wrote. That is harmless: the cache is rebuilt here for every listed voxel on
+// every call, the accumulate kernel reads a record only at a slot it reached through a key (voxel_find), and every key of a map that
+// has not overflowed is listed.
 __global__ __launch_bounds__(kLocThreads) void localize_planes_kernel(SurfelTable t, double leaf, uint32_t min_points, double planarity,
                                                                       LocPlane* __restrict__ cache, const double* __restrict__ poses_in,
                                                                       uint32_t n_clouds, uint32_t max_iterations, LocState* __restrict__ state) {

@@ -777,6 +777,13 @@ PYBIND11_MODULE(loam_python, m) {
       .def("add", &cloud_map_add<double>, py::arg("points"), py::arg("world_T_sensor") = py::none())
       .def("clear", &loam::CloudMap::clear)
       .def(
+          "crop",
+          [](loam::CloudMap& map, const std::array<double, 3>& lo, const std::array<double, 3>& hi, const std::array<double, 3>& center) {
+            const loam::MapCrop c = map.crop(lo, hi, center);
+            return py::make_tuple(c.kept, c.removed);
+          },
+          py::arg("lo"), py::arg("hi"), py::arg("center") = std::array<double, 3>{0.0, 0.0, 0.0})
+      .def(
           "points",
           [](const loam::CloudMap& map, uint32_t min_points) {
             const loam::CloudMapPoints p = map.points(min_points);
@@ -838,6 +845,13 @@ PYBIND11_MODULE(loam_python, m) {
       .def("add", &surfel_map_add<float>, py::arg("points"), py::arg("world_T_sensor") = py::none())
       .def("add", &surfel_map_add<double>, py::arg("points"), py::arg("world_T_sensor") = py::none())
       .def("clear", &loam::SurfelMap::clear)
+      .def(
+          "crop",
+          [](loam::SurfelMap& map, const std::array<double, 3>& lo, const std::array<double, 3>& hi, const std::array<double, 3>& center) {
+            const loam::MapCrop c = map.crop(lo, hi, center);
+            return py::make_tuple(c.kept, c.removed);
+          },
+          py::arg("lo"), py::arg("hi"), py::arg("center") = std::array<double, 3>{0.0, 0.0, 0.0})
       .def("localize", &surfel_map_localize<float>, py::arg("points"), py::arg("init"), py::arg("params") = loam::LocalizeParams())
       .def("localize", &surfel_map_localize<double>, py::arg("points"), py::arg("init"), py::arg("params") = loam::LocalizeParams())
       .def(
@@ -887,6 +901,13 @@ PYBIND11_MODULE(loam_python, m) {
       .def("add", &occupancy_add<float>, py::arg("points"), py::arg("world_T_sensor") = py::none())
       .def("add", &occupancy_add<double>, py::arg("points"), py::arg("world_T_sensor") = py::none())
       .def("clear", &loam::OccupancyMap::clear)
+      .def(
+          "crop",
+          [](loam::OccupancyMap& map, const std::array<double, 3>& lo, const std::array<double, 3>& hi, const std::array<double, 3>& center) {
+            const loam::MapCrop c = map.crop(lo, hi, center);
+            return py::make_tuple(c.kept, c.removed);
+          },
+          py::arg("lo"), py::arg("hi"), py::arg("center") = std::array<double, 3>{0.0, 0.0, 0.0})
       .def(
           "query",
           [](const loam::OccupancyMap& map, const Arr& points) {
