@@ -46,6 +46,24 @@ struct OccupancyCells {
   Occupancy state(size_t i) const { return static_cast<Occupancy>(states[i]); }
 };
 
+/// loamx_distance_params; the defaults are loamx_default_distance_params'
+struct DistanceParams {
+  uint32_t max_dist_voxels = 10;     ///< the cap R in voxels, 1 .. 255: no obstacle within it reads FAR
+  bool unknown_is_obstacle = false;  ///< voxels never seen count as obstacles
+};
+
+/// What OccupancyMap::distanceBox and ::distanceSlice return (loamx.h, "occupancy distance field"): per entry the squared
+/// distance in voxels to the nearest obstacle (FAR beyond the cap), the offset to that obstacle in voxels (`axes` int16 per entry:
+/// 3 for a box, 2 for a slice; zeros where d2 is 0 or FAR) and the distance in metres (+inf for FAR)
+struct DistanceField {
+  static constexpr uint16_t FAR = LOAMX_DIST_FAR;
+  size_t axes = 3;
+  std::vector<uint16_t> d2;
+  std::vector<int16_t> offset;
+  std::vector<float> metres;
+  size_t size() const { return d2.size(); }
+};
+
 /// The map (loamx_occupancy_map): table and counters on the device. Cheap to copy (shared handle).
 class OccupancyMap {
  public:
@@ -109,6 +127,15 @@ class OccupancyMap {
     gpu::check(ctx, loamx_occupancy_slice(ctx, handle_.get(), vmin.data(), dims.data(), grid.data()));
     return grid;
   }
+  /// The clearance of every voxel of the box: the exact distance to the nearest obstacle voxel of the map, those in a halo of
+  /// max_dist_voxels around the box included. The layout is box()'s.
+  DistanceField distanceBox(const std::array<int32_t, 3>& vmin, const std::array<uint32_t, 3>& dims, const DistanceParams& params = DistanceParams()) {
+    return distance(loamx_occupancy_distance_box_host, vmin, dims, params, (size_t)dims[0] * dims[1] * dims[2], 3);
+  }
+  /// The 2-D clearance grid of the box's columns, each column an obstacle by the state slice() gives it. The layout is slice()'s.
+  DistanceField distanceSlice(const std::array<int32_t, 3>& vmin, const std::array<uint32_t, 3>& dims, const DistanceParams& params = DistanceParams()) {
+    return distance(loamx_occupancy_distance_slice_host, vmin, dims, params, (size_t)dims[0] * dims[1], 2);
+  }
   OccupancyStats stats() const {
     loamx_ctx* ctx = gpu::defaultContext();
     loamx_occupancy_stats s;
@@ -121,6 +148,19 @@ class OccupancyMap {
   loamx_occupancy_map* handle() const { return handle_.get(); }
 
  private:
+  template <typename Fn>
+  DistanceField distance(Fn fn, const std::array<int32_t, 3>& vmin, const std::array<uint32_t, 3>& dims, const DistanceParams& params, size_t n,
+                         size_t axes) {
+    loamx_ctx* ctx = gpu::defaultContext();
+    loamx_distance_params p;
+    loamx_default_distance_params(&p);
+    p.max_dist_voxels = params.max_dist_voxels, p.unknown_is_obstacle = params.unknown_is_obstacle ? 1u : 0u;
+    DistanceField out;
+    out.axes = axes;
+    out.d2.resize(n), out.offset.resize(axes * n), out.metres.resize(n);
+    gpu::check(ctx, fn(ctx, handle_.get(), vmin.data(), dims.data(), &p, out.d2.data(), out.offset.data(), out.metres.data()));
+    return out;
+  }
   template <template <typename> class Accessor, typename PointType, typename Alloc>
   void addPacked(const std::vector<PointType, Alloc>& points, const double* pose) {
     loamx_ctx* ctx = gpu::defaultContext();

@@ -261,6 +261,7 @@ int loamx_ctx_last_assoc_coop_forms(loamx_ctx* ctx, int which_kind, uint32_t out
  *   segmentation:  NO_SEGMENT_TILES (every connected edge through the global union, no tile labelling in LDS: the same bytes, see "scan segmentation")
  *   map cleaning:  NO_VISIBILITY_RANGES (the votes kernel reads the scans' points, no first launch that writes every cell's squared range: the same bytes, see "map cleaning")
  *   occupancy map: NO_OCCUPANCY_COMBINE (one claim per visit instead of one per run of a wavefront: the same bytes, see "occupancy map")
+ *   distance field: NO_DISTANCE_EARLY_EXIT (the y- and z-pass walk their whole window: the same bytes, see "occupancy distance field")
  *   surfel map:    NO_SURFEL_COMBINE (one claim per point instead of one per run of a wavefront: the same bytes, see "surfel map")
  *   localisation:  NO_LOCALIZE_PLANES (no plane cache, every candidate voxel finished where it is looked at: the same bytes, see "surfel localisation")
  * Unknown name: LOAMX_ERR_BAD_PARAM.
@@ -1289,6 +1290,59 @@ int loamx_occupancy_query(loamx_ctx* ctx, const loamx_occupancy_map* map, const 
 int loamx_occupancy_box(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3], uint32_t* counts_out,
                         uint8_t* state_out);
 int loamx_occupancy_slice(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3], uint8_t* grid_out);
+
+/* ---- occupancy distance field (no reference counterpart; the ESDF of voxblox and nvblox, truncated). What a planner takes from
+ * an occupancy map is clearance: per voxel of a box, or per column of a slice, the exact Euclidean distance to the nearest
+ * obstacle voxel and the direction to it. The field is integer and exact, so every schedule gives the same bytes and a numpy model
+ * is compared by equality (tests/distance_common.py). The rule is executable in loam_amd/csrc/distance_math.h (host + device);
+ * tests/hostcheck_distance compares a g++ build of it with the model.
+ *   obstacle   a voxel is an obstacle iff its state is OCCUPIED, or, with unknown_is_obstacle, UNKNOWN. The state of a voxel is
+ *              the one loamx_occupancy_box_dev writes: step 5 of the occupancy map on the voxel's counts, (0, 0) for a voxel
+ *              without a slot and for a voxel outside |v| < 2^20, which reads as without a slot. With the usual thresholds
+ *              (min_hits >= 1, min_passes >= 1) both are UNKNOWN. The slice: column (x, y) takes the state
+ *              loamx_occupancy_slice_dev gives it over its dims[2] levels, and the field is 2-D over columns.
+ *   field      R = max_dist_voxels, 1 <= R <= 255. For a voxel v of the box, D(v) is the minimum of |w - v|^2, the integer sum of
+ *              the squared offsets, over ALL obstacle voxels w of the lattice, those outside the box included: the map is read
+ *              in a halo of R voxels around the box on every axis (the slice: on x and y), so a window that follows the robot has
+ *              no edge artefacts. d2(v) = D(v) if D(v) <= R^2, otherwise LOAMX_DIST_FAR = 0xFFFF; R^2 <= 65025 < 0xFFFF. An
+ *              obstacle voxel has d2 = 0.
+ *   nearest    offset(v) = w* - v per axis, where w* is the minimiser with the LOWEST LINEAR INDEX, x fastest: the lowest z, then
+ *              the lowest y, then the lowest x. (0, 0, 0) where d2 is 0 or LOAMX_DIST_FAR. The slice has two components (x, y).
+ *   metres     (float)(sqrt((double) d2) * leaf), each operation rounded on its own; +inf for LOAMX_DIST_FAR.
+ * Truncation stays exact: if D(v) <= R^2 the minimiser lies within +-R on every axis, so three separable passes x, y, z over
+ * windows of +-R find it, and every intermediate above R^2 may be dropped as "none". Ties of the passes go to the lower
+ * coordinate (x-pass: the lower x; y-pass: the lower y'; z-pass: the lower z'), which yields exactly the minimiser named above.
+ * Layout: that of loamx_occupancy_box_dev (entry (z dims[1] + y) dims[0] + x) and of loamx_occupancy_slice_dev (y dims[0] + x);
+ * offsets are 3 (slice: 2) int16 per entry. Each of the three outputs may be NULL. A box with a dimension of 0 writes nothing (the
+ * slice: dims[0] or dims[1]; with dims[2] == 0 every column is UNKNOWN).
+ * Kernels (loam_amd/csrc/distance_kernels.hip): a bit mask of the extended box, one wavefront's ballot per 64-bit word (the only
+ * launch that reads the table); the x-pass on the mask words by count-leading / count-trailing zeros; the y-pass and the z-pass one
+ * voxel per lane, walking outwards and stopping as soon as k^2 exceeds the best found, so the cost follows the distance found and
+ * not R. Context option NO_DISTANCE_EARLY_EXIT: the whole window is walked; the same bytes. No atomics, nothing read back.
+ * The device forms enqueue on the context's stream and return. The mask and the pass intermediates belong to the handle: they are
+ * allocated at the handle's first distance call, grown when a call needs more (such a call may wait on the allocator and the
+ * stream) and freed at destroy; every call that fits only enqueues. The map's table is only read. A refused call changes nothing,
+ * outputs included.
+ * LOAMX_ERR_BAD_PARAM: a null map, vmin, dims or params, max_dist_voxels == 0, a map of another context. LOAMX_ERR_UNSUPPORTED:
+ * max_dist_voxels > 255; more than 2^31 voxels in the EXTENDED box (dims + 2R per axis; the slice: dims[0] + 2R by dims[1] + 2R
+ * columns). LOAMX_ERR_HIP: the allocation of the staging failed. */
+#define LOAMX_DIST_FAR 0xFFFFu
+typedef struct {
+  uint32_t max_dist_voxels;     /* 10 */
+  uint32_t unknown_is_obstacle; /* 0 */
+} loamx_distance_params;
+void loamx_default_distance_params(loamx_distance_params* p);
+int loamx_occupancy_distance_box(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3],
+                                 const loamx_distance_params* params, uint16_t* d_d2_out /* [n] */, int16_t* d_offset_out /* [n][3] */,
+                                 float* d_metres_out /* [n] */);
+int loamx_occupancy_distance_slice(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3],
+                                   const loamx_distance_params* params, uint16_t* d_d2_out /* [dims[1]][dims[0]] */,
+                                   int16_t* d_offset_out /* [.][2] */, float* d_metres_out);
+/* host forms, synchronous: the same fields to host arrays */
+int loamx_occupancy_distance_box_host(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3],
+                                      const loamx_distance_params* params, uint16_t* d2_out, int16_t* offset_out, float* metres_out);
+int loamx_occupancy_distance_slice_host(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3],
+                                        const loamx_distance_params* params, uint16_t* d2_out, int16_t* offset_out, float* metres_out);
 
 /* ---- surfel map (no reference counterpart; the per-voxel Gaussians of NDT, the surfels of a point-to-plane map). What the
  * consumers of a map need beyond a centroid: per voxel the mean, the covariance, its eigenvalues and the normal, turned towards

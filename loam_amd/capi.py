@@ -326,6 +326,29 @@ class OccupancyParams:
 OCCUPANCY_STATS_DTYPE = np.dtype([(n, np.uint64) for n in ("rays_offered", "rays_hit", "invalid", "range_short", "range_long", "outside", "visits",
                                                           "voxels", "overflow")])
 OCC_UNKNOWN, OCC_FREE, OCC_OCCUPIED = 0, 1, 2  # LOAMX_OCC_*: the state of a voxel
+DIST_FAR = 0xFFFF  # LOAMX_DIST_FAR: the squared distance of a voxel with no obstacle within max_dist_voxels
+
+
+class DistanceParamsStruct(C.Structure):
+    """loamx_distance_params (include/loamx.h)"""
+    _fields_ = [("max_dist_voxels", C.c_uint32), ("unknown_is_obstacle", C.c_uint32)]
+
+
+class DistanceParams:
+    """The rule of an occupancy distance field (loamx_distance_params): the cap R in voxels (1 .. 255) and whether UNKNOWN voxels
+    are obstacles. Anything left out takes the C ABI's default."""
+    NAMES = ("max_dist_voxels", "unknown_is_obstacle")
+
+    def __init__(self, max_dist_voxels=None, unknown_is_obstacle=None):
+        d = DistanceParamsStruct()
+        load().loamx_default_distance_params(C.byref(d))
+        self.max_dist_voxels = d.max_dist_voxels if max_dist_voxels is None else max_dist_voxels
+        self.unknown_is_obstacle = d.unknown_is_obstacle if unknown_is_obstacle is None else unknown_is_obstacle
+
+    def struct(self):
+        if not 0 <= int(self.max_dist_voxels) <= 0xFFFFFFFF:
+            raise ValueError("DistanceParams: max_dist_voxels does not fit 32 bits")
+        return DistanceParamsStruct(int(self.max_dist_voxels), 1 if self.unknown_is_obstacle else 0)
 
 
 class SegmentParamsStruct(C.Structure):
@@ -510,6 +533,8 @@ EXPORTS = [
     "loamx_default_localize_params", "loamx_surfel_localizer_create", "loamx_surfel_localizer_destroy", "loamx_surfel_localizer_run",
     "loamx_surfel_localizer_run_f32", "loamx_surfel_localizer_run_host", "loamx_surfel_localizer_run_host_f32",
     "loamx_cloud_map_crop", "loamx_surfel_map_crop", "loamx_occupancy_crop",
+    "loamx_default_distance_params", "loamx_occupancy_distance_box", "loamx_occupancy_distance_slice",
+    "loamx_occupancy_distance_box_host", "loamx_occupancy_distance_slice_host",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -777,6 +802,11 @@ def load(build_if_missing=True):
     lib.loamx_occupancy_box.argtypes = lib.loamx_occupancy_box_dev.argtypes
     lib.loamx_occupancy_slice_dev.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), vp]
     lib.loamx_occupancy_slice.argtypes = lib.loamx_occupancy_slice_dev.argtypes
+    lib.loamx_default_distance_params.argtypes = [C.POINTER(DistanceParamsStruct)]
+    lib.loamx_default_distance_params.restype = None
+    for name in ("loamx_occupancy_distance_box", "loamx_occupancy_distance_slice", "loamx_occupancy_distance_box_host",
+                 "loamx_occupancy_distance_slice_host"):
+        getattr(lib, name).argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(DistanceParamsStruct), vp, vp, vp]
     lib.loamx_occupancy_stats_read.argtypes = [vp, vp, vp]
     lib.loamx_occupancy_claims_read.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
     lib.loamx_occupancy_add_cloud.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
@@ -1325,6 +1355,41 @@ class OccupancyMap(_VoxelMap):
         self.ctx._check(self.ctx.lib.loamx_occupancy_slice(self.ctx.h, self._handle(), v.ctypes.data_as(C.POINTER(C.c_int32)),
                                                            d.ctypes.data_as(C.POINTER(C.c_uint32)), grid.ctypes.data))
         return grid
+
+    def _distance_dev(self, name, vmin, dims, params, d_d2_out, d_offset_out, d_metres_out):
+        v, d = _box_args(vmin, dims, name)
+        st = (params or DistanceParams()).struct()
+        self.ctx._check(getattr(self.ctx.lib, "loamx_occupancy_" + name)(
+            self.ctx.h, self._handle(), v.ctypes.data_as(C.POINTER(C.c_int32)), d.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st),
+            d_d2_out or None, d_offset_out or None, d_metres_out or None))
+
+    def distance_box_dev(self, vmin, dims, params=None, d_d2_out=0, d_offset_out=0, d_metres_out=0):
+        """the distance field of the box (include/loamx.h, "occupancy distance field") to device addresses, each 0 = not wanted:
+        squared distances in voxels (uint16 [n], DIST_FAR beyond the cap), offsets to the nearest obstacle (int16 [n][3]) and metres
+        (float32 [n]), in the layout of box_dev (loamx_occupancy_distance_box). Asynchronous."""
+        self._distance_dev("distance_box", vmin, dims, params, d_d2_out, d_offset_out, d_metres_out)
+
+    def distance_slice_dev(self, vmin, dims, params=None, d_d2_out=0, d_offset_out=0, d_metres_out=0):
+        """the 2-D distance field of the box's columns to device addresses, each 0 = not wanted: uint16 [dims[1]][dims[0]], int16
+        [.][2], float32 (loamx_occupancy_distance_slice). Asynchronous."""
+        self._distance_dev("distance_slice", vmin, dims, params, d_d2_out, d_offset_out, d_metres_out)
+
+    def _distance_host(self, name, vmin, dims, params, shape, axes):
+        v, d = _box_args(vmin, dims, name)
+        st = (params or DistanceParams()).struct()
+        d2, offset, metres = np.zeros(shape, dtype=np.uint16), np.zeros(shape + (axes,), dtype=np.int16), np.zeros(shape, dtype=np.float32)
+        self.ctx._check(getattr(self.ctx.lib, "loamx_occupancy_" + name + "_host")(
+            self.ctx.h, self._handle(), v.ctypes.data_as(C.POINTER(C.c_int32)), d.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st),
+            d2.ctypes.data, offset.ctypes.data, metres.ctypes.data))
+        return d2, offset, metres
+
+    def distance_box(self, vmin, dims, params=None):
+        """(d2 (dz, dy, dx) uint16, offset (dz, dy, dx, 3) int16, metres (dz, dy, dx) float32) of the box"""
+        return self._distance_host("distance_box", vmin, dims, params, (int(dims[2]), int(dims[1]), int(dims[0])), 3)
+
+    def distance_slice(self, vmin, dims, params=None):
+        """(d2 (dy, dx) uint16, offset (dy, dx, 2) int16, metres (dy, dx) float32) of the box's columns"""
+        return self._distance_host("distance_slice", vmin, dims, params, (int(dims[1]), int(dims[0])), 2)
 
     def stats(self):
         """one OCCUPANCY_STATS_DTYPE record (loamx_occupancy_stats_read; synchronises)"""

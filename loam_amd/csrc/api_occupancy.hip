@@ -1,12 +1,16 @@
 // api_occupancy.hip — the occupancy map (loamx.h, "occupancy map"): the map handle with its one device block (table and counters),
-// the add, clear, query, box, slice and stats entry points and their host forms.
+// the add, clear, query, box, slice and stats entry points and their host forms, and the distance field of a box or slice
+// (loamx.h, "occupancy distance field") with the staging the handle keeps for it.
 #include "api_voxelmap.h"
+#include "distance_math.h"
 
 struct loamx_occupancy_map : loamx::VoxelMapBase {  // ones: keys; zeros: counts and counters
   loamx_occupancy_params params = {};
   loamx::OccRule rule = {};
   loamx::OccStateRule state_rule = {};
   loamx::OccTable t = {};
+  void* dist_block = nullptr;  // the staging of the distance field, allocated at the first distance call, grown when one needs more
+  size_t dist_bytes = 0;
 };
 
 using namespace loamx;
@@ -88,6 +92,79 @@ int read_out(loamx_ctx* ctx, size_t n, uint32_t* counts_out, uint8_t* state_out)
 
 bool bad_double(double v) { return !isfinite(v) || v < 0.0; }
 
+// the checks of a distance call; *n: the voxels of the box or the columns of the slice (0: nothing to do)
+int distance_check(loamx_ctx* ctx, const loamx_occupancy_map* map, const int32_t* vmin, const uint32_t* dims, const loamx_distance_params* params,
+                   bool slice, unsigned long long* n) {
+  int rc = voxel_map_check(ctx, map, kKind);
+  if (rc != LOAMX_OK) return rc;
+  if (!vmin || !dims || !params) return fail(ctx, LOAMX_ERR_BAD_PARAM, "null argument");
+  if (params->max_dist_voxels == 0) return fail(ctx, LOAMX_ERR_BAD_PARAM, "max_dist_voxels must be >= 1");
+  if (params->max_dist_voxels > kDistMaxR) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "max_dist_voxels > 255 not supported");
+  const unsigned long long halo = 2ull * params->max_dist_voxels;
+  unsigned long long ext = dims[0] + halo;  // every factor and every product is tested before the next is formed
+  if (ext <= kOccMaxRead) ext *= dims[1] + halo;
+  if (ext <= kOccMaxRead && !slice) ext *= dims[2] + halo;
+  if (ext > kOccMaxRead) return fail(ctx, LOAMX_ERR_UNSUPPORTED, "the box extended by max_dist_voxels on every side holds at most 2^31 voxels");
+  *n = (unsigned long long)dims[0] * dims[1] * (slice ? 1u : dims[2]);
+  return LOAMX_OK;
+}
+
+// grows the handle's staging to the call's size (the only part of a distance call that may wait) and enqueues the launches
+int launch_distance_call(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t* vmin, const uint32_t* dims, const loamx_distance_params* params,
+                         bool slice, uint16_t* d_d2, int16_t* d_offset, float* d_metres) {
+  const DistGeom g = make_dist_geom(vmin, dims, params->max_dist_voxels, params->unknown_is_obstacle != 0, slice);
+  size_t bytes = 0;
+  (void)dist_staging_carve(nullptr, g, &bytes);
+  if (bytes > map->dist_bytes) {
+    if (map->dist_block) {
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      HIP_TRY(ctx, hipFree(map->dist_block));
+      map->dist_block = nullptr, map->dist_bytes = 0;
+    }
+    hipError_t e = hipMalloc(&map->dist_block, bytes);
+    if (e != hipSuccess) {
+      map->dist_block = nullptr;
+      return fail(ctx, LOAMX_ERR_HIP, std::string("distance field staging: ") + hipGetErrorString(e));
+    }
+    map->dist_bytes = bytes;
+  }
+  untimed(ctx);
+  launch_distance(map->t, map->state_rule, map->rule.leaf, g, dist_staging_carve(map->dist_block, g, nullptr),
+                  !(ctx->reg_flags & kRegFlagNoDistanceEarlyExit), d_d2, d_offset, d_metres, ctx->stream);
+  CHECK_LAUNCH(ctx, "occupancy distance kernels");
+  return LOAMX_OK;
+}
+
+int distance_dev(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t* vmin, const uint32_t* dims, const loamx_distance_params* params, bool slice,
+                 uint16_t* d_d2, int16_t* d_offset, float* d_metres) {
+  API_ENTER(ctx);
+  unsigned long long n = 0;
+  int rc = distance_check(ctx, map, vmin, dims, params, slice, &n);
+  if (rc != LOAMX_OK || n == 0 || (!d_d2 && !d_offset && !d_metres)) return rc;
+  return launch_distance_call(ctx, map, vmin, dims, params, slice, d_d2, d_offset, d_metres);
+}
+
+int distance_host(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t* vmin, const uint32_t* dims, const loamx_distance_params* params, bool slice,
+                  uint16_t* d2_out, int16_t* offset_out, float* metres_out) {
+  API_ENTER(ctx);
+  unsigned long long n = 0;
+  int rc = distance_check(ctx, map, vmin, dims, params, slice, &n);
+  if (rc != LOAMX_OK || n == 0 || (!d2_out && !offset_out && !metres_out)) return rc;
+  const size_t axes = slice ? 2 : 3;
+  const size_t o_off = align256(n * sizeof(uint16_t)), o_m = o_off + align256(n * axes * sizeof(int16_t));
+  untimed(ctx);
+  ENSURE(ctx, WS_OCC_OUT, o_m + n * sizeof(float));
+  char* b = static_cast<char*>(ctx->ws[WS_OCC_OUT].p);
+  rc = launch_distance_call(ctx, map, vmin, dims, params, slice, d2_out ? reinterpret_cast<uint16_t*>(b) : nullptr,
+                            offset_out ? reinterpret_cast<int16_t*>(b + o_off) : nullptr, metres_out ? reinterpret_cast<float*>(b + o_m) : nullptr);
+  if (rc != LOAMX_OK) return rc;
+  if (d2_out) HIP_TRY(ctx, hipMemcpyAsync(d2_out, b, n * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (offset_out) HIP_TRY(ctx, hipMemcpyAsync(offset_out, b + o_off, n * axes * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (metres_out) HIP_TRY(ctx, hipMemcpyAsync(metres_out, b + o_m, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return LOAMX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -143,6 +220,7 @@ int loamx_occupancy_create(loamx_ctx* ctx, const loamx_occupancy_params* params,
 void loamx_occupancy_destroy(loamx_ctx* ctx, loamx_occupancy_map* map) {
   if (!map) return;
   voxel_map_destroy(ctx, map);
+  if (map->dist_block) (void)hipFree(map->dist_block);  // (behind the stream's work: voxel_map_destroy has waited for it)
   delete map;
 }
 
@@ -255,6 +333,28 @@ int loamx_occupancy_slice(loamx_ctx* ctx, const loamx_occupancy_map* map, const 
   HIP_TRY(ctx, hipMemcpyAsync(grid_out, ctx->ws[WS_OCC_OUT].p, n, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return LOAMX_OK;
+}
+
+void loamx_default_distance_params(loamx_distance_params* p) {
+  if (!p) return;
+  p->max_dist_voxels = 10, p->unknown_is_obstacle = 0;
+}
+
+int loamx_occupancy_distance_box(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3],
+                                 const loamx_distance_params* params, uint16_t* d_d2_out, int16_t* d_offset_out, float* d_metres_out) {
+  return distance_dev(ctx, map, vmin, dims, params, false, d_d2_out, d_offset_out, d_metres_out);
+}
+int loamx_occupancy_distance_slice(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3],
+                                   const loamx_distance_params* params, uint16_t* d_d2_out, int16_t* d_offset_out, float* d_metres_out) {
+  return distance_dev(ctx, map, vmin, dims, params, true, d_d2_out, d_offset_out, d_metres_out);
+}
+int loamx_occupancy_distance_box_host(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3],
+                                      const loamx_distance_params* params, uint16_t* d2_out, int16_t* offset_out, float* metres_out) {
+  return distance_host(ctx, map, vmin, dims, params, false, d2_out, offset_out, metres_out);
+}
+int loamx_occupancy_distance_slice_host(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3],
+                                        const loamx_distance_params* params, uint16_t* d2_out, int16_t* offset_out, float* metres_out) {
+  return distance_host(ctx, map, vmin, dims, params, true, d2_out, offset_out, metres_out);
 }
 
 int loamx_occupancy_stats_read(loamx_ctx* ctx, const loamx_occupancy_map* map, loamx_occupancy_stats* out) {

@@ -648,6 +648,29 @@ struct OccBox {
 void launch_occupancy_box(const OccTable& t, const OccStateRule& sr, const OccBox& box, uint32_t* d_counts_out, uint8_t* d_state_out, hipStream_t s);
 void launch_occupancy_slice(const OccTable& t, const OccStateRule& sr, const OccBox& box, uint8_t* d_grid_out, hipStream_t s);
 
+/* ---- occupancy distance field (distance_kernels.hip; the rule: distance_math.h and loamx.h) ----------------------------------------- */
+constexpr uint32_t kRegFlagNoDistanceEarlyExit = 8388608u;  // (loamx_ctx::reg_flags) the y- and z-pass walk the whole window of +-R
+// a call's box and what follows from it: the extended box e = dims + 2R (a slice: e[2] = 1, its columns take their state over
+// `levels` levels) and W, the 64-bit mask words of a row
+struct DistGeom {
+  int32_t vmin[3];
+  uint32_t dims[3];
+  uint32_t e[3];
+  uint32_t R, W, levels;
+  uint32_t unknown_is_obstacle, slice;
+};
+DistGeom make_dist_geom(const int32_t* vmin, const uint32_t* dims, uint32_t R, bool unknown_is_obstacle, bool slice);
+// the staging of a call in one block: the mask, the x-pass's offsets, the y-pass's dwords (a box only)
+struct DistStaging {
+  unsigned long long* mask;  // [e[2] e[1]][W]
+  int16_t* dx;               // [e[2] e[1]][dims[0]]
+  uint32_t* dxy;             // [e[2]][dims[1]][dims[0]]
+};
+DistStaging dist_staging_carve(void* block, const DistGeom& g, size_t* bytes);  // (block may be nullptr: only the size is wanted)
+// mask, x, y (and z) on a box with no dimension of 0; each output may be nullptr. The table is only read.
+void launch_distance(const OccTable& t, const OccStateRule& sr, double leaf, const DistGeom& g, const DistStaging& w, bool early, uint16_t* d_d2_out,
+                     int16_t* d_offset_out, float* d_metres_out, hipStream_t s);
+
 /* ---- surfel map (surfel_kernels.hip; the rule: surfel_math.h and loamx.h) ----------------------------------------------------------- */
 constexpr uint32_t kRegFlagNoSurfelCombine = 2097152u;  // (loamx_ctx::reg_flags) one claim per point, no run combining
 constexpr uint32_t kSurfelSlotWords = 12;               // 64-bit sums of a slot: s[3], S[6], W[3] (surfel_math.h: kSurfelMoments)

@@ -4,6 +4,7 @@
 // on that ray alone: every schedule, every split over workgroups and every batch split leaves the same bytes. No launch waits for
 // another workgroup, and every loop has a bound that is known before it starts.
 #include "loamx_internal.h"
+#include "occupancy_read.h"
 #include "voxel_table.h"
 
 namespace loamx {
@@ -100,12 +101,7 @@ __global__ __launch_bounds__(kOccThreads) void occupancy_walk_kernel(const T* __
   }
 }
 
-/* ---- read-outs: plain loads, behind the walks on the same stream ------------------------------------------------------------ */
-// the count word of a voxel, 0 without a slot
-__device__ __forceinline__ unsigned long long occ_lookup(const OccTable& t, uint64_t key) {
-  const uint32_t s = voxel_find(t.keys, t.log2_cap, key);
-  return s != kMapNoSlot ? t.counts[s] : 0ull;
-}
+/* ---- read-outs: plain loads, behind the walks on the same stream (occ_lookup, occ_box_key: occupancy_read.h) ----------------- */
 __device__ __forceinline__ void occ_write(unsigned long long word, const OccStateRule& sr, unsigned long long i, uint32_t* __restrict__ counts_out,
                                           uint8_t* __restrict__ state_out) {
   const uint32_t hits = (uint32_t)(word >> 32), passes = (uint32_t)word;
@@ -122,14 +118,6 @@ __global__ __launch_bounds__(kOccThreads) void occupancy_query_kernel(OccTable t
   uint32_t u[3];
   const bool ok = cloud_cell(load_point_strided(pts, i, stride), leaf, key, u);
   occ_write(ok ? occ_lookup(t, key) : 0ull, sr, i, counts_out, state_out);
-}
-
-// the key of voxel vmin + (x, y, z); false outside |v| < 2^20
-__device__ __forceinline__ bool occ_box_key(const OccBox& box, uint32_t x, uint32_t y, uint32_t z, uint64_t& key) {
-  const long long vx = (long long)box.vmin[0] + x, vy = (long long)box.vmin[1] + y, vz = (long long)box.vmin[2] + z;
-  const bool ok = vx > -1048576ll && vx < 1048576ll && vy > -1048576ll && vy < 1048576ll && vz > -1048576ll && vz < 1048576ll;
-  key = ok ? voxel_pack((uint64_t)(vx + 1048576ll), (uint64_t)(vy + 1048576ll), (uint64_t)(vz + 1048576ll)) : 0ull;
-  return ok;
 }
 
 __global__ __launch_bounds__(kOccThreads) void occupancy_box_kernel(OccTable t, OccStateRule sr, OccBox box, uint32_t* __restrict__ counts_out,

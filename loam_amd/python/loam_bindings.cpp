@@ -226,6 +226,27 @@ inline void occupancy_box_args(const std::array<int64_t, 3>& vmin, const std::ar
     v[a] = (int32_t)vmin[a], d[a] = (uint32_t)dims[a];
   }
 }
+// OccupancyMap.distanceBox / distanceSlice: (d2, offset, metres) shaped like box() / slice()
+inline py::tuple occupancy_distance(loam::OccupancyMap& map, const std::array<int64_t, 3>& vmin, const std::array<int64_t, 3>& dims,
+                                    const loam::DistanceParams& params, bool slice) {
+  std::array<int32_t, 3> v;
+  std::array<uint32_t, 3> d;
+  occupancy_box_args(vmin, dims, v, d);
+  std::vector<py::ssize_t> shape{(py::ssize_t)d[1], (py::ssize_t)d[0]};
+  if (!slice) shape.insert(shape.begin(), (py::ssize_t)d[2]);
+  std::vector<py::ssize_t> shape_off = shape;
+  shape_off.push_back(slice ? 2 : 3);
+  py::array_t<uint16_t> d2(shape);
+  py::array_t<int16_t> offset(shape_off);
+  py::array_t<float> metres(shape);
+  loamx_distance_params p;
+  loamx_default_distance_params(&p);
+  p.max_dist_voxels = params.max_dist_voxels, p.unknown_is_obstacle = params.unknown_is_obstacle ? 1u : 0u;
+  loamx_ctx* ctx = loam::gpu::defaultContext();
+  loam::gpu::check(ctx, (slice ? loamx_occupancy_distance_slice_host : loamx_occupancy_distance_box_host)(
+                            ctx, map.handle(), v.data(), d.data(), &p, d2.mutable_data(), offset.mutable_data(), metres.mutable_data()));
+  return py::make_tuple(d2, offset, metres);
+}
 template <typename T>
 py::tuple organize_cloud(const py::array_t<T, py::array::c_style>& points, const loam::ScanLayout& layout, const std::optional<ArrRings>& rings) {
   if (points.ndim() != 2 || points.shape(1) < 3) throw std::runtime_error("points: expected an (N, 3) or (N, 4) array");
@@ -890,7 +911,12 @@ PYBIND11_MODULE(loam_python, m) {
       .def_readwrite("min_hits", &loam::OccupancyParams::min_hits)
       .def_readwrite("occ_ratio", &loam::OccupancyParams::occ_ratio)
       .def_readwrite("min_passes", &loam::OccupancyParams::min_passes);
+  py::class_<loam::DistanceParams>(m, "DistanceParams")
+      .def(py::init<>())
+      .def_readwrite("max_dist_voxels", &loam::DistanceParams::max_dist_voxels)
+      .def_readwrite("unknown_is_obstacle", &loam::DistanceParams::unknown_is_obstacle);
   py::class_<loam::OccupancyMap> occupancy_map(m, "OccupancyMap");
+  occupancy_map.attr("DIST_FAR") = (int)loam::DistanceField::FAR;
   occupancy_map.attr("UNKNOWN") = (int)loam::Occupancy::UNKNOWN;
   occupancy_map.attr("FREE") = (int)loam::Occupancy::FREE;
   occupancy_map.attr("OCCUPIED") = (int)loam::Occupancy::OCCUPIED;
@@ -946,6 +972,18 @@ PYBIND11_MODULE(loam_python, m) {
             return grid;
           },
           py::arg("vmin"), py::arg("dims"))
+      .def(
+          "distanceBox",
+          [](loam::OccupancyMap& map, const std::array<int64_t, 3>& vmin, const std::array<int64_t, 3>& dims, const loam::DistanceParams& params) {
+            return occupancy_distance(map, vmin, dims, params, false);
+          },
+          py::arg("vmin"), py::arg("dims"), py::arg("params") = loam::DistanceParams())
+      .def(
+          "distanceSlice",
+          [](loam::OccupancyMap& map, const std::array<int64_t, 3>& vmin, const std::array<int64_t, 3>& dims, const loam::DistanceParams& params) {
+            return occupancy_distance(map, vmin, dims, params, true);
+          },
+          py::arg("vmin"), py::arg("dims"), py::arg("params") = loam::DistanceParams())
       .def("stats", [](const loam::OccupancyMap& map) {
         const loam::OccupancyStats s = map.stats();
         py::dict d;
