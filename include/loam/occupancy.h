@@ -4,7 +4,8 @@
  * grid: the voxel of the return counts a hit, every voxel in front of it a pass. A voxel is then occupied, free or unknown
  * (never seen), the distinction OctoMap provides. The counts are integers, so the map does not depend on how the device
  * schedules its threads or on how a drive is split into calls. It is read per point, as a dense box of voxels, or as the 2-D
- * grid a planner takes. The rule is written out in loamx.h ("occupancy map").
+ * grid a planner takes. The rule is written out in loamx.h ("occupancy map"). castRays and renderScans ask what a ray through the
+ * map meets first, and what scan the map predicts at a pose (loamx.h, "occupancy ray casting").
  */
 #pragma once
 #include <array>
@@ -62,6 +63,39 @@ struct DistanceField {
   std::vector<int16_t> offset;
   std::vector<float> metres;
   size_t size() const { return d2.size(); }
+};
+
+/// loamx_raycast_params; the defaults are loamx_default_raycast_params'
+struct RaycastParams {
+  enum HitAt : uint32_t { AT_ENTER = LOAMX_RAY_AT_ENTER, AT_MIDDLE = LOAMX_RAY_AT_MIDDLE };
+  uint32_t skip_start = 0;        ///< visits at the start of a ray that are walked but not tested (a ray that starts on a surface)
+  bool unknown_stops = false;     ///< a voxel never seen stops the ray (status UNKNOWN); otherwise it is counted and passed
+  uint32_t max_steps = 3 * 4098;  ///< the step cap, at most 2^22: a longer walk ends TRUNCATED
+  HitAt hit_at = AT_MIDDLE;       ///< renderScans only: the return lies where the beam enters the hit voxel, or half way through it
+};
+
+/// loamx_ray_record (loamx.h, "occupancy ray casting"): what a ray met first
+struct RayRecord {
+  enum Status : uint32_t {
+    CLEAR = LOAMX_RAY_CLEAR, HIT = LOAMX_RAY_HIT, UNKNOWN = LOAMX_RAY_UNKNOWN, TRUNCATED = LOAMX_RAY_TRUNCATED, OUTSIDE = LOAMX_RAY_OUTSIDE,
+    INVALID = LOAMX_RAY_INVALID
+  };
+  uint32_t status = CLEAR;
+  uint32_t visits = 0;                   ///< voxels visited, the last one included
+  std::array<int32_t, 3> voxel{0, 0, 0};  ///< the voxel the ray stopped or ended in
+  uint32_t n_unknown = 0;
+  double t_enter = 0.0, t_exit = 0.0;    ///< the parameters in [0, 1] at which the segment enters and leaves that voxel
+  bool hit() const { return status == HIT; }
+};
+static_assert(sizeof(RayRecord) == sizeof(loamx_ray_record), "RayRecord is loamx_ray_record");
+
+/// What OccupancyMap::renderScans returns: per pose and beam (entry pose n_beams + beam) the point in the sensor frame (packed
+/// x y z; (0, 0, 0) where nothing is hit: the "no return" cell of an organised scan), the range and the record
+struct RenderedScans {
+  size_t n_poses = 0, n_beams = 0;
+  std::vector<double> xyz;
+  std::vector<double> ranges;
+  std::vector<RayRecord> records;
 };
 
 /// The map (loamx_occupancy_map): table and counters on the device. Cheap to copy (shared handle).
@@ -136,6 +170,34 @@ class OccupancyMap {
   DistanceField distanceSlice(const std::array<int32_t, 3>& vmin, const std::array<uint32_t, 3>& dims, const DistanceParams& params = DistanceParams()) {
     return distance(loamx_occupancy_distance_slice_host, vmin, dims, params, (size_t)dims[0] * dims[1], 2);
   }
+  /// What each segment origins[i] -> ends[i] (map frame, packed x y z) meets first: OctoMap's castRay, for line-of-sight and
+  /// segment-collision checks
+  std::vector<RayRecord> castRays(const std::vector<double>& origins, const std::vector<double>& ends, const RaycastParams& params = RaycastParams()) const {
+    if (origins.size() != ends.size() || origins.size() % 3) throw std::invalid_argument("castRays: origins and ends are packed x y z of equal length");
+    loamx_ctx* ctx = gpu::defaultContext();
+    const loamx_raycast_params p = raycastParams(params);
+    std::vector<RayRecord> out(origins.size() / 3);
+    gpu::check(ctx, loamx_occupancy_cast_rays_host(ctx, handle_.get(), origins.data(), ends.data(), 3, out.size(), &p,
+                                                   reinterpret_cast<loamx_ray_record*>(out.data())));
+    return out;
+  }
+  /// The scans the map predicts at the poses (world_T_sensor) for the unit beam directions `dirs` (sensor frame, packed x y z, in
+  /// the scan's cell order), out to max_range. The range of a return is a voxel's entry or middle: quantised to the leaf.
+  RenderedScans renderScans(const std::vector<double>& dirs, const std::vector<Pose3d>& poses, double max_range,
+                            const RaycastParams& params = RaycastParams()) const {
+    if (dirs.size() % 3) throw std::invalid_argument("renderScans: dirs is packed x y z");
+    loamx_ctx* ctx = gpu::defaultContext();
+    const loamx_raycast_params p = raycastParams(params);
+    RenderedScans out;
+    out.n_poses = poses.size(), out.n_beams = dirs.size() / 3;
+    std::vector<double> packed(7 * poses.size());
+    for (size_t i = 0; i < poses.size(); i++) poses[i].toArray(packed.data() + 7 * i);
+    const size_t n = out.n_poses * out.n_beams;
+    out.xyz.resize(3 * n), out.ranges.resize(n), out.records.resize(n);
+    gpu::check(ctx, loamx_occupancy_render_scans_host(ctx, handle_.get(), dirs.data(), out.n_beams, packed.data(), out.n_poses, max_range, &p,
+                                                      out.xyz.data(), out.ranges.data(), reinterpret_cast<loamx_ray_record*>(out.records.data())));
+    return out;
+  }
   OccupancyStats stats() const {
     loamx_ctx* ctx = gpu::defaultContext();
     loamx_occupancy_stats s;
@@ -148,6 +210,12 @@ class OccupancyMap {
   loamx_occupancy_map* handle() const { return handle_.get(); }
 
  private:
+  static loamx_raycast_params raycastParams(const RaycastParams& params) {
+    loamx_raycast_params p;
+    loamx_default_raycast_params(&p);
+    p.skip_start = params.skip_start, p.unknown_stops = params.unknown_stops ? 1u : 0u, p.max_steps = params.max_steps, p.hit_at = params.hit_at;
+    return p;
+  }
   template <typename Fn>
   DistanceField distance(Fn fn, const std::array<int32_t, 3>& vmin, const std::array<uint32_t, 3>& dims, const DistanceParams& params, size_t n,
                          size_t axes) {

@@ -262,6 +262,7 @@ int loamx_ctx_last_assoc_coop_forms(loamx_ctx* ctx, int which_kind, uint32_t out
  *   map cleaning:  NO_VISIBILITY_RANGES (the votes kernel reads the scans' points, no first launch that writes every cell's squared range: the same bytes, see "map cleaning")
  *   occupancy map: NO_OCCUPANCY_COMBINE (one claim per visit instead of one per run of a wavefront: the same bytes, see "occupancy map")
  *   distance field: NO_DISTANCE_EARLY_EXIT (the y- and z-pass walk their whole window: the same bytes, see "occupancy distance field")
+ *   ray casting:   RAYCAST_COMBINE (one look-up per run of neighbouring lanes in the same voxel instead of one per lane: the same bytes, see "occupancy ray casting")
  *   surfel map:    NO_SURFEL_COMBINE (one claim per point instead of one per run of a wavefront: the same bytes, see "surfel map")
  *   localisation:  NO_LOCALIZE_PLANES (no plane cache, every candidate voxel finished where it is looked at: the same bytes, see "surfel localisation")
  * Unknown name: LOAMX_ERR_BAD_PARAM.
@@ -1343,6 +1344,87 @@ int loamx_occupancy_distance_box_host(loamx_ctx* ctx, loamx_occupancy_map* map, 
                                       const loamx_distance_params* params, uint16_t* d2_out, int16_t* offset_out, float* metres_out);
 int loamx_occupancy_distance_slice_host(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t vmin[3], const uint32_t dims[3],
                                         const loamx_distance_params* params, uint16_t* d2_out, int16_t* offset_out, float* metres_out);
+
+/* ---- occupancy ray casting (no reference counterpart; OctoMap's castRay). "What does a ray from here meet first?": line of sight
+ * and segment collision for a planner, and the scan the map predicts at a pose, to lay beside the scan that arrived. A ray is a
+ * segment from o to e in the map frame, three doubles each. The result is integer or individually rounded FP64 and depends on that
+ * ray alone, so every schedule gives the same bytes and a Python model is compared by equality (tests/raycast_common.py). The rule
+ * is executable in loam_amd/csrc/raycast_math.h (host + device); tests/hostcheck_raycast compares a g++ build of it with the model.
+ * FP64 throughout; every product, quotient, sum and difference is one operation rounded on its own; no libm call.
+ *   1 validity   a coordinate of o or e that is not finite: status INVALID, no walk.
+ *   2 walk       step 4 of the occupancy map on (o, e), unchanged: the same set-up, the same pick, the same ties. A voxel coordinate
+ *                of o or e outside |v| < 2^20: status OUTSIDE, no walk. Otherwise the start voxel is visit 0 and up to
+ *                rem[0] + rem[1] + rem[2] steps follow.
+ *   3 parameters t_enter of visit 0 is 0.0; of every other visit it is the tMax that was picked in the step that led into the
+ *                voxel, before that step advanced it. t_exit of a visit is the smallest tMax among the axes with rem > 0 on arrival,
+ *                1.0 if no axis has steps left. So t_exit of visit k and t_enter of visit k + 1 are the same double.
+ *   4 test       visits with index < skip_start are walked but not tested (a ray that starts on a surface). For every other visit
+ *                the voxel's count word is read (a voxel without a slot: (0, 0)) and step 5 of the occupancy map gives its state
+ *                under the map's own thresholds. OCCUPIED: stop, status HIT. UNKNOWN with unknown_stops != 0: stop, status UNKNOWN.
+ *                UNKNOWN with unknown_stops == 0: n_unknown += 1 and on. FREE: on.
+ *   5 cap        the walk takes at most max_steps steps (default 3 x 4098, the bound of a walk of the map's own add; above 2^22:
+ *                LOAMX_ERR_UNSUPPORTED). A visit that did not stop with no step left in the walk: status CLEAR (the ray ended in
+ *                e's voxel). Otherwise, with the cap used up: status TRUNCATED. Segment lengths are device data that the host
+ *                cannot refuse; the cap is what bounds a lane's time.
+ *   6 record     40 bytes, every byte written for every ray: status, visits (voxels visited, the last one included), the voxel the
+ *                ray stopped or ended in, n_unknown, t_enter and t_exit of that voxel. OUTSIDE and INVALID: zeros behind the status.
+ * Rendered scans. d_dirs: n_beams x 3 doubles, the unit directions of the beams in the sensor frame in the scan's cell order; the
+ *   caller supplies them (the scan layout stores cell boundaries, not centres), so no cos or sin runs in the library. d_poses:
+ *   n_poses x 7 in DEVICE memory (qx qy qz qw tx ty tz). Beam b of pose i is the segment from o = t_i to
+ *   e = pose_i.act((max_range d.x, max_range d.y, max_range d.z)), cast by the rule above; a pose with an entry that is not finite
+ *   makes all of its beams INVALID. On HIT tau = t_enter (LOAMX_RAY_AT_ENTER) or 0.5 * (t_enter + t_exit) (LOAMX_RAY_AT_MIDDLE),
+ *   range = tau * max_range and the point is (range d.x, range d.y, range d.z) in the sensor frame. Every other status: range 0 and
+ *   the point (+0, +0, +0), the "no return" cell of the organiser, so d_scans_out (n_poses x n_beams x 3 doubles) goes straight
+ *   into the extraction, the place descriptors and the visibility votes. The range is a voxel's entry or middle: it is quantised
+ *   to the leaf. hit_at is used by this form only.
+ * Kernels (loam_amd/csrc/raycast_kernels.hip). One ray per lane, 256 threads; the lanes of a wavefront are neighbouring rays or
+ *   beams in input order, and the wavefront loops while any lane has a voxel to visit. In every trip every lane that tests its
+ *   voxel looks it up. Context option RAYCAST_COMBINE: runs of neighbouring lanes that test the same voxel make ONE look-up, the
+ *   head of the run probes the table and the others take the count word from it; the same bytes, only `probes` differs. Measured,
+ *   the two forms are level and the plain one a little faster, so it is the default. The table is only
+ *   read. Both device forms enqueue on the context's stream and return; nothing is read back. A refused call writes nothing.
+ * Census. loamx_ctx_last_raycast_census reads back (it synchronises) the counters of the context's last cast or render call:
+ *   rays, visits (the TESTED visits: those that needed a count word), probes (look-ups made: equal to visits without combining),
+ *   and the rays by status. A call with no ray leaves all zero.
+ * LOAMX_ERR_BAD_PARAM: a null map or params, a map of another context, null origins, ends or records with n > 0, stride < 3,
+ *   an unknown hit_at; the render: null d_dirs or d_poses with rays, max_range not finite or <= 0. LOAMX_ERR_UNSUPPORTED:
+ *   max_steps > 2^22, n > 2^31 (the render: n_poses x n_beams > 2^31), a stride beyond 32 bits. No ray: LOAMX_OK, nothing written. */
+enum { LOAMX_RAY_CLEAR = 0, LOAMX_RAY_HIT = 1, LOAMX_RAY_UNKNOWN = 2, LOAMX_RAY_TRUNCATED = 3, LOAMX_RAY_OUTSIDE = 4, LOAMX_RAY_INVALID = 5 };
+enum { LOAMX_RAY_AT_ENTER = 0, LOAMX_RAY_AT_MIDDLE = 1 };
+typedef struct {
+  uint32_t skip_start;    /* 0 */
+  uint32_t unknown_stops; /* 0 */
+  uint32_t max_steps;     /* 3 x 4098 */
+  uint32_t hit_at;        /* LOAMX_RAY_AT_MIDDLE */
+} loamx_raycast_params;
+typedef struct {
+  uint32_t status; /* LOAMX_RAY_* */
+  uint32_t visits;
+  int32_t voxel[3];
+  uint32_t n_unknown;
+  double t_enter, t_exit;
+} loamx_ray_record;
+typedef struct {
+  uint64_t rays, visits, probes;
+  uint64_t hit, unknown, clear, truncated, outside, invalid;
+} loamx_raycast_census;
+void loamx_default_raycast_params(loamx_raycast_params* p);
+/* n segments in DEVICE memory, segment i from d_origins + i stride to d_ends + i stride (doubles); one record each */
+int loamx_occupancy_cast_rays(loamx_ctx* ctx, const loamx_occupancy_map* map, const double* d_origins, const double* d_ends, size_t stride, size_t n,
+                              const loamx_raycast_params* params, loamx_ray_record* d_records_out /* [n] */);
+/* the expected scans of the map: ray (i, b) at index i n_beams + b of every output; each output may be NULL */
+int loamx_occupancy_render_scans(loamx_ctx* ctx, const loamx_occupancy_map* map, const double* d_dirs /* [n_beams][3] */, size_t n_beams,
+                                 const double* d_poses /* [n_poses][7] */, size_t n_poses, double max_range, const loamx_raycast_params* params,
+                                 double* d_scans_out /* [n_poses][n_beams][3] */, double* d_ranges_out /* [n_poses][n_beams] */,
+                                 loamx_ray_record* d_records_out /* [n_poses][n_beams] */);
+/* host forms, synchronous: host arrays in and out */
+int loamx_occupancy_cast_rays_host(loamx_ctx* ctx, const loamx_occupancy_map* map, const double* origins, const double* ends, size_t stride, size_t n,
+                                   const loamx_raycast_params* params, loamx_ray_record* records_out);
+int loamx_occupancy_render_scans_host(loamx_ctx* ctx, const loamx_occupancy_map* map, const double* dirs, size_t n_beams, const double* poses,
+                                      size_t n_poses, double max_range, const loamx_raycast_params* params, double* scans_out, double* ranges_out,
+                                      loamx_ray_record* records_out);
+/* synchronises */
+int loamx_ctx_last_raycast_census(loamx_ctx* ctx, loamx_raycast_census* out);
 
 /* ---- surfel map (no reference counterpart; the per-voxel Gaussians of NDT, the surfels of a point-to-plane map). What the
  * consumers of a map need beyond a centroid: per voxel the mean, the covariance, its eigenvalues and the normal, turned towards

@@ -351,6 +351,58 @@ class DistanceParams:
         return DistanceParamsStruct(int(self.max_dist_voxels), 1 if self.unknown_is_obstacle else 0)
 
 
+class RaycastParamsStruct(C.Structure):
+    """loamx_raycast_params (include/loamx.h)"""
+    _fields_ = [("skip_start", C.c_uint32), ("unknown_stops", C.c_uint32), ("max_steps", C.c_uint32), ("hit_at", C.c_uint32)]
+
+
+# LOAMX_RAY_*: the status of a ray, and where on the hit voxel a rendered return lies
+RAY_CLEAR, RAY_HIT, RAY_UNKNOWN, RAY_TRUNCATED, RAY_OUTSIDE, RAY_INVALID = range(6)
+RAY_AT_ENTER, RAY_AT_MIDDLE = 0, 1
+# loamx_ray_record (40 bytes) and loamx_raycast_census
+RAY_RECORD_DTYPE = np.dtype([("status", np.uint32), ("visits", np.uint32), ("voxel", np.int32, 3), ("n_unknown", np.uint32),
+                             ("t_enter", np.float64), ("t_exit", np.float64)])
+RAYCAST_CENSUS_DTYPE = np.dtype([(n, np.uint64) for n in ("rays", "visits", "probes", "hit", "unknown", "clear", "truncated", "outside", "invalid")])
+
+
+class RaycastParams:
+    """The rule of a ray cast through an occupancy map (loamx_raycast_params): visits at the start that are walked but not tested,
+    whether an UNKNOWN voxel stops a ray, the step cap, and where on the hit voxel a rendered return lies (RAY_AT_ENTER /
+    RAY_AT_MIDDLE). Anything left out takes the C ABI's default."""
+    NAMES = ("skip_start", "unknown_stops", "max_steps", "hit_at")
+
+    def __init__(self, skip_start=None, unknown_stops=None, max_steps=None, hit_at=None):
+        d = RaycastParamsStruct()
+        load().loamx_default_raycast_params(C.byref(d))
+        given = dict(skip_start=skip_start, unknown_stops=unknown_stops, max_steps=max_steps, hit_at=hit_at)
+        for name in self.NAMES:
+            setattr(self, name, getattr(d, name) if given[name] is None else given[name])
+
+    def struct(self):
+        for name in self.NAMES:
+            if not 0 <= int(getattr(self, name)) <= 0xFFFFFFFF:
+                raise ValueError(f"RaycastParams: {name} does not fit 32 bits")
+        return RaycastParamsStruct(int(self.skip_start), 1 if self.unknown_stops else 0, int(self.max_steps), int(self.hit_at))
+
+
+def beam_directions(scan_lines, points_per_line, organize_params=None):
+    """(scan_lines * points_per_line, 3) float64: the unit directions of the CENTRES of a scan layout's cells, in cell order (line
+    major), for OccupancyMap.render_scans. Column c is centred on azimuth_zero + sgn 2 pi c / W (its boundaries lie half a column to
+    either side: loamx_organize_params), line l on its elevation: the given elevations, or linear from fov_bottom to fov_top."""
+    o = organize_params or OrganizeParams()
+    H, W = int(scan_lines), int(points_per_line)
+    if o.elevations is not None:
+        if o.elevations.size != H:
+            raise ValueError(f"beam_directions: {o.elevations.size} elevations for {H} scan lines")
+        el = o.elevations.astype(np.float64)
+    else:
+        el = np.array([o.fov_bottom + (o.fov_top - o.fov_bottom) * l / (H - 1) if H > 1 else 0.5 * (o.fov_bottom + o.fov_top) for l in range(H)])
+    az = o.azimuth_zero + (-1.0 if o.clockwise else 1.0) * (2.0 * np.pi * np.arange(W) / W)
+    d = np.stack([np.cos(el)[:, None] * np.cos(az)[None, :], np.cos(el)[:, None] * np.sin(az)[None, :],
+                  np.sin(el)[:, None] * np.ones(W)[None, :]], axis=-1).reshape(H * W, 3)
+    return np.ascontiguousarray(d / np.linalg.norm(d, axis=1)[:, None])
+
+
 class SegmentParamsStruct(C.Structure):
     """loamx_segment_params (include/loamx.h)"""
     _fields_ = [("ground_lines", C.c_uint64), ("ground_angle", C.c_double), ("segment_angle", C.c_double),
@@ -535,6 +587,8 @@ EXPORTS = [
     "loamx_cloud_map_crop", "loamx_surfel_map_crop", "loamx_occupancy_crop",
     "loamx_default_distance_params", "loamx_occupancy_distance_box", "loamx_occupancy_distance_slice",
     "loamx_occupancy_distance_box_host", "loamx_occupancy_distance_slice_host",
+    "loamx_default_raycast_params", "loamx_occupancy_cast_rays", "loamx_occupancy_render_scans", "loamx_occupancy_cast_rays_host",
+    "loamx_occupancy_render_scans_host", "loamx_ctx_last_raycast_census",
 ]
 
 # bits of loamx_ctx_last_extract_route (include/loamx.h: LOAMX_ROUTE_*), in bit order
@@ -807,6 +861,13 @@ def load(build_if_missing=True):
     for name in ("loamx_occupancy_distance_box", "loamx_occupancy_distance_slice", "loamx_occupancy_distance_box_host",
                  "loamx_occupancy_distance_slice_host"):
         getattr(lib, name).argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(DistanceParamsStruct), vp, vp, vp]
+    lib.loamx_default_raycast_params.argtypes = [C.POINTER(RaycastParamsStruct)]
+    lib.loamx_default_raycast_params.restype = None
+    lib.loamx_occupancy_cast_rays.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, C.POINTER(RaycastParamsStruct), vp]
+    lib.loamx_occupancy_cast_rays_host.argtypes = lib.loamx_occupancy_cast_rays.argtypes
+    lib.loamx_occupancy_render_scans.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_double, C.POINTER(RaycastParamsStruct), vp, vp, vp]
+    lib.loamx_occupancy_render_scans_host.argtypes = lib.loamx_occupancy_render_scans.argtypes
+    lib.loamx_ctx_last_raycast_census.argtypes = [vp, vp]
     lib.loamx_occupancy_stats_read.argtypes = [vp, vp, vp]
     lib.loamx_occupancy_claims_read.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
     lib.loamx_occupancy_add_cloud.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
@@ -1390,6 +1451,53 @@ class OccupancyMap(_VoxelMap):
     def distance_slice(self, vmin, dims, params=None):
         """(d2 (dy, dx) uint16, offset (dy, dx, 2) int16, metres (dy, dx) float32) of the box's columns"""
         return self._distance_host("distance_slice", vmin, dims, params, (int(dims[1]), int(dims[0])), 2)
+
+    def cast_rays_dev(self, d_origins, d_ends, stride, n, d_records_out, params=None):
+        """n device-resident segments (double, map frame, `stride` doubles apart) cast through the map (include/loamx.h, "occupancy
+        ray casting"): one RAY_RECORD_DTYPE record each to a device address (loamx_occupancy_cast_rays). Asynchronous."""
+        if int(stride) < 0 or int(n) < 0:
+            raise ValueError("cast_rays_dev: stride or n is negative")
+        st = (params or RaycastParams()).struct()
+        self.ctx._check(self.ctx.lib.loamx_occupancy_cast_rays(self.ctx.h, self._handle(), d_origins or None, d_ends or None, int(stride), int(n),
+                                                               C.byref(st), d_records_out or None))
+
+    def cast_rays(self, origins, ends, params=None):
+        """host segments origins -> ends, (n, k >= 3) each with the same k -> (n,) RAY_RECORD_DTYPE records"""
+        o, e = np.ascontiguousarray(origins, dtype=np.float64), np.ascontiguousarray(ends, dtype=np.float64)
+        if o.ndim != 2 or o.shape[1] < 3 or o.shape != e.shape:
+            raise ValueError(f"cast_rays: origins and ends must both be (n, 3) or (n, k >= 3), not {o.shape} and {e.shape}")
+        st = (params or RaycastParams()).struct()
+        out = np.zeros(len(o), dtype=RAY_RECORD_DTYPE)
+        self.ctx._check(self.ctx.lib.loamx_occupancy_cast_rays_host(self.ctx.h, self._handle(), o.ctypes.data, e.ctypes.data, o.shape[1], len(o),
+                                                                    C.byref(st), out.ctypes.data))
+        return out
+
+    def render_scans_dev(self, d_dirs, n_beams, d_poses, n_poses, max_range, params=None, d_scans_out=0, d_ranges_out=0, d_records_out=0):
+        """the scans the map predicts at n_poses device-resident poses (n_poses x 7) for n_beams unit beam directions (n_beams x 3,
+        sensor frame, cell order: beam_directions) to device addresses, each 0 = not wanted: points (double [n_poses][n_beams][3],
+        (0, 0, 0) where nothing is hit), ranges (double) and records (loamx_occupancy_render_scans). Asynchronous."""
+        if int(n_beams) < 0 or int(n_poses) < 0:
+            raise ValueError("render_scans_dev: n_beams or n_poses is negative")
+        st = (params or RaycastParams()).struct()
+        self.ctx._check(self.ctx.lib.loamx_occupancy_render_scans(self.ctx.h, self._handle(), d_dirs or None, int(n_beams), d_poses or None, int(n_poses),
+                                                                  float(max_range), C.byref(st), d_scans_out or None, d_ranges_out or None,
+                                                                  d_records_out or None))
+
+    def render_scans(self, dirs, poses, max_range, params=None, scans=True, ranges=True, records=True):
+        """host beam directions (n_beams, 3) and poses (n_poses, 7) -> (scans (n_poses, n_beams, 3), ranges (n_poses, n_beams),
+        records (n_poses, n_beams) RAY_RECORD_DTYPE); an output that is not wanted is None"""
+        d, p = np.ascontiguousarray(dirs, dtype=np.float64), np.ascontiguousarray(poses, dtype=np.float64)
+        if d.ndim != 2 or d.shape[1] != 3 or p.ndim != 2 or p.shape[1] != 7:
+            raise ValueError(f"render_scans: dirs must be (n_beams, 3) and poses (n_poses, 7), not {d.shape} and {p.shape}")
+        st = (params or RaycastParams()).struct()
+        shape = (len(p), len(d))
+        out_s = np.zeros(shape + (3,), dtype=np.float64) if scans else None
+        out_r = np.zeros(shape, dtype=np.float64) if ranges else None
+        out_k = np.zeros(shape, dtype=RAY_RECORD_DTYPE) if records else None
+        self.ctx._check(self.ctx.lib.loamx_occupancy_render_scans_host(
+            self.ctx.h, self._handle(), d.ctypes.data, len(d), p.ctypes.data, len(p), float(max_range), C.byref(st),
+            out_s.ctypes.data if scans else None, out_r.ctypes.data if ranges else None, out_k.ctypes.data if records else None))
+        return out_s, out_r, out_k
 
     def stats(self):
         """one OCCUPANCY_STATS_DTYPE record (loamx_occupancy_stats_read; synchronises)"""
@@ -2142,6 +2250,13 @@ class Context:
         self._check(fn(self.h, a.ctypes.data, C.byref(lidar), C.byref(st), classes.ctypes.data, labels.ctypes.data, sizes.ctypes.data,
                        filtered.ctypes.data, clusters.ctypes.data, cells, stats.ctypes.data))
         return classes, labels, sizes, filtered, clusters[:int(stats[7])].copy(), stats
+
+    def last_raycast_census(self):
+        """one RAYCAST_CENSUS_DTYPE record of the context's last cast_rays / render_scans call: rays, tested visits, look-ups made
+        and the rays by status (loamx_ctx_last_raycast_census; synchronises)"""
+        c = np.zeros(1, dtype=RAYCAST_CENSUS_DTYPE)
+        self._check(self.lib.loamx_ctx_last_raycast_census(self.h, c.ctypes.data))
+        return c[0]
 
     def last_segment_census(self):
         """The last segmentation call of this context (loamx_ctx_last_segment_census): tile shape, tiles per scan, the connected

@@ -39,7 +39,8 @@ const OptionName kOptionNames[] = {
     {"NO_LIVE_DEAL", false, kRegFlagNoLiveDeal}, {"NO_CLOUDMAP_COMBINE", false, kRegFlagNoCloudmapCombine},
     {"NO_SEGMENT_TILES", false, kRegFlagNoSegmentTiles}, {"NO_VISIBILITY_RANGES", false, kRegFlagNoVisibilityRanges},
     {"NO_OCCUPANCY_COMBINE", false, kRegFlagNoOccupancyCombine}, {"NO_SURFEL_COMBINE", false, kRegFlagNoSurfelCombine},
-    {"NO_LOCALIZE_PLANES", false, kRegFlagNoLocalizePlanes}, {"NO_DISTANCE_EARLY_EXIT", false, kRegFlagNoDistanceEarlyExit}};
+    {"NO_LOCALIZE_PLANES", false, kRegFlagNoLocalizePlanes}, {"NO_DISTANCE_EARLY_EXIT", false, kRegFlagNoDistanceEarlyExit},
+    {"RAYCAST_COMBINE", false, kRegFlagRaycastCombine}};
 
 }  // namespace
 

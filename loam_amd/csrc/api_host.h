@@ -29,7 +29,7 @@ enum WsId {
   WS_CLOUD_IN, WS_CLOUD_POSE, WS_CLOUD_OUT,
   WS_SEG_BYTES, WS_SEG_WORDS, WS_SEG_COUNTS, WS_SEG_IN, WS_SEG_OUT,
   WS_VIS_RANGES, WS_VIS_CENSUS, WS_VIS_KEEP, WS_VIS_TILES, WS_VIS_IN, WS_VIS_SCANS, WS_VIS_POSES, WS_VIS_OUT,
-  WS_OCC_IN, WS_OCC_POSE, WS_OCC_OUT,
+  WS_OCC_IN, WS_OCC_POSE, WS_OCC_OUT, WS_RAY_CENSUS,
   WS_SURFEL_IN, WS_SURFEL_POSE, WS_SURFEL_OUT,
   WS_LOC_IN, WS_LOC_POSE, WS_LOC_OUT,
   WS_COUNT
@@ -111,6 +111,12 @@ struct loamx_ctx {
     bool valid = false, counted = false;  // counted: kernels ran and left the words (otherwise both counts are 0)
     uint32_t form = 0, scan_chunks = 0;
   } last_visibility;
+
+  // the last ray cast or render call (loamx_ctx_last_raycast_census): its counters are the words of WS_RAY_CENSUS
+  struct {
+    bool counted = false;  // a kernel ran and left the words (otherwise every count is 0)
+    uint64_t rays = 0;
+  } last_raycast;
 
   unsigned long long sweep_slots_base[2] = {0, 0};
   unsigned long long features_base = 0;  // events[2] at the last loamx_ctx_reset_kernel_stats

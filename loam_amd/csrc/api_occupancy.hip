@@ -1,17 +1,8 @@
 // api_occupancy.hip — the occupancy map (loamx.h, "occupancy map"): the map handle with its one device block (table and counters),
 // the add, clear, query, box, slice and stats entry points and their host forms, and the distance field of a box or slice
 // (loamx.h, "occupancy distance field") with the staging the handle keeps for it.
-#include "api_voxelmap.h"
+#include "api_occupancy.h"
 #include "distance_math.h"
-
-struct loamx_occupancy_map : loamx::VoxelMapBase {  // ones: keys; zeros: counts and counters
-  loamx_occupancy_params params = {};
-  loamx::OccRule rule = {};
-  loamx::OccStateRule state_rule = {};
-  loamx::OccTable t = {};
-  void* dist_block = nullptr;  // the staging of the distance field, allocated at the first distance call, grown when one needs more
-  size_t dist_bytes = 0;
-};
 
 using namespace loamx;
 
@@ -166,6 +157,8 @@ int distance_host(loamx_ctx* ctx, loamx_occupancy_map* map, const int32_t* vmin,
 }
 
 }  // namespace
+
+int loamx::occupancy_map_check(loamx_ctx* ctx, const loamx_occupancy_map* map) { return voxel_map_check(ctx, map, kKind); }
 
 extern "C" {
 

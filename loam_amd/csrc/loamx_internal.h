@@ -15,6 +15,7 @@
 #include "segment_math.h"
 #include "visibility_math.h"
 #include "occupancy_math.h"
+#include "raycast_math.h"
 #include "xcd_map.h"
 
 namespace loamx {
@@ -670,6 +671,18 @@ DistStaging dist_staging_carve(void* block, const DistGeom& g, size_t* bytes);  
 // mask, x, y (and z) on a box with no dimension of 0; each output may be nullptr. The table is only read.
 void launch_distance(const OccTable& t, const OccStateRule& sr, double leaf, const DistGeom& g, const DistStaging& w, bool early, uint16_t* d_d2_out,
                      int16_t* d_offset_out, float* d_metres_out, hipStream_t s);
+
+/* ---- occupancy ray casting (raycast_kernels.hip; the rule: raycast_math.h and loamx.h) ------------------------------------------------- */
+constexpr uint32_t kRegFlagRaycastCombine = 16777216u;  // (loamx_ctx::reg_flags) one look-up per run of lanes in the same voxel; unset: every lane its own
+// counter words of a call (the rays are the host's): tested visits, look-ups, then the rays by status in the order of LOAMX_RAY_*
+enum { kRayWordVisits = 0, kRayWordProbes = 1, kRayWordStatus = 2, kRayCensusWords = kRayWordStatus + kRayStatuses };
+// n > 0 segments origin -> end, `stride` doubles apart: one record each. The table is only read; d_census is added to.
+void launch_raycast(const OccTable& t, double leaf, const OccStateRule& sr, const RayRule& rule, const double* d_origins, const double* d_ends,
+                    uint32_t stride, unsigned long long n, RayRecord* d_records, unsigned long long* d_census, bool combine, hipStream_t s);
+// the n_beams beams of d_dirs at each of n_poses poses (n_poses n_beams > 0 rays, pose-major); each output may be nullptr
+void launch_raycast_render(const OccTable& t, double leaf, const OccStateRule& sr, const RayRule& rule, const double* d_dirs, uint32_t n_beams,
+                           const double* d_poses, unsigned long long n_poses, double max_range, double* d_scans, double* d_ranges,
+                           RayRecord* d_records, unsigned long long* d_census, bool combine, hipStream_t s);
 
 /* ---- surfel map (surfel_kernels.hip; the rule: surfel_math.h and loamx.h) ----------------------------------------------------------- */
 constexpr uint32_t kRegFlagNoSurfelCombine = 2097152u;  // (loamx_ctx::reg_flags) one claim per point, no run combining

@@ -226,6 +226,20 @@ inline void occupancy_box_args(const std::array<int64_t, 3>& vmin, const std::ar
     v[a] = (int32_t)vmin[a], d[a] = (uint32_t)dims[a];
   }
 }
+// the numpy dtype of loamx_ray_record (40 bytes) and the C struct of a RaycastParams
+inline py::dtype ray_record_dtype() {
+  py::list fields;
+  fields.append(py::make_tuple("status", "<u4")), fields.append(py::make_tuple("visits", "<u4"));
+  fields.append(py::make_tuple("voxel", "<i4", py::make_tuple(3))), fields.append(py::make_tuple("n_unknown", "<u4"));
+  fields.append(py::make_tuple("t_enter", "<f8")), fields.append(py::make_tuple("t_exit", "<f8"));
+  return py::dtype::from_args(fields);
+}
+inline loamx_raycast_params raycast_params(const loam::RaycastParams& params) {
+  loamx_raycast_params p;
+  loamx_default_raycast_params(&p);
+  p.skip_start = params.skip_start, p.unknown_stops = params.unknown_stops ? 1u : 0u, p.max_steps = params.max_steps, p.hit_at = params.hit_at;
+  return p;
+}
 // OccupancyMap.distanceBox / distanceSlice: (d2, offset, metres) shaped like box() / slice()
 inline py::tuple occupancy_distance(loam::OccupancyMap& map, const std::array<int64_t, 3>& vmin, const std::array<int64_t, 3>& dims,
                                     const loam::DistanceParams& params, bool slice) {
@@ -915,8 +929,20 @@ PYBIND11_MODULE(loam_python, m) {
       .def(py::init<>())
       .def_readwrite("max_dist_voxels", &loam::DistanceParams::max_dist_voxels)
       .def_readwrite("unknown_is_obstacle", &loam::DistanceParams::unknown_is_obstacle);
+  py::class_<loam::RaycastParams>(m, "RaycastParams")
+      .def(py::init<>())
+      .def_readwrite("skip_start", &loam::RaycastParams::skip_start)
+      .def_readwrite("unknown_stops", &loam::RaycastParams::unknown_stops)
+      .def_readwrite("max_steps", &loam::RaycastParams::max_steps)
+      .def_property(
+          "hit_at", [](const loam::RaycastParams& p) { return (uint32_t)p.hit_at; },
+          [](loam::RaycastParams& p, uint32_t v) { p.hit_at = static_cast<loam::RaycastParams::HitAt>(v); });
   py::class_<loam::OccupancyMap> occupancy_map(m, "OccupancyMap");
   occupancy_map.attr("DIST_FAR") = (int)loam::DistanceField::FAR;
+  occupancy_map.attr("RAY_CLEAR") = (int)loam::RayRecord::CLEAR, occupancy_map.attr("RAY_HIT") = (int)loam::RayRecord::HIT;
+  occupancy_map.attr("RAY_UNKNOWN") = (int)loam::RayRecord::UNKNOWN, occupancy_map.attr("RAY_TRUNCATED") = (int)loam::RayRecord::TRUNCATED;
+  occupancy_map.attr("RAY_OUTSIDE") = (int)loam::RayRecord::OUTSIDE, occupancy_map.attr("RAY_INVALID") = (int)loam::RayRecord::INVALID;
+  occupancy_map.attr("RAY_AT_ENTER") = (int)loam::RaycastParams::AT_ENTER, occupancy_map.attr("RAY_AT_MIDDLE") = (int)loam::RaycastParams::AT_MIDDLE;
   occupancy_map.attr("UNKNOWN") = (int)loam::Occupancy::UNKNOWN;
   occupancy_map.attr("FREE") = (int)loam::Occupancy::FREE;
   occupancy_map.attr("OCCUPIED") = (int)loam::Occupancy::OCCUPIED;
@@ -984,6 +1010,36 @@ PYBIND11_MODULE(loam_python, m) {
             return occupancy_distance(map, vmin, dims, params, true);
           },
           py::arg("vmin"), py::arg("dims"), py::arg("params") = loam::DistanceParams())
+      .def(
+          "castRays",
+          [](const loam::OccupancyMap& map, const Arr& origins, const Arr& ends, const loam::RaycastParams& params) {
+            if (origins.ndim() != 2 || origins.shape(1) < 3 || ends.ndim() != 2 || ends.shape(0) != origins.shape(0) || ends.shape(1) != origins.shape(1))
+              throw std::runtime_error("origins, ends: expected two (N, 3) arrays of the same shape");
+            const py::ssize_t n = origins.shape(0);
+            py::array records(ray_record_dtype(), std::vector<py::ssize_t>{n});
+            const loamx_raycast_params p = raycast_params(params);
+            loamx_ctx* ctx = loam::gpu::defaultContext();
+            loam::gpu::check(ctx, loamx_occupancy_cast_rays_host(ctx, map.handle(), origins.data(), ends.data(), (size_t)origins.shape(1), (size_t)n, &p,
+                                                                 static_cast<loamx_ray_record*>(records.mutable_data())));
+            return records;
+          },
+          py::arg("origins"), py::arg("ends"), py::arg("params") = loam::RaycastParams())
+      .def(
+          "renderScans",
+          [](const loam::OccupancyMap& map, const Arr& dirs, const Arr& poses, double max_range, const loam::RaycastParams& params) {
+            if (dirs.ndim() != 2 || dirs.shape(1) != 3) throw std::runtime_error("dirs: expected an (n_beams, 3) array");
+            if (poses.ndim() != 2 || poses.shape(1) != 7) throw std::runtime_error("poses: expected an (n_poses, 7) array (qx qy qz qw tx ty tz)");
+            const py::ssize_t nb = dirs.shape(0), np_ = poses.shape(0);
+            Arr scans(std::vector<py::ssize_t>{np_, nb, 3}), ranges(std::vector<py::ssize_t>{np_, nb});
+            py::array records(ray_record_dtype(), std::vector<py::ssize_t>{np_, nb});
+            const loamx_raycast_params p = raycast_params(params);
+            loamx_ctx* ctx = loam::gpu::defaultContext();
+            loam::gpu::check(ctx, loamx_occupancy_render_scans_host(ctx, map.handle(), dirs.data(), (size_t)nb, poses.data(), (size_t)np_, max_range, &p,
+                                                                    scans.mutable_data(), ranges.mutable_data(),
+                                                                    static_cast<loamx_ray_record*>(records.mutable_data())));
+            return py::make_tuple(scans, ranges, records);
+          },
+          py::arg("dirs"), py::arg("poses"), py::arg("max_range"), py::arg("params") = loam::RaycastParams())
       .def("stats", [](const loam::OccupancyMap& map) {
         const loam::OccupancyStats s = map.stats();
         py::dict d;
