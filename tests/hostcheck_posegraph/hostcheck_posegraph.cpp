@@ -180,6 +180,32 @@ int main() {
       return printf("n %llu: cost %g -> %g, termination %u\n", (unsigned long long)n, S.initial_cost, S.final_cost, S.termination), 1;
     for (uint64_t i = 0; i < 7 * n; i++)
       if (!isfinite(poses[i])) return printf("n %llu: a pose is not finite\n", (unsigned long long)n), 1;
+    // the routes around the inner solve: caps of either parity with further iterations, Huber weights, a rejected step (the
+    // start thrown far off), and information that is not positive semi-definite (p.q <= 0, or a pose block without a Cholesky
+    // factor)
+    for (int route = 0; route < 6; route++) {
+      std::vector<double> work = poses;
+      std::vector<PgoEdge> ed = edges;
+      PgoParams Q = P;
+      Q.max_iterations = 4;
+      if (route == 0) Q.max_pcg_iterations = 1;
+      if (route == 1) Q.max_pcg_iterations = 3;
+      if (route == 2) Q.huber_delta = 0.5;
+      if (route >= 2)
+        for (uint64_t i = 1; i < n; i++) {
+          const double d[6] = {1.5 * (rnd() - 0.5), 1.5 * (rnd() - 0.5), 1.5 * (rnd() - 0.5), 3.0 * (rnd() - 0.5), 3.0 * (rnd() - 0.5), 3.0 * (rnd() - 0.5)};
+          double moved[7];
+          hostcheck_pgo_retract(&work[7 * i], d, moved);
+          for (int k = 0; k < 7; k++) work[7 * i + k] = moved[k];
+        }
+      if (route >= 4)
+        for (int k = 0; k < 36; k++) ed.back().info[k] *= route == 4 ? -0.2 : -2.0;
+      hostcheck_pgo_optimize(work.data(), n, nullptr, ed.data(), ed.size(), &Q, &S);
+      if (S.termination > kPgoLambdaOverflow || !(S.final_cost <= S.initial_cost) || S.iterations == 0)
+        return printf("n %llu route %d: cost %g -> %g, termination %u\n", (unsigned long long)n, route, S.initial_cost, S.final_cost, S.termination), 1;
+      for (uint64_t i = 0; i < 7 * n; i++)
+        if (!isfinite(work[i])) return printf("n %llu route %d: a pose is not finite\n", (unsigned long long)n, route), 1;
+    }
     // a bad edge is counted and never followed
     edges[0].b = (uint32_t)n + 5;
     std::vector<double> before = poses;

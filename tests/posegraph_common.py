@@ -1,7 +1,10 @@
 """The rule of the pose-graph optimiser (include/loamx.h, "pose graph") in plain numpy: the pose algebra, the error of an edge,
 chi2, the Huber cost and the retraction, float64 operations one at a time in the header's order (numpy's elementwise loops
-round every operation on its own), so e and chi2 can be compared by bytes. No code shared with the kernels. Also: the
-test graphs, the binding of tests/hostcheck_posegraph and an independent solve by scipy."""
+round every operation on its own), so e and chi2 can be compared by bytes. No code shared with the kernels. Then the part
+between the Jacobians and the final poses: the dense normal equations with their damping in longdouble, the step read back
+from two sets of poses, a dense solve, textbook block-Jacobi PCG and the LM loop, with the checks of one step and of a trace
+that the host-build tests and the device tests share. Also: the test graphs, the binding of tests/hostcheck_posegraph and an
+independent solve by scipy."""
 import ctypes as C
 import os
 import subprocess
@@ -120,6 +123,175 @@ def graph_cost(poses, edges, huber_delta=0.0):
     return float(weight_cost(chi2(edges["information"], edge_errors(poses, edges)), huber_delta)[1].sum())
 
 
+# ---- the model of a step: dense normal equations, PCG and the LM loop (loamx.h: "Normal equations" to "Inner solve") -------------
+LD = np.longdouble
+MIN_DIAGONAL, MIN_LAMBDA, MAX_LAMBDA = 1e-6, 1e-12, 1e12
+
+
+def free_poses(n, fixed=None):
+    """indices of the poses that are variables (fixed None: pose 0 alone is fixed)"""
+    fx = np.zeros(n, dtype=bool)
+    if fixed is None:
+        fx[:1] = True
+    else:
+        fx[:] = np.asarray(fixed) != 0
+    return np.flatnonzero(~fx)
+
+
+def dense_system(poses, edges, fixed, lam, huber_delta, lin, removed=()):
+    """-> (H, g, free): H = sum w J^T Omega J + damping and g = sum w J^T Omega e over the edges, in longdouble, with the rows
+    and columns of the fixed poses (and of `removed`, poses that left the system) dropped; free: the poses that remain, in
+    order. A, B, e and w are the linearisation records `lin`; huber_delta only says which weight they must carry."""
+    n = len(poses)
+    assert len(lin) == len(edges)
+    assert huber_delta > 0.0 or (lin["weight"] == 1.0).all()
+    H, g = np.zeros((6 * n, 6 * n), dtype=LD), np.zeros(6 * n, dtype=LD)
+    om = mirrored(edges["information"]).astype(LD)
+    for k in range(len(edges)):
+        a, b = 6 * int(edges["a"][k]), 6 * int(edges["b"][k])
+        J = np.zeros((6, 6 * n), dtype=LD)
+        J[:, a:a + 6], J[:, b:b + 6] = lin["A"][k], lin["B"][k]
+        cols = np.r_[a:a + 6, b:b + 6]
+        wOJ = LD(lin["weight"][k]) * (om[k] @ J[:, cols])
+        H[np.ix_(cols, cols)] += J[:, cols].T @ wOJ
+        g[cols] += wOJ.T @ lin["e"][k].astype(LD)
+    d = np.diagonal(H).copy()
+    H[np.arange(6 * n), np.arange(6 * n)] = d + LD(lam) * np.maximum(d, LD(MIN_DIAGONAL))
+    free = np.setdiff1d(free_poses(n, fixed), np.asarray(removed, dtype=np.int64))
+    idx = (6 * free[:, None] + np.arange(6)).ravel()
+    return H[np.ix_(idx, idx)], g[idx], free
+
+
+def step_of(poses_before, poses_after):
+    """the increment (n, 6) that the retraction turned into poses_after: D = inv(T) o T', omega = 2 D_xyz / D_w, tau = t_D
+    (longdouble: the poses are float64, the read-back adds no rounding of that size)"""
+    T = tuple(np.asarray(poses_before, dtype=np.float64)[..., k].astype(LD) for k in range(7))
+    U = tuple(np.asarray(poses_after, dtype=np.float64)[..., k].astype(LD) for k in range(7))
+    qi = (-T[0], -T[1], -T[2], T[3])
+    D = quat_mul(qi, U[:4])
+    tau = quat_rotate(qi, tuple(U[4 + k] - T[4 + k] for k in range(3)))
+    return np.stack([LD(2) * D[0] / D[3], LD(2) * D[1] / D[3], LD(2) * D[2] / D[3], tau[0], tau[1], tau[2]], axis=-1)
+
+
+def dense_step(H, g):
+    """x of H x = -g: a float64 solve and one refinement step with the residual formed in longdouble"""
+    H64 = H.astype(np.float64)
+    x = np.linalg.solve(H64, -g.astype(np.float64)).astype(LD)
+    r = -g - H @ x
+    return x + np.linalg.solve(H64, r.astype(np.float64)).astype(LD)
+
+
+def block_inverses(H, dtype=LD):
+    """the inverses of the 6 x 6 diagonal blocks of H in `dtype` (float64 inverse, two Newton steps X <- X + X (I - M X))"""
+    out = []
+    for i in range(0, len(H), 6):
+        M = H[i:i + 6, i:i + 6].astype(dtype)
+        X = np.linalg.inv(M.astype(np.float64)).astype(dtype)
+        for _ in range(2):
+            X = X + X @ (np.eye(6, dtype=dtype) - M @ X)
+        out.append(X)
+    return out
+
+
+def precondition(Minv, r):
+    return np.concatenate([Minv[i] @ r[6 * i:6 * i + 6] for i in range(len(Minv))])
+
+
+def pcg_model(H, g, k, tol, dtype=LD):
+    """Textbook block-Jacobi PCG on H x = -g from x = 0 -> (x, iterations, why): stops at r.z <= tol^2 r0.z0 ("tolerance"),
+    after k iterations ("cap"), or at p.q <= 0, where it keeps x ("curvature")."""
+    H, g = H.astype(dtype), g.astype(dtype)
+    Minv = block_inverses(H, dtype)
+    x, r = np.zeros_like(g), -g
+    z = precondition(Minv, r)
+    p, rz_old, rz0, it = None, None, None, 0
+    while True:
+        rz = r @ z
+        if it == 0:
+            rz0 = rz
+        if not rz > dtype(tol) * dtype(tol) * rz0:
+            return x, it, "tolerance"
+        p = z if it == 0 else z + (rz / rz_old) * p
+        q = H @ p
+        pq = p @ q
+        if not pq > 0:
+            return x, it, "curvature"
+        alpha = rz / pq
+        x, r = x + alpha * p, r - alpha * q
+        z = precondition(Minv, r)
+        rz_old, it = rz, it + 1
+        if it >= k:
+            return x, it, "cap"
+
+
+def residual_ratio(H, g, x):
+    """sqrt(r^T M^-1 r / g^T M^-1 g) with r = -g - H x and M the diagonal blocks of H: the stopping rule on the true residual"""
+    Minv = block_inverses(H)
+    r = -g - H @ x
+    return float(np.sqrt((r @ precondition(Minv, r)) / (g @ precondition(Minv, g))))
+
+
+def preconditioned_condition(H):
+    """the condition number of M^-1/2 H M^-1/2"""
+    H64 = H.astype(np.float64)
+    S = np.zeros_like(H64)
+    for i in range(0, len(H64), 6):
+        w, v = np.linalg.eigh(H64[i:i + 6, i:i + 6])
+        S[i:i + 6, i:i + 6] = (v / np.sqrt(w)) @ v.T
+    ev = np.linalg.eigvalsh(S @ H64 @ S)
+    return float(ev[-1] / ev[0])
+
+
+def energy_distance(H, x, x_ref):
+    """||x - x_ref||_H / ||x_ref||_H"""
+    d = x - x_ref
+    return float(np.sqrt((d @ (H @ d)) / (x_ref @ (H @ x_ref))))
+
+
+def apply_step(poses, free, x):
+    d = np.zeros((len(poses), 6))
+    d[free] = np.asarray(x, dtype=np.float64).reshape(-1, 6)
+    return retract(poses, d)
+
+
+def lm_model(poses, edges, fixed=None, linearize=None, **params):
+    """The outer loop of loamx.h with dense_step as the inner solve and graph_cost for the costs -> one record per iteration:
+    accepted, lambda (after the decision), cost (after it), c0, c1, max_update, termination (None while the solve goes on).
+    linearize(poses, edges, huber_delta) gives the records (default: the host build's)."""
+    P = dict(DEFAULTS)
+    P.update(params)
+    linearize = linearize or host_linearize
+    poses = np.array(poses, dtype=np.float64)
+    lam, hd = P["initial_lambda"], P["huber_delta"]
+    c0 = graph_cost(poses, edges, hd)
+    trace = []
+    for it in range(P["max_iterations"]):
+        H, g, free = dense_system(poses, edges, fixed, lam, hd, linearize(poses, edges, hd))
+        x = dense_step(H, g)
+        cand = apply_step(poses, free, x)
+        c1, m = graph_cost(cand, edges, hd), float(np.abs(x).max())
+        rec = dict(accepted=False, c0=c0, c1=c1, max_update=m, termination=None)
+        if m <= P["step_tolerance"]:
+            rec["termination"] = STEP_CONVERGED
+        elif c1 < c0:
+            rec["accepted"] = True
+            lam = max(lam / 10.0, MIN_LAMBDA)
+            if c0 - c1 <= P["cost_tolerance"] * c0:
+                rec["termination"] = COST_CONVERGED
+            poses, c0 = cand, c1
+        else:
+            lam = 10.0 * lam
+            if lam > MAX_LAMBDA:
+                rec["termination"] = LAMBDA_OVERFLOW
+        if rec["termination"] is None and it + 1 >= P["max_iterations"]:
+            rec["termination"] = MAX_ITERATIONS
+        rec["lambda"], rec["cost"] = lam, c0
+        trace.append(rec)
+        if rec["termination"] is not None:
+            break
+    return trace
+
+
 # ---- test graphs ------------------------------------------------------------------------------------------------------------------
 def rand_quat(rng, max_angle):
     ax = rng.normal(size=3)
@@ -205,6 +377,66 @@ def full_graph(n, seed, sigma_rot=0.01, sigma_t=0.05):
     poses = retract(truth, np.concatenate([0.05 * rng.normal(size=(n, 3)), 0.3 * rng.normal(size=(n, 3))], axis=1))
     poses[0] = truth[0]
     return poses, make_edges(pairs, Z, info), truth
+
+
+def hub_graph(degree, seed):
+    """pose 0 sees every other pose; the others form a chain"""
+    poses, edges, truth = chain_graph(degree + 1, 0, seed)
+    rng = np.random.default_rng(seed + 1)
+    pairs = [(0, i) if i % 3 else (i, 0) for i in range(2, degree + 1)]
+    star = make_edges(pairs, measured(truth, pairs, rng, 0.001, 0.01), np.diag([900.0] * 3 + [200.0] * 3))
+    return poses, np.concatenate([edges, star]), truth
+
+
+def _ring40_fixed():
+    fx = np.zeros(40, np.uint8)
+    fx[[7, 22]] = 1
+    return fx
+
+
+def _ring40_information():
+    poses, edges, _ = chain_graph(40, 3, seed=20, closed=True)
+    rng = np.random.default_rng(21)
+    edges = edges.copy()
+    edges["information"] = np.stack([rand_information(rng) for _ in edges])
+    return poses, edges, None, 0.0
+
+
+def _ring40_outlier():
+    poses, edges, _ = chain_graph(40, 3, seed=20, closed=True)
+    edges = edges.copy()
+    edges["a_T_b"][-1, 4] += 5.0
+    return poses, edges, None, 1.0
+
+
+def _backwards_and_duplicated():
+    poses, edges, truth = chain_graph(20, 4, 8, closed=True)
+    back = make_edges([(8, 7)], measured(truth, [(8, 7)], np.random.default_rng(9)), np.diag([100.0] * 6))  # the reverse of edge 7
+    return poses, np.concatenate([edges, edges[[3, 3, 21]], back]), None, 0.0
+
+
+# the graphs of the step tests -> (poses, edges, fixed, huber_delta)
+STEP_GRAPHS = {
+    "ring12": lambda: chain_graph(12, 2, seed=30, closed=True)[:2] + (None, 0.0),
+    "ring40": lambda: chain_graph(40, 3, seed=20, closed=True)[:2] + (None, 0.0),
+    "ring40_fixed_7_22": lambda: chain_graph(40, 3, seed=20, closed=True)[:2] + (_ring40_fixed(), 0.0),
+    "full8": lambda: full_graph(8, seed=11)[:2] + (None, 0.0),
+    "hub30": lambda: hub_graph(30, 6)[:2] + (None, 0.0),
+    "ring40_information": _ring40_information,
+    "ring40_outlier_huber": _ring40_outlier,
+    "backwards_duplicated": _backwards_and_duplicated,
+    "hub300": lambda: hub_graph(300, 6)[:2] + (None, 0.0),
+}
+
+
+def shaken_ring12(seed=35):
+    """ring12 pushed off by 0.75 rad / 1.5 m per pose: far enough that the first two LM steps are rejected (at 0.5 rad / 1 m
+    the model accepts every step, whatever the seed and the initial lambda)"""
+    poses, edges, _ = chain_graph(12, 2, seed=30, closed=True)
+    rng = np.random.default_rng(seed)
+    poses = poses.copy()
+    poses[1:] = retract(poses[1:], np.concatenate([0.75 * rng.normal(size=(11, 3)), 1.5 * rng.normal(size=(11, 3))], axis=1))
+    return poses, edges
 
 
 def pose_distance(a, b):
@@ -328,3 +560,113 @@ def scipy_solve(poses, edges, fixed=None):
     sol = least_squares(res, np.zeros(6 * len(free)), jac=jac, method="trf", tr_solver="lsmr", tr_options=dict(atol=1e-14, btol=1e-14, maxiter=20000),
                         xtol=1e-15, ftol=1e-15, gtol=1e-15, max_nfev=400)
     return current(sol.x), float(2.0 * sol.cost)
+
+
+# ---- the checks of one LM step, shared by the host-build tests and the device tests ---------------------------------------------
+# Preconditioned residual ratio of the returned step over pcg_tolerance, where PCG ended by tolerance. The recurrence's r.z is
+# below tolerance^2 r0.z0 by construction; the true residual drifts from it by rounding. Measured on the host build, ratio /
+# tolerance at 1e-8: ring12 0.999, ring40 0.573, ring40_fixed_7_22 0.828, full8 0.732, hub30 0.803, ring40_outlier_huber 0.381,
+# backwards_duplicated 0.983, hub300 0.939; at 1e-12 between 0.021 (ring12) and 0.91 (ring40_fixed_7_22). ring40_information
+# stops at its cap of 240 iterations with a ratio of 7.2e-5. The bound leaves a factor 2 over the tolerance itself.
+RATIO_MARGIN = 2.0
+# energy-norm distance to the dense step: ||x - x*||_H <= sqrt(kappa) ratio ||x*||_H (r^T H^-1 r <= r^T M^-1 r / lambda_min and
+# g^T H^-1 g >= g^T M^-1 g / lambda_max of the preconditioned matrix), with a factor 10
+ENERGY_MARGIN = 10.0
+
+
+def check_step(name, poses, edges, fixed, huber_delta, lin, out, summary, pcg_tolerance, cap, removed=()):
+    """One LM step from `poses` (lambda = DEFAULTS' initial_lambda) gave `out` and `summary`: holds it to the dense system built
+    from the records `lin` (without the poses `removed`, which must not move). -> a dict of the figures, "by_tolerance" among them."""
+    H, g, free = dense_system(poses, edges, fixed, DEFAULTS["initial_lambda"], huber_delta, lin, removed)
+    x_ref = dense_step(H, g)
+    c0 = graph_cost(poses, edges, huber_delta)
+    assert graph_cost(apply_step(poses, free, x_ref), edges, huber_delta) < c0, f"{name}: the dense step does not lower the model's cost"
+    assert summary["iterations"] == 1 and summary["accepted"] == 1, f"{name}: the step was rejected: {summary}"
+    assert summary["termination"] == MAX_ITERATIONS
+    x_all = step_of(poses, out)
+    frozen = np.setdiff1d(np.arange(len(poses)), free)
+    assert not np.asarray(x_all[frozen], dtype=np.float64).any(), f"{name}: a pose outside the system moved"
+    x = x_all[free].ravel()
+    assert abs(float(np.abs(x).max()) - summary["max_update"]) <= 1e-9 * summary["max_update"], f"{name}: max_update is not the step's"
+    fig = dict(name=name, pcg_tolerance=pcg_tolerance, pcg_iterations=int(summary["pcg_iterations"]), ratio=residual_ratio(H, g, x),
+               energy=energy_distance(H, x, x_ref), kappa=preconditioned_condition(H), by_tolerance=bool(summary["pcg_iterations"] < cap))
+    print(f"{name} tol {pcg_tolerance:g}: {fig['pcg_iterations']} PCG iterations (cap {cap}), residual ratio {fig['ratio']:.3g} "
+          f"({fig['ratio'] / pcg_tolerance:.3g} of the tolerance), energy distance {fig['energy']:.3g}, kappa {fig['kappa']:.4g}")
+    if fig["by_tolerance"]:
+        assert fig["ratio"] <= RATIO_MARGIN * pcg_tolerance, fig
+        assert fig["energy"] <= ENERGY_MARGIN * pcg_tolerance * np.sqrt(fig["kappa"]), fig
+    else:  # a truncated solve promises a descent step only
+        assert float(g @ x) < 0.0, fig
+        assert summary["final_cost"] < summary["initial_cost"] and graph_cost(out, edges, huber_delta) < c0, fig
+    assert abs(summary["final_cost"] - graph_cost(out, edges, huber_delta)) <= 1e-12 * c0
+    return fig
+
+
+# Truncated steps against pcg_model: 100 times the largest relative difference between pcg_model in float64 and in longdouble
+# over the cases of test_posegraph_hostcheck.py::test_the_truncated_step_is_the_models (ring12 and full8, 1, 2, 3 and 7
+# iterations), measured 1.81e-15 (full8, 7 iterations). The host build's own largest distance is 2.1e-14.
+TRUNCATED_REL_BOUND = 1.81e-13
+
+
+def relative(x, ref):
+    return float(np.abs(x - ref).max() / np.abs(ref).max())
+
+
+# ---- a solve as a sequence of iterations ---------------------------------------------------------------------------------------
+def _same_bytes(a, b):
+    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+def _bytes_of(s):
+    return np.ascontiguousarray(s).tobytes()
+
+
+def prefix_trace(solve, poses, edges, K, **kw):
+    """Solves with max_iterations = 1..K. The prefix property by bytes: a solve of k iterations, continued for one iteration from
+    its poses and its lambda, is the solve of k + 1 iterations (poses, cost, lambda, the counts summed), and a solve that has
+    terminated early is not changed by a larger limit. -> per iteration (accepted, PCG iterations, lambda, cost), termination."""
+    runs = [solve(poses, edges, None, max_iterations=k, **kw) for k in range(1, K + 1)]
+    rows, prev = [], None
+    for k, (out, s) in enumerate(runs, start=1):
+        if prev is not None and prev[1]["termination"] != MAX_ITERATIONS:
+            assert _same_bytes(out, prev[0]) and _bytes_of(s) == _bytes_of(prev[1]), k
+            continue
+        assert s["iterations"] == k
+        if prev is not None:
+            more, sm = solve(prev[0], edges, None, max_iterations=1, **dict(kw, initial_lambda=float(prev[1]["lambda"])))
+            assert _same_bytes(more, out), k
+            assert _bytes_of(sm["initial_cost"]) == _bytes_of(prev[1]["final_cost"]) and _bytes_of(s["initial_cost"]) == _bytes_of(runs[0][1]["initial_cost"])
+            for f in ("final_cost", "lambda", "max_update", "termination"):
+                assert _bytes_of(sm[f]) == _bytes_of(s[f]), (k, f)
+            for f in ("accepted", "pcg_iterations"):
+                assert prev[1][f] + sm[f] == s[f], (k, f)
+        before = prev[1] if prev is not None else dict(accepted=0, pcg_iterations=0)
+        rows.append((int(s["accepted"] - before["accepted"]), int(s["pcg_iterations"] - before["pcg_iterations"]), float(s["lambda"]), float(s["final_cost"])))
+        prev = (out, s)
+    return rows, int(prev[1]["termination"])
+
+
+TRACE_KW = dict(cost_tolerance=0.1, step_tolerance=0.0)
+TRACE_GRAPHS = {
+    "ring12": lambda: STEP_GRAPHS["ring12"]()[:2],
+    "ring40": lambda: STEP_GRAPHS["ring40"]()[:2],
+    "ring12_shaken": shaken_ring12,
+}
+
+
+def check_trace(name, solve, linearize=None, K=8):
+    """the accept / reject sequence, the lambda sequence and the termination of `solve` against lm_model; costs to 100
+    pcg_tolerance relatively. No decision of the model may be marginal: the solver's costs are within 1e-6 of the model's, so
+    the margin of the accept test (|c0 - c1|) and of the convergence test (|c0 - c1 - cost_tolerance c0|) must exceed 1e-4 c0."""
+    poses, edges = TRACE_GRAPHS[name]()
+    model = lm_model(poses, edges, None, linearize=linearize, max_iterations=K, **TRACE_KW)
+    for r in model:
+        assert abs(r["c0"] - r["c1"]) > 1e-4 * r["c0"] and abs(r["c0"] - r["c1"] - TRACE_KW["cost_tolerance"] * r["c0"]) > 1e-4 * r["c0"], r
+    rows, termination = prefix_trace(solve, poses, edges, K, **TRACE_KW)
+    print(name, "model:", "".join("A" if r["accepted"] else "r" for r in model), "solver:", rows, termination)
+    assert [r[0] for r in rows] == [int(r["accepted"]) for r in model]
+    assert [r[2] for r in rows] == [r["lambda"] for r in model]
+    assert termination == model[-1]["termination"]
+    for row, r in zip(rows, model):
+        assert abs(row[3] - r["cost"]) <= 100.0 * DEFAULTS["pcg_tolerance"] * r["cost"], (row, r)
+    return [int(r["accepted"]) for r in model]

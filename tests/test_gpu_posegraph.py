@@ -1,6 +1,8 @@
 """-m gpu: the pose-graph optimiser on the device against the host build of the same header (tests/hostcheck_posegraph: the whole
 solve in the kernels' orders) BY BYTES: linearisation records, final poses and the whole summary, on the smallest graphs at which
-each kernel can go wrong; gauge, information and Huber cases; determinism; refusals; the edge kernel; a drive end to end."""
+each kernel can go wrong; gauge, information and Huber cases; determinism; refusals; the edge kernel; a drive end to end. Then
+one LM step of the device against the dense normal equations built from its own linearisation records, every termination code,
+a rejected step followed by accepted ones against the model's LM loop, and inner solves capped at odd and even counts."""
 import numpy as np
 import pytest
 
@@ -30,13 +32,7 @@ def check(poses, edges, fixed=None, **kw):
     return got, s
 
 
-def hub_graph(degree, seed):
-    """pose 0 sees every other pose; the others form a chain"""
-    poses, edges, truth = G.chain_graph(degree + 1, 0, seed)
-    rng = np.random.default_rng(seed + 1)
-    pairs = [(0, i) if i % 3 else (i, 0) for i in range(2, degree + 1)]
-    star = G.make_edges(pairs, G.measured(truth, pairs, rng, 0.001, 0.01), np.diag([900.0] * 3 + [200.0] * 3))
-    return poses, np.concatenate([edges, star]), truth
+hub_graph = G.hub_graph
 
 
 def shaken(graph, seed):
@@ -274,3 +270,71 @@ def test_a_drive_end_to_end():
     want, ws = G.host_optimize(r["odometry"], r["edges"])
     assert _same(r["corrected"], want) and _same(r["summary"], ws)
     assert np.array_equal(r["edges"]["a"], np.r_[np.arange(11), 0]) and np.array_equal(r["edges"]["b"], np.r_[np.arange(1, 12), 11])
+
+
+# ---- one LM step, the terminations and the trace on the device (the models and figures: tests/posegraph_common.py) ---------------
+ONE_STEP = dict(max_iterations=1, cost_tolerance=0.0, step_tolerance=0.0)
+
+
+def _linearize(poses, edges, huber_delta=0.0):
+    return ctx().pose_graph_linearize(poses, edges, huber_delta)
+
+
+@pytest.mark.parametrize("name", ["ring12", "ring40_fixed_7_22", "ring40_outlier_huber", "hub300"])
+def test_the_device_step_satisfies_the_stopping_rule_and_is_the_dense_step(name):
+    """G.check_step on the device's own poses and its own linearisation records. hub300 (301 poses, 599 edges: two workgroups,
+    chunked sums) ends by tolerance after 47 and 72 of at most 500 PCG iterations."""
+    poses, edges, fixed, hd = G.STEP_GRAPHS[name]()
+    if name == "hub300":
+        assert len(poses) > 256 and len(edges) > 256
+    for tol in (1e-8, 1e-12):
+        out, s = check(poses, edges, fixed, pcg_tolerance=tol, huber_delta=hd, **ONE_STEP)
+        fig = G.check_step(name, poses, edges, fixed, hd, _linearize(poses, edges, hd), out, s, tol, min(500, 6 * len(poses)))
+        assert fig["by_tolerance"]
+
+
+def test_every_termination_code_on_the_device():
+    poses, edges, _ = G.chain_graph(12, 1, seed=30, closed=True)
+    out, s = check(poses, edges)
+    assert s["termination"] == G.COST_CONVERGED and s["accepted"] >= 1 and s["final_cost"] < s["initial_cost"]
+    _, s1 = check(poses, edges, max_iterations=1, cost_tolerance=0.0)
+    assert s1["termination"] == G.MAX_ITERATIONS and s1["iterations"] == 1 and s1["accepted"] == 1
+    # a rejected step leaves the poses as they were
+    far, far_edges = G.shaken_ring12()
+    out0, s0 = check(far, far_edges, **ONE_STEP)
+    assert s0["termination"] == G.MAX_ITERATIONS and s0["accepted"] == 0 and s0["lambda"] == 10.0 * G.DEFAULTS["initial_lambda"] and _same(out0, far)
+    assert s0["final_cost"] == s0["initial_cost"] and s0["pcg_iterations"] >= 1 and s0["max_update"] > 0.0
+    # at the minimum every step is rejected until lambda passes 1e12 ...
+    best, _ = check(poses, edges, max_iterations=100, cost_tolerance=0.0, step_tolerance=0.0, pcg_tolerance=1e-12)
+    out2, s2 = check(best, edges, max_iterations=100, cost_tolerance=0.0, step_tolerance=0.0, initial_lambda=1e9)
+    assert s2["termination"] == G.LAMBDA_OVERFLOW and s2["lambda"] > 1e12 and s2["iterations"] < 100
+    assert s2["accepted"] == 0 and _same(out2, best)
+    # ... unless the step is already below the step tolerance
+    out3, s3 = check(best, edges, step_tolerance=1e-3)
+    assert s3["termination"] == G.STEP_CONVERGED and s3["iterations"] == 1 and s3["accepted"] == 0 and _same(out3, best)
+    assert 0.0 < s3["max_update"] <= 1e-3 and s3["pcg_iterations"] >= 1
+
+
+def test_a_rejected_step_followed_by_an_accepted_one():
+    """the shaken ring12 iteration by iteration (solves of 1 .. 8 iterations, the prefix property between device runs by bytes)
+    against G.lm_model on the device's linearisation records: two rejections, then acceptances"""
+    accepted = G.check_trace("ring12_shaken", check, _linearize)
+    assert accepted[:3] == [0, 0, 1]
+
+
+@pytest.mark.parametrize("name", ["ring12", "hub300"])
+def test_capped_inner_solves_of_both_parities_then_further_iterations(name):
+    """max_pcg_iterations 1, 2, 3, 7: the inner solve stops at its cap with the direction in either of the launcher's two arrays
+    and the state in either copy, and three more LM iterations follow. By bytes against the host build; the first step also
+    against G.pcg_model."""
+    poses, edges, fixed, hd = G.STEP_GRAPHS[name]()
+    H, g, free = G.dense_system(poses, edges, fixed, G.DEFAULTS["initial_lambda"], hd, _linearize(poses, edges, hd))
+    for k in (1, 2, 3, 7):
+        out, s = check(poses, edges, fixed, max_iterations=4, max_pcg_iterations=k)
+        assert s["iterations"] == 4 and s["pcg_iterations"] == 4 * k and s["accepted"] >= 2 and s["final_cost"] < s["initial_cost"]
+        first, s1 = check(poses, edges, fixed, max_pcg_iterations=k, **ONE_STEP)
+        ref, it, why = G.pcg_model(H, g, k, G.DEFAULTS["pcg_tolerance"])
+        d = G.relative(G.step_of(poses, first)[free].ravel(), ref)
+        print(f"{name} k {k}: first step against the model {d:.3g}; {s}")
+        assert (it, why) == (k, "cap") and s1["pcg_iterations"] == k and s1["accepted"] == 1
+        assert d <= G.TRUNCATED_REL_BOUND

@@ -1,6 +1,7 @@
 """CPU-only: the pose-graph optimiser's arithmetic (loam_amd/csrc/posegraph_math.h, built for the host by tests/hostcheck_posegraph
 with a loop that runs the whole solve in the kernels' orders) against the numpy model of the rule (tests/posegraph_common.py),
-against central differences and against an independent solver."""
+against central differences and against an independent solver; and every LM step in between against the model's dense normal
+equations, its PCG and its LM loop."""
 import os
 import subprocess
 
@@ -173,3 +174,92 @@ def test_sanitizer_program():
     subprocess.check_call(["make", "-s", "-C", d, "san"])
     out = subprocess.run([os.path.join(d, "hostcheck_posegraph_san")], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "hostcheck_posegraph ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+
+
+# ---- one LM step against a dense solve of the normal equations -----------------------------------------------------------------
+ONE_STEP = dict(max_iterations=1, cost_tolerance=0.0, step_tolerance=0.0)
+STEP_NAMES = ["ring12", "ring40", "ring40_fixed_7_22", "full8", "hub30", "ring40_information", "ring40_outlier_huber", "backwards_duplicated"]
+
+
+def _one_step(name, tol):
+    poses, edges, fixed, hd = G.STEP_GRAPHS[name]()
+    out, s = G.host_optimize(poses, edges, fixed, pcg_tolerance=tol, huber_delta=hd, **ONE_STEP)
+    return G.check_step(name, poses, edges, fixed, hd, G.host_linearize(poses, edges, hd), out, s, tol, min(G.DEFAULTS["max_pcg_iterations"], 6 * len(poses)))
+
+
+@pytest.mark.parametrize("tol", [1e-8, 1e-12])
+def test_the_step_is_the_dense_step(tol):
+    """A solve of one iteration returns the poses after one step; the step read back from them (G.step_of) must satisfy the
+    documented stopping rule on the TRUE residual of the dense normal equations (G.dense_system, longdouble, from the
+    linearisation records) and lie within the textbook energy-norm bound of their dense solution. See G.check_step and the
+    figures beside G.RATIO_MARGIN. ring40_information runs into the cap of 240 iterations (ratio 7.2e-5): there only a descent
+    step is promised and checked."""
+    figs = [_one_step(name, tol) for name in STEP_NAMES]
+    assert len(figs) == 8
+    by_tol = [f["name"] for f in figs if f["by_tolerance"]]
+    print(f"ended by tolerance at {tol:g}: {by_tol}; largest ratio / tolerance {max([f['ratio'] for f in figs if f['by_tolerance']], default=0.0) / tol:.3g}")
+    if tol == 1e-8:
+        assert len(by_tol) >= 6
+    fig = _one_step("hub300", tol)  # the device tests' graph of more than 256 poses and edges must end by tolerance too
+    assert fig["by_tolerance"] and fig["pcg_iterations"] < 500
+    poses, edges, _, _ = G.STEP_GRAPHS["hub300"]()
+    assert len(poses) > 256 and len(edges) > 256
+
+
+def test_the_truncated_step_is_the_models():
+    worst_ref, worst = 0.0, 0.0
+    for name in ("ring12", "full8"):
+        poses, edges, fixed, hd = G.STEP_GRAPHS[name]()
+        H, g, free = G.dense_system(poses, edges, fixed, G.DEFAULTS["initial_lambda"], hd, G.host_linearize(poses, edges, hd))
+        for k in (1, 2, 3, 7):
+            out, s = G.host_optimize(poses, edges, fixed, max_pcg_iterations=k, **ONE_STEP)
+            ref, it, why = G.pcg_model(H, g, k, G.DEFAULTS["pcg_tolerance"])
+            ref64, it64, _ = G.pcg_model(H, g, k, G.DEFAULTS["pcg_tolerance"], np.float64)
+            assert (it, why, it64) == (k, "cap", k) and s["pcg_iterations"] == k and s["accepted"] == 1
+            d_ref, d = G.relative(ref64, ref), G.relative(G.step_of(poses, out)[free].ravel(), ref)
+            print(f"{name} k {k}: model float64 vs longdouble {d_ref:.3g}, host build vs longdouble {d:.3g}")
+            worst_ref, worst = max(worst_ref, d_ref), max(worst, d)
+            assert d <= G.TRUNCATED_REL_BOUND, (name, k, d)
+    print(f"largest: reference {worst_ref:.3g} (the bound is 100 times 1.81e-15), host build {worst:.3g}")
+    assert 100.0 * worst_ref <= 1.5 * G.TRUNCATED_REL_BOUND  # the constant still is what the reference shows
+
+
+@pytest.mark.parametrize("name", sorted(G.TRACE_GRAPHS))
+def test_the_trace_is_the_models(name):
+    accepted = G.check_trace(name, G.host_optimize)
+    if name == "ring12_shaken":
+        assert accepted[:3] == [0, 0, 1]  # a rejection followed by an acceptance
+
+
+def _indefinite(scale):
+    """ring12 with the information of the closing edge (11 -> 0, pose 0 fixed) scaled by a negative factor"""
+    poses, edges, fixed, hd = G.STEP_GRAPHS["ring12"]()
+    edges = edges.copy()
+    assert (edges["a"][11], edges["b"][11]) == (11, 0)
+    edges["information"][11] *= scale
+    assert np.linalg.eigvalsh(G.mirrored(edges["information"][11]))[0] < 0.0
+    H, g, free = G.dense_system(poses, edges, fixed, G.DEFAULTS["initial_lambda"], hd, G.host_linearize(poses, edges, hd))
+    pd = [bool(np.linalg.eigvalsh(H[i:i + 6, i:i + 6].astype(np.float64))[0] > 0.0) for i in range(0, len(H), 6)]
+    return poses, edges, H, g, free, pd
+
+
+def test_information_that_is_not_positive_semidefinite():
+    """The route exists: with -0.2 times its information on the closing edge every damped pose block of ring12 still has a
+    Cholesky factor, H has a negative eigenvalue, and the model's PCG meets p.q <= 0 in its fourth iteration. The solver must
+    stop there too and keep the x of three iterations. With -0.4 times, the block of pose 11 is no longer positive definite:
+    the pose leaves the system for the iteration, and the step is held to the dense system without it."""
+    poses, edges, H, g, free, pd = _indefinite(-0.2)
+    assert all(pd) and np.linalg.eigvalsh(H.astype(np.float64))[0] < 0.0
+    ref, it, why = G.pcg_model(H, g, 72, G.DEFAULTS["pcg_tolerance"])
+    assert why == "curvature" and it == 3
+    out, s = G.host_optimize(poses, edges, None, **ONE_STEP)
+    assert s["pcg_iterations"] == it
+    d = G.relative(G.step_of(poses, out)[free].ravel(), ref)
+    print(f"stopped at p.q <= 0 after {it} iterations, x against the model {d:.3g}")
+    assert d <= G.TRUNCATED_REL_BOUND
+    poses, edges, H, g, free, pd = _indefinite(-0.4)
+    gone = [int(free[i]) for i in range(len(pd)) if not pd[i]]
+    assert gone == [11]
+    out, s = G.host_optimize(poses, edges, None, **ONE_STEP)
+    fig = G.check_step("ring12 without pose 11", poses, edges, None, 0.0, G.host_linearize(poses, edges), out, s, G.DEFAULTS["pcg_tolerance"], 72, removed=gone)
+    assert fig["by_tolerance"]
