@@ -15,10 +15,10 @@ LIB_PATH = os.path.join(LIB_DIR, "libloamx.so")
 SOURCES = ["api_core.hip", "api_extract.hip", "api_register.hip", "api_sequence.hip", "api_index.hip", "api_comm.hip",
            "extract_kernels.hip", "register_kernels.hip", "synth_kernels.hip", "sequence_kernels.hip", "map_kernels.hip", "info_kernels.hip",
            "api_organize.hip", "organize_kernels.hip", "api_place.hip", "place_kernels.hip", "api_posegraph.hip", "posegraph_kernels.hip",
-           "api_cloudmap.hip", "cloudmap_kernels.hip", "api_segment.hip", "segment_kernels.hip", "api_visibility.hip", "visibility_kernels.hip",
+           "api_cloudmap.hip", "cloudmap_kernels.hip", "listed_kernels.hip", "api_segment.hip", "segment_kernels.hip", "api_visibility.hip", "visibility_kernels.hip",
            "api_occupancy.hip", "occupancy_kernels.hip", "api_surfel.hip", "surfel_kernels.hip", "api_localize.hip", "localize_kernels.hip", "crop_kernels.hip",
            "distance_kernels.hip", "api_raycast.hip", "raycast_kernels.hip"]
-HEADERS = ["api_host.h", "loamx_internal.h", "extract_math.h", "select_rows.h", "reg_math.h", "synth.h", "deskew_math.h", "map_math.h", "info_math.h", "organize_math.h", "place_math.h", "posegraph_math.h", "xcd_map.h", "cloudmap_math.h", "map_compact.h", "segment_math.h", "visibility_math.h", "occupancy_math.h", "voxel_table.h", "api_voxelmap.h", "surfel_math.h", "surfel_slot.h", "api_surfel.h", "localize_math.h", "crop_math.h", "distance_math.h", "occupancy_read.h", "raycast_math.h", "api_occupancy.h", os.path.join("..", "..", "include", "loamx.h")]
+HEADERS = ["api_host.h", "loamx_internal.h", "extract_math.h", "select_rows.h", "reg_math.h", "synth.h", "deskew_math.h", "map_math.h", "info_math.h", "organize_math.h", "place_math.h", "posegraph_math.h", "xcd_map.h", "cloudmap_math.h", "map_compact.h", "segment_math.h", "visibility_math.h", "occupancy_math.h", "voxel_table.h", "api_voxelmap.h", "surfel_math.h", "surfel_slot.h", "api_listedmap.h", "listed_accumulate.h", "localize_math.h", "crop_math.h", "distance_math.h", "occupancy_read.h", "raycast_math.h", "api_occupancy.h", os.path.join("..", "..", "include", "loamx.h")]
 # -ffp-contract=off: the reference's x86-64 build has no FMA; curvature bits must match
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 

@@ -218,8 +218,9 @@ struct TimedScope {
   PendingEvent pe;
   bool on, attach;
   LaunchScope ls;
-  // attach: the events ride on the scope's own kernels (single-stream scopes); otherwise marker events around it
-  TimedScope(loamx_ctx* c, int kernel, double bytes, bool attach_ = false) : ctx(c), on(c->timing), attach(attach_) {
+  // attach: the events ride on the scope's own kernels (single-stream scopes); otherwise marker events around it. kernel < 0:
+  // what the scope holds has no row of its own and is never timed
+  TimedScope(loamx_ctx* c, int kernel, double bytes, bool attach_ = false) : ctx(c), on(c->timing && kernel >= 0), attach(attach_) {
     if (on) {
       pe.kernel = kernel, pe.bytes = bytes;
       if (attach) {

@@ -1,7 +1,7 @@
 // api_localize.hip — surfel localisation (loamx.h, "surfel localisation"): the localiser handle with its one device block (plane
 // cache, partial sums, per-cloud state), the run entry points and their host forms. Every launch of a call is enqueued up front;
 // nothing is read back. On this handle the plain names are the device forms.
-#include "api_surfel.h"
+#include "api_listedmap.h"
 #include "localize_math.h"
 
 struct loamx_surfel_localizer {

@@ -12,7 +12,7 @@ constexpr size_t kOccMaxVoxels = (size_t)1 << 30;
 constexpr unsigned long long kOccMaxRead = 1ull << 31;  // points of a query, voxels of a box
 
 // the clouds of the call chunk by chunk, their rays in launches of kOccChunkRays
-int add_locked(loamx_ctx* ctx, VoxelMapBase* base, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
+int add_locked(loamx_ctx* ctx, VoxelMapBase* base, const VoxelMapKind&, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
                const double* d_poses) {
   loamx_occupancy_map* map = static_cast<loamx_occupancy_map*>(base);
   const bool combine = !(ctx->reg_flags & kRegFlagNoOccupancyCombine);

@@ -1,12 +1,12 @@
-// api_voxelmap.h — the host side that the handles of the cloud map (api_cloudmap.hip) and of the occupancy map
-// (api_occupancy.hip) share: the head of the handle, the checks, clear, crop and destroy, and the two forms of an add around the
-// map's own add_locked. Each map names itself in a VoxelMapKind, so every error text reads as that map's.
+// api_voxelmap.h — the host side that the handles of the three voxel maps share (the cloud map and the surfel map through
+// api_listedmap.h, the occupancy map in api_occupancy.hip): the head of the handle, the checks, clear, crop and destroy, and the two
+// forms of an add around the map's own add_locked. Each map names itself in a VoxelMapKind, so every error text reads as that map's.
 #pragma once
 #include "api_host.h"
 
 namespace loamx {
 
-// a map handle starts with this (loamx_cloud_map and loamx_occupancy_map derive from it)
+// a map handle starts with this (ListedMapBase and loamx_occupancy_map derive from it)
 struct VoxelMapBase {
   loamx_ctx* owner = nullptr;  // the context it was created on: its mutex and stream order every use
   int device = 0;
@@ -21,8 +21,8 @@ struct VoxelMapKind {
   const char *name, *a_name, *items;  // "cloud map", "a cloud map", "points"
   uint64_t max_offered;               // items between two clears
   int ws_in, ws_pose;                 // the workspace the host form of an add uploads to
-  // the map's launches for checked arguments; the caller holds ctx->mu and has selected the device
-  int (*add_locked)(loamx_ctx* ctx, VoxelMapBase* map, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
+  // the map's launches for checked arguments (kind: this record); the caller holds ctx->mu and has selected the device
+  int (*add_locked)(loamx_ctx* ctx, VoxelMapBase* map, const VoxelMapKind& kind, const void* d_points, bool f32, size_t stride, const size_t* offsets, size_t n_clouds,
                     const double* d_poses);
 };
 
@@ -101,7 +101,7 @@ inline int voxel_map_add_dev(loamx_ctx* ctx, VoxelMapBase* map, const VoxelMapKi
   size_t total = 0;
   int rc = voxel_map_add_check(ctx, map, kind, d_points, stride, offsets, n_clouds, &total);
   if (rc != LOAMX_OK || total == 0) return rc;
-  return kind.add_locked(ctx, map, d_points, f32, stride, offsets, n_clouds, d_poses);
+  return kind.add_locked(ctx, map, kind, d_points, f32, stride, offsets, n_clouds, d_poses);
 }
 
 // one cloud in host memory: upload, the device path, synchronise
@@ -119,7 +119,7 @@ inline int voxel_map_add_host(loamx_ctx* ctx, VoxelMapBase* map, const VoxelMapK
   ENSURE(ctx, kind.ws_pose, 7 * sizeof(double));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[kind.ws_in].p, points, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (pose) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws[kind.ws_pose].p, pose, 7 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  rc = kind.add_locked(ctx, map, ctx->ws[kind.ws_in].p, f32, stride, offsets, 1, pose ? wsp<double>(ctx, kind.ws_pose) : nullptr);
+  rc = kind.add_locked(ctx, map, kind, ctx->ws[kind.ws_in].p, f32, stride, offsets, 1, pose ? wsp<double>(ctx, kind.ws_pose) : nullptr);
   if (rc != LOAMX_OK) {
     (void)hipStreamSynchronize(ctx->stream);  // (the upload must not outlive the caller's array)
     return rc;

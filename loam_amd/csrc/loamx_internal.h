@@ -536,7 +536,8 @@ size_t map_compact_ws_bytes(size_t n);
 void launch_map_compact(const double* d_in, const uint8_t* d_keep, uint32_t n, uint32_t* d_tiles, double* d_out, uint32_t* d_src_idx,
                         uint32_t* d_total, const VoxelTable* fix, const uint32_t* d_slot, uint32_t owner_base, hipStream_t s);
 
-/* ---- cloud map (cloudmap_kernels.hip; the rule: cloudmap_math.h and loamx.h) ------------------------------------------------- */
+/* ---- cloud map and the listed voxel table it shares with the surfel map (cloudmap_kernels.hip, listed_kernels.hip,
+ *      listed_accumulate.h; the rule: cloudmap_math.h and loamx.h) --------------------------------------------------------------- */
 constexpr uint32_t kCloudChunkPoints = 1u << 22;  // points per round of launches of an add (its scratch is sized for them at create)
 constexpr uint32_t kRegFlagNoCloudmapCombine = 65536u;  // (loamx_ctx::reg_flags) one claim per point, no run combining
 // counter words of a map: [kCloudUsed .. kCloudOutside] of cloudmap_math.h, then the overflow and the claims (run heads: CAS
@@ -547,23 +548,34 @@ enum { kCloudLenListed = 0, kCloudLenPending = 1, kCloudLens = 4 };
 struct CloudRule {
   double leaf, min_r2, max_r2;
 };
-// Open-addressed table as VoxelTable: 2^log2_cap slots; keys and first start as 0xFF bytes, everything else as zero bytes.
-struct CloudTable {
-  unsigned long long* keys;   // [cap] voxel key (map_math.h) or all ones (empty)
-  uint32_t* first;            // [cap] lowest running index of a point of the voxel
-  unsigned long long* sums;   // [cap][3] sums of the points' 32-bit offsets inside the voxel
-  uint32_t* count;            // [cap]
+// The listed voxel table of the cloud map and of the surfel map. Open-addressed as VoxelTable: 2^log2_cap slots; keys and first start
+// as 0xFF bytes, everything else as zero bytes. The 64-bit words of a slot are its owner's compile-time constant, not a field:
+constexpr uint32_t kCloudSlotWords = 3;    // sums of the points' 32-bit offsets inside the voxel
+constexpr uint32_t kSurfelSlotWords = 12;  // s[3], S[6], W[3] (surfel_math.h: kSurfelMoments)
+struct ListedTable {
+  unsigned long long* keys;     // [cap] voxel key (map_math.h) or all ones (empty)
+  uint32_t* first;              // [cap] lowest running index of a point of the voxel
+  unsigned long long* payload;  // [cap][words of a slot]
+  uint32_t* count;              // [cap]
   uint32_t log2_cap;
   uint32_t max_voxels;
-  uint32_t* list;             // [max_voxels] slots in order of first appearance
-  unsigned long long* words;  // [kCloudWords]
-  uint32_t* lens;             // [kCloudLens]
+  uint32_t* list;               // [max_voxels] slots in order of first appearance
+  unsigned long long* words;    // [kCloudWords]
+  uint32_t* lens;               // [kCloudLens]
 };
-void launch_cloud_accumulate(const void* d_points, bool f32, uint32_t stride, const OrgOffsets& offs, uint32_t n_clouds, unsigned long long p0,
-                             uint32_t n, uint32_t g0, const double* d_poses, const CloudRule& rule, const CloudTable& t, bool combine, uint32_t* d_slot,
-                             hipStream_t s);
-void launch_cloud_list(const CloudTable& t, const uint32_t* d_slot, uint32_t n, uint32_t g0, uint8_t* d_keep, uint32_t* d_tiles, hipStream_t s);
-void launch_cloud_emit(const CloudTable& t, double leaf, uint32_t min_points, uint8_t* d_keep, uint32_t* d_tiles, double* d_xyz_out,
+// Points p0 .. p0 + n - 1 of the call's array (0 < n <= kCloudChunkPoints), which lie in the clouds of `offs`; g0: the running
+// index of point p0; d_poses: the pose of offs' first cloud onwards, or nullptr. d_slot: n words.
+typedef void ListedAccumulate(const void* d_points, bool f32, uint32_t stride, const OrgOffsets& offs, uint32_t n_clouds, unsigned long long p0,
+                              uint32_t n, uint32_t g0, const double* d_poses, const CloudRule& rule, const ListedTable& t, bool combine, uint32_t* d_slot,
+                              hipStream_t s);
+ListedAccumulate launch_cloud_accumulate, launch_surfel_accumulate;
+// behind the accumulate of the same points: their new voxels join the list. d_keep: n bytes; d_tiles: map_compact_ws_bytes(n)
+void launch_listed_list(const ListedTable& t, const uint32_t* d_slot, uint32_t n, uint32_t g0, uint8_t* d_keep, uint32_t* d_tiles, hipStream_t s);
+// the first half of an emit: the flags of the listed voxels with at least min_points points, the tile offsets, *d_n_out their number.
+// d_keep: max_voxels bytes; d_tiles: map_compact_ws_bytes(max_voxels)
+void launch_listed_emit_flags(const ListedTable& t, uint32_t min_points, uint8_t* d_keep, uint32_t* d_tiles, uint32_t* d_n_out, hipStream_t s);
+// the whole emit of the cloud map: the flags, then the centroids. Writes *d_n_out in every case.
+void launch_cloud_emit(const ListedTable& t, double leaf, uint32_t min_points, uint8_t* d_keep, uint32_t* d_tiles, double* d_xyz_out,
                        uint32_t* d_count_out, uint32_t* d_first_out, size_t capacity, uint32_t* d_n_out, hipStream_t s);
 
 /* ---- scan segmentation (segment_kernels.hip; the rule: segment_math.h and loamx.h) ------------------------------------------- */
@@ -628,7 +640,7 @@ enum {
   kOccWordHit = 0, kOccWordInvalid, kOccWordShort, kOccWordLong, kOccWordOutside, kOccWordVisits, kOccWordVoxels, kOccWordClaims,
   kOccWordOverflow, kOccWords = 16
 };
-// Open-addressed table as CloudTable: 2^log2_cap slots; keys start as 0xFF bytes, counts and words as zero bytes.
+// Open-addressed table as ListedTable: 2^log2_cap slots; keys start as 0xFF bytes, counts and words as zero bytes.
 struct OccTable {
   unsigned long long* keys;    // [cap] voxel key (map_math.h) or all ones (empty)
   unsigned long long* counts;  // [cap] hits << 32 | passes
@@ -686,29 +698,13 @@ void launch_raycast_render(const OccTable& t, double leaf, const OccStateRule& s
 
 /* ---- surfel map (surfel_kernels.hip; the rule: surfel_math.h and loamx.h) ----------------------------------------------------------- */
 constexpr uint32_t kRegFlagNoSurfelCombine = 2097152u;  // (loamx_ctx::reg_flags) one claim per point, no run combining
-constexpr uint32_t kSurfelSlotWords = 12;               // 64-bit sums of a slot: s[3], S[6], W[3] (surfel_math.h: kSurfelMoments)
-// Open-addressed table as CloudTable, with the cloud map's counter and length words (kCloudWord*, kCloudLen*): keys and first
-// start as 0xFF bytes, everything else as zero bytes.
-struct SurfelTable {
-  unsigned long long* keys;   // [cap]
-  uint32_t* first;            // [cap] lowest running index of a point of the voxel
-  unsigned long long* mom;    // [cap][kSurfelSlotWords]
-  uint32_t* count;            // [cap]
-  uint32_t log2_cap;
-  uint32_t max_voxels;
-  uint32_t* list;             // [max_voxels] slots in order of first appearance
-  unsigned long long* words;  // [kCloudWords]
-  uint32_t* lens;             // [kCloudLens]
-};
-// the arguments of launch_cloud_accumulate / _list / _emit, on a SurfelTable
-void launch_surfel_accumulate(const void* d_points, bool f32, uint32_t stride, const OrgOffsets& offs, uint32_t n_clouds, unsigned long long p0,
-                              uint32_t n, uint32_t g0, const double* d_poses, const CloudRule& rule, const SurfelTable& t, bool combine, uint32_t* d_slot,
-                              hipStream_t s);
-void launch_surfel_list(const SurfelTable& t, const uint32_t* d_slot, uint32_t n, uint32_t g0, uint8_t* d_keep, uint32_t* d_tiles, hipStream_t s);
-void launch_surfel_emit(const SurfelTable& t, double leaf, uint32_t min_points, uint8_t* d_keep, uint32_t* d_tiles, loamx_surfel* d_out,
+// the table is a ListedTable of kSurfelSlotWords words per slot, with the cloud map's counter and length words; the add is
+// launch_surfel_accumulate and launch_listed_list (above). The whole emit: the flags, then the records (skipped when only the
+// number is asked for). Writes *d_n_out in every case.
+void launch_surfel_emit(const ListedTable& t, double leaf, uint32_t min_points, uint8_t* d_keep, uint32_t* d_tiles, loamx_surfel* d_out,
                         double* d_xyz_out, double* d_normal_out, size_t capacity, uint32_t* d_n_out, hipStream_t s);
 // read-only, behind the adds on the same stream; each output may be nullptr
-void launch_surfel_query(const SurfelTable& t, double leaf, uint32_t min_points, const double* d_points, uint32_t stride, unsigned long long n,
+void launch_surfel_query(const ListedTable& t, double leaf, uint32_t min_points, const double* d_points, uint32_t stride, unsigned long long n,
                          loamx_surfel* d_out, double* d_distance_out, uint32_t* d_count_out, hipStream_t s);
 
 /* ---- surfel localisation (localize_kernels.hip; the rule: localize_math.h and loamx.h) ------------------------------------------- */
@@ -725,12 +721,12 @@ struct LocPartial {
 };
 size_t localize_partials(size_t max_points);  // partials a launch of at most kOrgChunkClouds clouds and max_points points can write
 // the plane cache (cache may be nullptr: the plain form) and the state of the call's n_clouds clouds from d_poses_in
-void launch_localize_planes(const SurfelTable& t, double leaf, uint32_t min_points, double planarity, LocPlane* cache, const double* d_poses_in,
+void launch_localize_planes(const ListedTable& t, double leaf, uint32_t min_points, double planarity, LocPlane* cache, const double* d_poses_in,
                             uint32_t n_clouds, uint32_t max_iterations, LocState* state, hipStream_t s);
 // one evaluation of the clouds of `offs` (at most kOrgChunkClouds, `largest` the points of the largest) at the poses of `state`
 // (the state of offs' first cloud onwards); final_pass: clouds that have stopped are evaluated too
 void launch_localize_accumulate(const void* d_points, bool f32, uint32_t stride, const OrgOffsets& offs, uint32_t n_clouds, unsigned long long largest,
-                                const LocState* state, const LocRule& rule, const SurfelTable& t, const LocPlane* cache, bool final_pass,
+                                const LocState* state, const LocRule& rule, const ListedTable& t, const LocPlane* cache, bool final_pass,
                                 LocPartial* partials, hipStream_t s);
 // behind it: one iteration of the solve per cloud, or (final_pass) the poses, result records and information records (d_info may be
 // nullptr), each from offs' first cloud onwards

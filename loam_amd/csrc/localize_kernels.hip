@@ -35,7 +35,7 @@ static_assert(kLocCounters <= 8, "LocPartial::c holds the counters");
 // held a removed voxel keep the record an earlier call wrote. That is harmless: the cache is rebuilt here for every listed voxel on
 // every call, the accumulate kernel reads a record only at a slot it reached through a key (voxel_find), and every key of a map that
 // has not overflowed is listed.
-__global__ __launch_bounds__(kLocThreads) void localize_planes_kernel(SurfelTable t, double leaf, uint32_t min_points, double planarity,
+__global__ __launch_bounds__(kLocThreads) void localize_planes_kernel(ListedTable t, double leaf, uint32_t min_points, double planarity,
                                                                       LocPlane* __restrict__ cache, const double* __restrict__ poses_in,
                                                                       uint32_t n_clouds, uint32_t max_iterations, LocState* __restrict__ state) {
   const uint32_t j = blockIdx.x * kLocThreads + threadIdx.x;
@@ -94,7 +94,7 @@ __device__ __forceinline__ size_t partial_base(const OrgOffsets& offs, uint32_t 
  * candidate is found and finished in turn (surfel_of_slot), which gives the same bytes through the same functions. */
 template <typename T, bool kPlanes>
 __global__ __launch_bounds__(kLocThreads, kPlanes ? LOAMX_LOC_WAVES : 1) void localize_accumulate_kernel(const T* __restrict__ pts, uint32_t stride, OrgOffsets offs,
-                                                                          const LocState* __restrict__ state, LocRule R, SurfelTable t,
+                                                                          const LocState* __restrict__ state, LocRule R, ListedTable t,
                                                                           const LocPlane* __restrict__ cache, uint32_t final_pass,
                                                                           LocPartial* __restrict__ partials) {
   __shared__ double s_sum[kLocThreads / 64][kInfoSums];
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(64) void localize_step_kernel(OrgOffsets offs, uint
 
 template <typename T, bool kPlanes>
 void accumulate(const void* d_points, uint32_t stride, const OrgOffsets& offs, uint32_t n_clouds, uint32_t chunks, const LocState* state,
-                const LocRule& rule, const SurfelTable& t, const LocPlane* cache, bool final_pass, LocPartial* partials, hipStream_t s) {
+                const LocRule& rule, const ListedTable& t, const LocPlane* cache, bool final_pass, LocPartial* partials, hipStream_t s) {
   launch_kernel((localize_accumulate_kernel<T, kPlanes>), dim3(chunks, n_clouds), dim3(kLocThreads), 0, s, static_cast<const T*>(d_points), stride,
                 offs, state, rule, t, cache, final_pass ? 1u : 0u, partials);
 }
@@ -244,7 +244,7 @@ void accumulate(const void* d_points, uint32_t stride, const OrgOffsets& offs, u
 
 size_t localize_partials(size_t max_points) { return max_points / kLocChunk + kOrgChunkClouds + 1; }
 
-void launch_localize_planes(const SurfelTable& t, double leaf, uint32_t min_points, double planarity, LocPlane* cache, const double* d_poses_in,
+void launch_localize_planes(const ListedTable& t, double leaf, uint32_t min_points, double planarity, LocPlane* cache, const double* d_poses_in,
                             uint32_t n_clouds, uint32_t max_iterations, LocState* state, hipStream_t s) {
   const uint32_t most = cache && t.max_voxels > n_clouds ? t.max_voxels : n_clouds;
   if (most == 0) return;
@@ -253,7 +253,7 @@ void launch_localize_planes(const SurfelTable& t, double leaf, uint32_t min_poin
 }
 
 void launch_localize_accumulate(const void* d_points, bool f32, uint32_t stride, const OrgOffsets& offs, uint32_t n_clouds, unsigned long long largest,
-                                const LocState* state, const LocRule& rule, const SurfelTable& t, const LocPlane* cache, bool final_pass,
+                                const LocState* state, const LocRule& rule, const ListedTable& t, const LocPlane* cache, bool final_pass,
                                 LocPartial* partials, hipStream_t s) {
   const uint32_t chunks = (uint32_t)((largest + kLocChunk - 1) / kLocChunk);
   if (n_clouds == 0 || chunks == 0) return;

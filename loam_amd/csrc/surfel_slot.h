@@ -6,8 +6,8 @@
 
 namespace loamx {
 
-__device__ __forceinline__ loamx_surfel surfel_of_slot(const SurfelTable& t, uint32_t s, uint32_t count, double leaf) {
-  const unsigned long long* w = t.mom + (size_t)s * kSurfelSlotWords;
+__device__ __forceinline__ loamx_surfel surfel_of_slot(const ListedTable& t, uint32_t s, uint32_t count, double leaf) {
+  const unsigned long long* w = t.payload + (size_t)s * kSurfelSlotWords;
   uint64_t sum[3], S[6];
   int64_t W[3];
 #pragma unroll

@@ -211,3 +211,27 @@ def test_cloud_map_scopes(caller_stream):
         for m in maps:
             m.close()
         h.close()
+
+
+@pytest.mark.parametrize("caller_stream", (False, True), ids=("private_stream", "caller_stream"))
+def test_surfel_map_counts_in_no_cloud_scope(caller_stream):
+    """the surfel map runs the cloud map's add loop and list kernels, but has no rows of its own: with timing on, an add and an emit
+    of a surfel map leave all four cloud_* rows (and every other) at zero launches"""
+    h = Harness(caller_stream)
+    m = None
+    try:
+        c = h.ctx
+        c.enable_kernel_timing(True)
+        m = c.surfel_map(max_voxels=1 << 12)
+        m.add_cloud(capi.synth_scan_host(1, 0, 0, 16, 256, 0.01))
+        records, n = m.emit()
+        assert n > 0 and len(records) == n and int(m.stats()["points_used"]) > 0
+        st = c.kernel_stats()
+        assert tuple(st) == SCOPES
+        for name in ("cloud_accumulate_kernel", "cloud_accumulate_plain_kernel", "cloud_list_kernels", "cloud_emit_kernels"):
+            assert st[name]["launches"] == 0, (name, st[name])
+        assert all_zero(st)
+    finally:
+        if m is not None:
+            m.close()
+        h.close()
